@@ -13,7 +13,10 @@ collective (weak scaling: every rank sketches its own 12 500 genomes).
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
-Rank 0 prints ONE JSON line (see README / DESIGN.md "Measurement" for the fields).
+Rank 0 prints ONE JSON line (see README / DESIGN.md "Measurement" for the fields).  A plain run sets up, warms up, times exactly
+--steps steps and prints the headline fields (metric, value, unit, ms_per_step, ...); `--full` adds everything else after the timed
+steps: rooflines, stage times, the packed and pack-first passes, the census, per-rank evidence, the CPU baseline and the oracle
+spot check.  `--dump-outputs DIR` writes the images of the last timed step (a fixed sample of them) as DIR/*.npy.
 """
 import argparse
 import json
@@ -31,6 +34,58 @@ def algorithmic_bytes_per_genome(L, image_bytes, ascii_input):
     """SURVEY.md §8(d), per genome of L surviving bases with an S-byte image: a kernel whose input is the ASCII
     records moves L + S bytes; one whose input is the packed 2-bit form moves ceil(L/4) + S."""
     return (L if ascii_input else (L + 3) // 4) + image_bytes
+
+
+DUMP_BYTES = 64 * 10**6         # --dump-outputs: what the files may hold in all
+
+
+def sample_rows(n, row_bytes, budget):
+    """--dump-outputs: the indices of at most budget // row_bytes of n rows, all of them when they fit, else a fixed seeded choice
+    (the same on every run, so that two builds can be compared output for output), ascending."""
+    import numpy as np
+    m = max(1, budget // max(row_bytes, 1))
+    if n <= m:
+        return np.arange(n, dtype=np.int64)
+    return np.sort(np.random.default_rng(20261015).choice(n, m, replace=False)).astype(np.int64)
+
+
+def dump_outputs(d, arrays):
+    """--dump-outputs DIR: every (name, array) as DIR/<name>.npy — float32 when it holds the values exactly (image bytes), else float64."""
+    import numpy as np
+
+    def exact(a):
+        a = np.asarray(a)
+        return a.astype(np.float32 if a.dtype.itemsize <= 2 and a.dtype.kind in "ui" else np.float64)
+    arrays = {name: exact(a) for name, a in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_BYTES, "--dump-outputs would write %d bytes" % total
+    os.makedirs(d, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(d, name + ".npy"), a)
+
+
+def image_sample(img, budget):
+    """This rank's images [n, image bytes] (a device uint8 tensor), or a seeded sample of their rows: {images, genome_index}."""
+    import torch
+    idx = sample_rows(img.shape[0], img.shape[1] * 4, budget)
+    rows = img.index_select(0, torch.from_numpy(idx).to(img.device)).cpu().numpy()
+    return {"images": rows, "genome_index": idx}
+
+
+def pair_sample(outs, b0, b1, budget):
+    """The defined entries of one triangle pair block — rows [b0, b1) x columns [0, b1), row-major, column <= row (lash_gfx950.h,
+    pair_block) — or a seeded sample of them: {pair_row, pair_col} and every (name, device tensor) of `outs` at those entries."""
+    import numpy as np
+    import torch
+    cnt = np.minimum(b1, b0 + 1 + np.arange(b1 - b0, dtype=np.int64))         # defined columns per row
+    cum = np.cumsum(cnt)
+    idx = sample_rows(int(cum[-1]), 8 * (2 + len(outs)), budget)
+    row = np.searchsorted(cum, idx, side="right")
+    col = idx - (cum[row] - cnt[row])
+    pos = torch.from_numpy(row * b1 + col).to(next(iter(outs.values())).device)
+    got = {"pair_row": b0 + row, "pair_col": col}
+    got.update({name: t.index_select(0, pos).cpu().numpy() for name, t in outs.items()})
+    return got
 
 
 def host_provenance():
@@ -400,6 +455,34 @@ def allpairs_bench(args, ctx, torch, dist, dev, rank, world, algo, k, p, seed, L
     if dist:
         dist.barrier()
     elapsed = time.perf_counter() - t0
+    pairs = N * (N + 1) // 2 * args.steps                 # all ranks' bands together: the printed triangle per step
+
+    def line(elapsed):
+        kmers = G * (L - k + 1) * world * args.steps
+        return {"metric": "k-mers/s sketched + all-vs-all (%s, k=%d)" % (algo, k), "value": kmers / elapsed, "unit": "k-mers/s",
+                "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3,
+                "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u64",
+                "data": "synthetic" if not dist or dist.get_backend() == "nccl" else "synthetic (LAUNCH DRY RUN: ranks share GPUs over gloo, not a scaling measurement)",
+                "config": {"workload": "configs[3] shape: %d synthetic %d-bp genomes per GPU sketched (-a %s -k %d), images all-gathered over "
+                                       "RCCL (%d x %d B), every rank holds them as a resident set and computes its two bands of the lower triangle "
+                                       "(%d of %d rows, equal printed pairs per rank)"
+                                       % (G, L, algo, k, N, ib, sum(b - a for a, b in bands), N), "genomes_per_gpu": G, "genome_length": L, "algo": algo, "k": k, "p": p},
+                "printed_pairs_per_s": pairs / elapsed}
+
+    if args.dump_outputs and rank == 0:
+        # the last timed step's outputs: the gathered images, and its last pair block (what lash_sketch_set_pair_block writes for this algorithm)
+        outs = {"hmh": {"pair_c": o_c, "pair_n": o_n}, "hll": {"pair_zeros": o_c, "pair_sum": o_u}, "ull": {"pair_union": o_u}}[algo]
+        got = image_sample(every, DUMP_BYTES // 2)
+        got.update(pair_sample(outs, blocks[-1][0], blocks[-1][1], DUMP_BYTES // 2 - (1 << 20)))
+        dump_outputs(args.dump_outputs, got)
+    if not args.full:
+        if dist:
+            t = torch.tensor([elapsed], dtype=torch.float64, device=dev if dist.get_backend() == "nccl" else "cpu")
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+            elapsed = float(t.item())
+        if rank == 0:
+            print(json.dumps(line(elapsed)))
+        return
     s = step(timed=True)
     torch.cuda.synchronize()
     stage = {"sketch": ev[0].elapsed_time(ev[1]), "gather": ev[1].elapsed_time(ev[2]), "set + pairs": ev[2].elapsed_time(ev[3])}
@@ -453,22 +536,12 @@ def allpairs_bench(args, ctx, torch, dist, dev, rank, world, algo, k, p, seed, L
     fmt.close()
     s.free()
     if rank == 0:
-        kmers = G * (L - k + 1) * world * args.steps
-        pairs = N * (N + 1) // 2 * args.steps             # all ranks' bands together: the printed triangle per step
-        print(json.dumps({
-            "metric": "k-mers/s sketched + all-vs-all (%s, k=%d)" % (algo, k), "value": kmers / elapsed, "unit": "k-mers/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3,
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u64",
-            "data": "synthetic" if not dist or dist.get_backend() == "nccl" else "synthetic (LAUNCH DRY RUN: ranks share GPUs over gloo, not a scaling measurement)",
-            "config": {"workload": "configs[3] shape: %d synthetic %d-bp genomes per GPU sketched (-a %s -k %d), images all-gathered over "
-                                   "RCCL (%d x %d B), every rank holds them as a resident set and computes its two bands of the lower triangle "
-                                   "(%d of %d rows, equal printed pairs per rank)"
-                                   % (G, L, algo, k, N, ib, sum(b - a for a, b in bands), N), "genomes_per_gpu": G, "genome_length": L, "algo": algo, "k": k, "p": p},
-            "printed_pairs_per_s": pairs / elapsed, "stage_ms_rank0": stage, "ranks": evidence,
+        print(json.dumps(dict(line(elapsed), **{
+            "stage_ms_rank0": stage, "ranks": evidence,
             "host_side": {"cardinalities_s_all_sketches": card_s, "rows_to_text_pairs_per_s_this_rank": host_pairs_per_s, "threads": threads,
                           "note": "lash_dist_rows + row text in C++ (liblash_host.so), outside the timed step: a full run's wall time is "
                                   "bounded by this, not by the GPU (profiles/r03/config3_full_one_gpu.log)"},
-            "roofline": None, "cpu_baseline": None}))
+            "roofline": None, "cpu_baseline": None})))
 
 
 def cli_bench(args):
@@ -625,12 +698,23 @@ def main():
     ap.add_argument("--no-parity-check", action="store_true")
     ap.add_argument("--no-ubench", action="store_true", help="do not run tools/ubench_hash for the VALU ceiling (profiler runs: "
                     "rocprofv3 follows child processes); the committed profiles/valu.json figure is quoted instead")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also measure and check what the headline does not need: the "
+                    "rooflines (HBM, VALU issue: tools/ubench_hash), stage times, the packed-resident and pack-first passes, the k-mer census, "
+                    "per-rank evidence, the CPU baseline and the parity spot check against the oracle; allpairs: per-stage times, the collective "
+                    "alone and the host side.  Without it a run sets up, warms up, times --steps steps and prints the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the timed path computed in its last step (rank 0's) "
+                    "as DIR/<name>.npy, float32 / float64, at most 64 MB in all: the sketch images (a fixed, seeded sample of the genomes "
+                    "when they do not fit) and genome_index, their rows; allpairs adds the last pair block's defined entries")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(self_launch(args.gpus))
     if args.workload == "cli":                              # (cli: `lash sketch` from files on tmpfs, one GPU; see cli_bench)
         assert args.gpus == 1, "--workload cli runs the command line on one GPU (it takes -d for more)"
+        if args.dump_outputs:
+            ap.error("--dump-outputs: --workload cli's output is the sketches file `lash sketch` writes; the other workloads dump theirs")
         if args.genomes == 12500:
             args.genomes = 1000                             # configs[1] size unless asked otherwise
         return cli_bench(args)
@@ -763,7 +847,8 @@ def main():
     torch.cuda.synchronize()
     if dist:
         dist.barrier()
-    ctx.enable_timing(True)                   # HIP events on the stream the kernels run on
+    if args.full:
+        ctx.enable_timing(True)               # HIP events on the stream the kernels run on
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
@@ -772,15 +857,43 @@ def main():
     if dist:
         dist.barrier()
     elapsed = time.perf_counter() - t0
-    tm = ctx.timing()
-    ctx.enable_timing(False)
-    evidence = rank_evidence(torch, dist, dev, rank, world, local_rank,
-                             {"elapsed_ms": elapsed / args.steps * 1e3, "sketch_ms": tm["sketch_ms"] / max(tm["calls"], 1),
-                              "kmers_census": int(tm["kmers"]), "first_genome": int(first)})
+    if args.dump_outputs and rank == 0:                     # (here: --full's later passes write d_img again)
+        dump_outputs(args.dump_outputs, image_sample(d_img.view(G, ib), DUMP_BYTES - (1 << 20)))
+    if args.full:
+        tm = ctx.timing()
+        ctx.enable_timing(False)
+        evidence = rank_evidence(torch, dist, dev, rank, world, local_rank,
+                                 {"elapsed_ms": elapsed / args.steps * 1e3, "sketch_ms": tm["sketch_ms"] / max(tm["calls"], 1),
+                                  "kmers_census": int(tm["kmers"]), "first_genome": int(first)})
     if dist:
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev if dist.get_backend() == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+
+    kmers_step_rank = viral_kmers if viral else G * kmers_per_genome
+    total_kmers = kmers_step_rank * world * args.steps
+    value = total_kmers / elapsed
+    line = {
+        "metric": "k-mers/s sketched (%s, k=%d)" % (algo, k), "value": value, "unit": "k-mers/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3,
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u64",
+        "data": "synthetic" if not dist or dist.get_backend() == "nccl" else "synthetic (LAUNCH DRY RUN: ranks share GPUs over gloo, not a scaling measurement)",
+        "config": {"workload": ("ONE sketch of %d synthetic 150-bp records (%d bp) per GPU" % (n_rec, L) if reads else
+                                ("%d synthetic genomes of 3..300 kbp (log-uniform, mean %d bp, %.2f GB), 1..4 records each, per GPU%s" % (G, L, v_total / 1e9, "")) if viral else
+                                "%d synthetic %d-bp genomes per GPU%s" % (G, L, {"none": "", "nrun": ", one 100-byte N run in each",
+                                                                                 "lower": ", every other 10 kb block lower-case"}[args.dirty]))
+                               + ", -a %s -k %d%s, seed %d, ASCII records resident in HBM -> sketch images in HBM "
+                                 "(lash_sketch_batch_device: filter_out_n + k-mers + xxh3 + registers + images)"
+                               % (algo, k, "" if algo == "hmh" else " -p %d" % p, seed),
+                   "genomes_per_gpu": G, "genome_length": L, "records_per_gpu": n_rec, "dirty": args.dirty,
+                   "algo": algo, "k": k, "p": p, "sharding": "genomes across ranks", "layout": args.layout or "default"}}
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(line))
+        ctx.close()
+        if dist:
+            dist.destroy_process_group()
+        return
 
     # informational: the same batch kept resident as 2-bit (lash_pack_device once, then only the sketch + finalize stages)
     pk = ctx.pack_device(d_seq, d_rec, n_rec, goff, rec_off)
@@ -811,10 +924,7 @@ def main():
     del d_img2
     assert routes_agree, "direct and pack-first routes disagree"
 
-    kmers_step_rank = viral_kmers if viral else G * kmers_per_genome
     assert tm["kmers"] == kmers_step_rank * args.steps, "device k-mer census disagrees with the workload"
-    total_kmers = kmers_step_rank * world * args.steps
-    value = total_kmers / elapsed
 
     out = None
     if rank == 0:
@@ -840,20 +950,7 @@ def main():
                 traffic = tj.get(key, {}).get("hbm_bytes_per_launch") if args.dirty == "none" and not args.layout else None   # (the counter passes are of the clean workload under the default layout)
             except Exception:
                 traffic = None
-        out = {
-            "metric": "k-mers/s sketched (%s, k=%d)" % (algo, k), "value": value, "unit": "k-mers/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3,
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u64",
-            "data": "synthetic" if not dist or dist.get_backend() == "nccl" else "synthetic (LAUNCH DRY RUN: ranks share GPUs over gloo, not a scaling measurement)",
-            "config": {"workload": ("ONE sketch of %d synthetic 150-bp records (%d bp) per GPU" % (n_rec, L) if reads else
-                                    ("%d synthetic genomes of 3..300 kbp (log-uniform, mean %d bp, %.2f GB), 1..4 records each, per GPU%s" % (G, L, v_total / 1e9, "")) if viral else
-                                    "%d synthetic %d-bp genomes per GPU%s" % (G, L, {"none": "", "nrun": ", one 100-byte N run in each",
-                                                                                     "lower": ", every other 10 kb block lower-case"}[args.dirty]))
-                                   + ", -a %s -k %d%s, seed %d, ASCII records resident in HBM -> sketch images in HBM "
-                                     "(lash_sketch_batch_device: filter_out_n + k-mers + xxh3 + registers + images)"
-                                   % (algo, k, "" if algo == "hmh" else " -p %d" % p, seed),
-                       "genomes_per_gpu": G, "genome_length": L, "records_per_gpu": n_rec, "dirty": args.dirty,
-                       "algo": algo, "k": k, "p": p, "sharding": "genomes across ranks", "layout": args.layout or "default"},
+        out = dict(line, **{
             "roofline": {"bound": "hbm", "kernel": ("sketch_kernel<DIRECT> + stream_sketch_kernel (sketch stage)" if dirty_in else ("sketch_kernel<DIRECT, DEFER>" if defer else "sketch_kernel<DIRECT>")) if direct or dirty_in else ("sole_sketch_kernel (whole genomes on persistent workgroups, ASCII in)" if sole else "sketch_kernel"), "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
                          "traffic_source": "profiles/traffic.json: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this workload, committed (not collected in this run)" if traffic else None,
@@ -883,7 +980,7 @@ def main():
                 "pack_roofline": {"bound": "hbm", "kernel": "pack_lookback_kernel", "unit": "GB/s", "peak": HBM_PEAK_GBS,
                                   "achieved": G * (L + (L + 3) // 4) / (tm_pf["pack_ms"] / 3 * 1e-3) / 1e9,
                                   "frac": (alg_bytes_of(True) + alg_bytes_of(False) - 2 * G * ib) / (tm_pf["pack_ms"] / 3 * 1e-3) / 1e9 / HBM_PEAK_GBS}},
-        }
+        })
 
     if rank == 0 and args.layout:
         out["roofline_valu"]["layout_note"] = ("--layout %s: the issue ceiling and the committed instruction count quoted here are the DEFAULT rule's "

@@ -132,3 +132,35 @@ def test_rank_evidence_over_gloo_world_size_3():
     import torch
     one = _bench().rank_evidence(torch, None, torch.device("cpu"), 0, 1, 0, {"elapsed_ms": 5.0})
     assert one["ranks_seen"] == 1 and one["per_rank_ms"] == [5.0] and one["imbalance"] == 1.0 and one["devices_distinct"] == 1
+
+
+def test_dumped_outputs_are_seeded_bounded_and_exact(tmp_path):
+    """--dump-outputs: all rows when they fit, else the same seeded sample on every run; values exact in float32 / float64; at most 64 MB;
+    of a triangle pair block only the defined entries (column <= row), each at its own row and column."""
+    import numpy as np
+    import torch
+    b = _bench()
+    assert list(b.sample_rows(5, 100, 1000)) == [0, 1, 2, 3, 4]
+    budget = b.DUMP_BYTES - (1 << 20)
+    a = b.sample_rows(12500, 32768 * 4, budget)
+    assert len(a) == budget // (32768 * 4) and np.all(np.diff(a) > 0) and 0 <= a[0] and a[-1] < 12500
+    assert np.array_equal(a, b.sample_rows(12500, 32768 * 4, budget))
+    img = torch.arange(600 * 50, dtype=torch.int64).remainder(251).to(torch.uint8).view(600, 50)
+    got = b.image_sample(img, 50 * 4 * 100)
+    assert len(got["genome_index"]) == 100 and np.array_equal(got["images"], img.numpy()[got["genome_index"]])
+    b0, b1 = 3, 7
+    ent = torch.arange((b1 - b0) * b1, dtype=torch.float64)
+    pairs = b.pair_sample({"pair_u": ent, "pair_c": ent.to(torch.int32)}, b0, b1, 1 << 20)
+    assert len(pairs["pair_row"]) == sum(min(b1, r + 1) for r in range(b0, b1))
+    assert np.all(pairs["pair_col"] <= pairs["pair_row"]) and np.all(pairs["pair_u"] == (pairs["pair_row"] - b0) * b1 + pairs["pair_col"])
+    few = b.pair_sample({"pair_u": ent}, b0, b1, 3 * 8 * 5)
+    assert len(few["pair_row"]) == 5 and np.all(few["pair_u"] == (few["pair_row"] - b0) * b1 + few["pair_col"])
+    d = str(tmp_path / "out")
+    b.dump_outputs(d, dict(got, **pairs))
+    back = {f[:-4]: np.load(os.path.join(d, f)) for f in os.listdir(d)}
+    assert back["images"].dtype == np.float32 and back["pair_c"].dtype == back["genome_index"].dtype == back["pair_u"].dtype == np.float64
+    assert np.array_equal(back["images"], got["images"]) and np.array_equal(back["pair_c"], pairs["pair_c"])
+    import pytest
+    with pytest.raises(AssertionError, match="would write"):
+        b.dump_outputs(d, {"big": np.zeros(b.DUMP_BYTES // 8 + 1)})
+    assert len(os.listdir(d)) == len(back)

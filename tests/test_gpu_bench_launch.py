@@ -46,7 +46,7 @@ def test_two_ranks_dry_run_on_one_gpu():
     env = dict(os.environ, LASH_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     env.pop("WORLD_SIZE", None)
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-                        "--master-port", str(port), "bench.py", "--gpus", "2", "--steps", "3", "--warmup", "1", "--genomes", "40"],
+                        "--master-port", str(port), "bench.py", "--gpus", "2", "--steps", "3", "--warmup", "1", "--genomes", "40", "--full"],
                        cwd=ROOT, capture_output=True, text=True, env=env, timeout=900)
     _check_line(r)
 
@@ -57,7 +57,7 @@ def test_plain_command_line_launches_its_own_ranks():
     env = dict(os.environ, LASH_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     for v in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(v, None)
-    r = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--steps", "3", "--warmup", "1", "--genomes", "40"],
+    r = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--steps", "3", "--warmup", "1", "--genomes", "40", "--full"],
                        cwd=ROOT, capture_output=True, text=True, env=env, timeout=900)
     _check_line(r)
 
@@ -77,14 +77,14 @@ def test_every_workload_rehearses_with_two_ranks():
     for v in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(v, None)
     r = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--steps", "2", "--warmup", "1", "--workload", "reads", "--algo", "ull", "-p", "12",
-                        "--reads", "2000000"], cwd=ROOT, capture_output=True, text=True, env=env, timeout=900)
+                        "--reads", "2000000", "--full"], cwd=ROOT, capture_output=True, text=True, env=env, timeout=900)
     j = _one_line(r)
     assert j["n_gpus"] == 2 and "DRY RUN" in j["data"] and j["cpu_baseline"] is None
     assert abs(j["value"] * j["ms_per_step"] * 1e-3 * 2 / (2 * 2_000_000 * (150 - 16 + 1) * 2) - 1) < 1e-6
     _check_ranks(j, 2)
     assert [q["kmers_census"] for q in j["ranks"]["per_rank"]] == [2_000_000 * (150 - 16 + 1) * 2] * 2      # every rank's device census
     r = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--steps", "2", "--warmup", "1", "--workload", "allpairs", "--genomes", "300",
-                        "--length", "200000"], cwd=ROOT, capture_output=True, text=True, env=env, timeout=900)
+                        "--length", "200000", "--full"], cwd=ROOT, capture_output=True, text=True, env=env, timeout=900)
     j = _one_line(r)
     assert j["n_gpus"] == 2 and "DRY RUN" in j["data"] and j["printed_pairs_per_s"] > 0
     assert set(j["stage_ms_rank0"]) == {"sketch", "gather", "set + pairs"}
@@ -124,7 +124,7 @@ def test_the_viral_workload_prints_the_same_contract():
     env = dict(os.environ)
     for v in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "LASH_BENCH_BACKEND", "LASH_SOLE_MAX"):
         env.pop(v, None)
-    r = subprocess.run([sys.executable, "bench.py", "--workload", "viral", "--genomes", "3000", "--steps", "3", "--warmup", "1", "--cpu-seconds", "1"],
+    r = subprocess.run([sys.executable, "bench.py", "--workload", "viral", "--genomes", "3000", "--steps", "3", "--warmup", "1", "--cpu-seconds", "1", "--full"],
                        cwd=ROOT, capture_output=True, text=True, env=env, timeout=900)
     j = _one_line(r)
     assert j["n_gpus"] == 1 and j["unit"] == "k-mers/s" and "3..300 kbp" in j["config"]["workload"]
@@ -140,10 +140,37 @@ def test_the_layout_flag_reproduces_the_line_on_an_alternative_rule():
     for v in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "LASH_BENCH_BACKEND"):
         env.pop(v, None)
     for spec in ("hmh_x=low", "kmer=lsb"):
-        r = subprocess.run([sys.executable, "bench.py", "--genomes", "300", "--steps", "2", "--warmup", "1", "--cpu-seconds", "1", "--layout", spec],
+        r = subprocess.run([sys.executable, "bench.py", "--genomes", "300", "--steps", "2", "--warmup", "1", "--cpu-seconds", "1", "--layout", spec, "--full"],
                            cwd=ROOT, capture_output=True, text=True, env=env, timeout=900)
         j = _one_line(r)
         assert j["config"]["layout"] == spec and j["parity_vs_oracle"].startswith("bit-identical"), j.get("parity_vs_oracle")
         assert j["roofline"]["kernel"] == "sketch_kernel<DIRECT, DEFER>" and j["roofline"]["traffic"] is None      # x = low defers like the default
         assert j["ranks"]["ranks_seen"] == 1 and j["ranks"]["devices_distinct"] == 1 and "layout_note" in j["roofline_valu"]
         assert abs(j["value"] * j["ms_per_step"] * 1e-3 / (300 * (5_000_000 - 16 + 1)) - 1) < 1e-6
+
+
+def test_a_plain_run_prints_the_headline_and_dumps_its_last_step(tmp_path):
+    """Without --full a run only times its steps: the line carries the headline fields and nothing measured after them.
+    --dump-outputs writes the last timed step's images; two runs with the same arguments write the same arrays, and they are the oracle's."""
+    import numpy as np
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import oracle_lib as O
+    env = dict(os.environ)
+    for v in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "LASH_BENCH_BACKEND"):
+        env.pop(v, None)
+    dumps = []
+    for run in range(2):
+        d = str(tmp_path / ("out%d" % run))
+        r = subprocess.run([sys.executable, "bench.py", "--genomes", "40", "--length", "200000", "--steps", "3", "--warmup", "1", "--dump-outputs", d],
+                           cwd=ROOT, capture_output=True, text=True, env=env, timeout=900)
+        j = _one_line(r)
+        assert j["steps"] == 3 and j["warmup"] == 1 and j["unit"] == "k-mers/s" and j["higher_is_better"] is True and j["dtype"] == "u64"
+        assert abs(j["value"] * j["ms_per_step"] * 1e-3 * 3 / (40 * (200_000 - 16 + 1) * 3) - 1) < 1e-6
+        assert not {"roofline", "roofline_valu", "cpu_baseline", "parity_vs_oracle", "ranks", "routes_agree"} & set(j)
+        dumps.append({f[:-4]: np.load(os.path.join(d, f)) for f in sorted(os.listdir(d))})
+    a, b = dumps
+    assert set(a) == {"images", "genome_index"} and a["images"].dtype == np.float32 and a["images"].shape == (40, 32768)
+    assert all(np.array_equal(a[n], b[n]) for n in a) and list(a["genome_index"]) == list(range(40))
+    for g in (0, 39):
+        want = O.sketch_genomes(O.HMH, 16, 0, 42, O.synth_genome(g, 200_000), np.array([0, 200_000], np.uint64), np.array([0, 1], np.uint64))[0]
+        assert np.array_equal(a["images"][g], want.astype(np.float32))

@@ -7,7 +7,7 @@ import json
 d=json.load(open('gpurun_out/d_$name.json'))
 print('$name', '%.4g' % d['value'], '%.3f ms' % d['ms_per_step'], 'kernel %.3f ms' % d['roofline']['avg_launch_ms'], 'frac %.4f' % d['roofline']['frac'], d.get('routes_agree'))
 "; }
-C="--no-cpu-baseline --no-ubench"
+C="--full --no-cpu-baseline --no-ubench"
 for df in -1 0; do
 export LASH_DEFER_MIN=$df
 run m${df}_L1M python bench.py --genomes 12000 --length 1000000 $C

@@ -3,7 +3,7 @@ import json,sys
 d=json.loads(sys.stdin.read())
 print('$name', '%.4g' % d['value'], '%.3f ms' % d['ms_per_step'], 'kernel %.3f ms' % d['roofline']['avg_launch_ms'], 'frac %.4f' % d['roofline']['frac'], d['roofline']['kernel'])
 "; }
-C="--no-cpu-baseline --no-ubench --no-parity-check"
+C="--full --no-cpu-baseline --no-ubench --no-parity-check"
 for g in 1000 600 300 100; do
 run g${g}_default python bench.py --genomes $g $C
 LASH_DEFER_MIN=0 run g${g}_defer_all python bench.py --genomes $g $C

@@ -5,7 +5,7 @@ import json,sys
 d=json.loads(sys.stdin.read())
 print('$name', '%.4g' % d['value'], '%.3f ms' % d['ms_per_step'], 'kernel %.3f ms' % d['roofline']['avg_launch_ms'], 'frac %.4f' % d['roofline']['frac'])
 "; }
-C="--no-cpu-baseline --no-ubench --no-parity-check --steps 10 --warmup 2"
+C="--full --no-cpu-baseline --no-ubench --no-parity-check --steps 10 --warmup 2"
 for spec in "60000 200000" "40000 300000" "30000 400000" "24000 500000" "20000 600000" "16000 750000" "12000 1000000" "6000 2000000"; do
     set -- $spec
     LASH_DEFER_MIN=0 run L$2_defer python bench.py --genomes $1 --length $2 $C

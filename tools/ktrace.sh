@@ -2,7 +2,7 @@
 # tools/ktrace.sh <tag> [bench args] — rocprofv3 kernel trace of bench.py, per-kernel average durations (GPU box)
 TAG=${1:-kt}; shift
 REPO=$(pwd); OUT=$REPO/gpurun_out/prof_$TAG; mkdir -p "$OUT"; export TMPDIR=/tmp; cd /tmp
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -- python3 $REPO/bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-parity-check "$@" > "$OUT/trace.log" 2>&1
+timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -- python3 $REPO/bench.py --steps 5 --warmup 2 --full --no-cpu-baseline --no-parity-check "$@" > "$OUT/trace.log" 2>&1
 cd $REPO
 python3 - "$OUT" <<'PY'
 import csv, glob, sys, collections

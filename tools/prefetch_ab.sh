@@ -6,7 +6,7 @@ import json
 d=json.load(open('gpurun_out/p_$name.json'))
 print('$name', '%.4g' % d['value'], '%.3f ms' % d['ms_per_step'], 'kernel %.3f ms' % d['roofline']['avg_launch_ms'], 'frac %.4f' % d['roofline']['frac'], d['roofline']['kernel'], d.get('routes_agree','')[:40])
 "; }
-C="--no-cpu-baseline --no-ubench"
+C="--full --no-cpu-baseline --no-ubench"
 LASH_DEFER_MIN=-1 run plain_g2500 python bench.py --genomes 2500 $C
 run defer_g2500 python bench.py --genomes 2500 $C
 run cfg1 python bench.py --genomes 1000 $C

@@ -3,7 +3,7 @@ import json,sys
 d=json.loads(sys.stdin.read())
 print('$name', '%.4g' % d['value'], '%.3f ms' % d['ms_per_step'], 'kernel %.3f ms' % d['roofline']['avg_launch_ms'], 'frac %.4f' % d['roofline']['frac'], d['roofline']['kernel'])
 "; }
-C="--no-cpu-baseline --no-ubench --no-parity-check"
+C="--full --no-cpu-baseline --no-ubench --no-parity-check"
 for g in 40 150 300 600 1000 1500 2400; do
 LASH_SLICE_FACTOR=4 run g${g}_sf4 python bench.py --genomes $g $C
 run g${g}_new python bench.py --genomes $g $C

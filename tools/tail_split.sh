@@ -7,7 +7,7 @@ import json
 d=json.load(open('gpurun_out/g_$name.json'))
 print('$name', '%.4g' % d['value'], '%.3f ms' % d['ms_per_step'], 'kernel %.3f ms' % d['roofline']['avg_launch_ms'], 'frac %.4f' % d['roofline']['frac'])
 "; }
-C="--no-cpu-baseline --no-ubench"
+C="--full --no-cpu-baseline --no-ubench"
 for ts in 1 4; do
 export LASH_TAIL_SPLIT=$ts
 for g in 40 150 300 600 1200 2400; do run ts${ts}_g$g python bench.py --genomes $g $C; done
