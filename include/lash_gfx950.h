@@ -377,6 +377,20 @@ int      lash_sketch_set_pair_block(lash_ctx *ctx, const lash_sketch_set *ref, u
 int      lash_sketch_set_pair_block_device(lash_ctx *ctx, const lash_sketch_set *ref, uint32_t r0, uint32_t r1, const lash_sketch_set *qry,
                                            uint32_t n_cols, int triangle, int ull_estimator, uint32_t *d_c_or_zero, uint32_t *d_n,
                                            double *d_sum_or_union);
+/* pair_block_within: `lash dist --max-dist`.  The same block as pair_block, but what comes back is only its pairs whose distance d
+ * (lash_dist_rows' number, before the "same name -> 0" rule, which is the caller's) passes d <= max_dist; NaN never passes.  The pair
+ * statistics, HyperMinHash's expected collisions of small pairs and a filter kernel run on the device; only the candidates the filter
+ * lets through are copied back, and each is evaluated here exactly as lash_dist_rows evaluates it.  Survivors are written in (row,
+ * col) order — out_row[i] is the set row (r0 <= row < r1), out_col[i] the column, out_dist[i] d — the first `cap` of them; *n_kept
+ * is their full count (> cap: call again with larger buffers; the result is deterministic).  n_candidates (may be NULL): how many
+ * pairs the filter kernel passed to the host.  LASH_ERANGE with *bad_pair = (row - r0) * n_cols + col of the first such pair in
+ * (row, col) order exactly when lash_dist_rows would refuse the block (an HLL union in the bias-table regime that `tables` does
+ * not cover).  Needs lash_sketch_set_cardinalities on both sets; prepare as for pair_block.  triangle / n_cols as pair_block;
+ * k, model, fp32, tables as lash_dist_rows.  max_dist NaN: LASH_EINVAL. */
+int      lash_sketch_set_pair_block_within(lash_ctx *ctx, const lash_sketch_set *ref, uint32_t r0, uint32_t r1, const lash_sketch_set *qry,
+                                           uint32_t n_cols, int triangle, int k, int model, int fp32, int ull_estimator,
+                                           const lash_hll_bias *tables, double max_dist, uint32_t *out_row, uint32_t *out_col,
+                                           double *out_dist, uint64_t cap, uint64_t *n_kept, uint64_t *bad_pair, uint64_t *n_candidates);
 
 /* HyperMinHash sets: hyperminhash's expected_collisions(n, m) for the pairs of a block in which BOTH sketches hold at most 2^19
  * distinct k-mers (the regime in which the crate walks 65 536 cells per pair; lash_hmh_pair_expected_collisions below):

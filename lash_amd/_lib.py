@@ -104,6 +104,8 @@ PROTOTYPES = {
     "lash_sketch_set_hmh_expected_collisions": (_int, [_vp, _vp, _u32, _u32, _vp, _u32, _vp, C.POINTER(_u64)]),
     "lash_sketch_set_pair_block": (_int, [_vp, _vp, _u32, _u32, _vp, _u32, _int, _int, _vp, _vp, _vp]),
     "lash_sketch_set_pair_block_device": (_int, [_vp, _vp, _u32, _u32, _vp, _u32, _int, _int, _vp, _vp, _vp]),
+    "lash_sketch_set_pair_block_within": (_int, [_vp, _vp, _u32, _u32, _vp, _u32, _int, _int, _int, _int, _int, _vp, C.c_double, _vp, _vp, _vp,
+                                                  _u64, C.POINTER(_u64), C.POINTER(_u64), C.POINTER(_u64)]),
     "lash_synth_genomes_device": (_int, [_vp, _u64, _u32, _u64, _vp]),
 }
 

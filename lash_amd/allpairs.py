@@ -105,6 +105,9 @@ class _Formatter:
         self.lib.lash_host_formatter_error.restype = C.c_char_p
         self.lib.lash_host_formatter_error.argtypes = [C.c_void_p]
         self.lib.lash_host_formatter_free.argtypes = [C.c_void_p]
+        self.lib.lash_host_formatter_within.restype = C.c_int64
+        self.lib.lash_host_formatter_within.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                        C.c_uint64, C.c_int]
         n = len(names)
         arr = (C.c_char_p * n)(*[s.encode() for s in names])
         card = np.ascontiguousarray(card, dtype=np.float64)
@@ -118,6 +121,13 @@ class _Formatter:
             raise LashError(_lib.ERANGE, self.lib.lash_host_formatter_error(self.h).decode())
         return w
 
+    def within(self, b0, b1, max_dist, survivors, fd):
+        row, col, dist = (np.ascontiguousarray(x) for x in survivors)
+        w = self.lib.lash_host_formatter_within(self.h, b0, b1, 1, float(max_dist), row.ctypes.data, col.ctypes.data, dist.ctypes.data, len(row), fd)
+        if w < 0:
+            raise OSError("lash_host_formatter_within: " + self.lib.lash_host_formatter_error(self.h).decode())
+        return w
+
     def close(self):
         if self.h:
             self.lib.lash_host_formatter_free(self.h)
@@ -125,10 +135,13 @@ class _Formatter:
 
 
 def all_vs_all_stream(algo, p, k, local_images, counts, names, out_prefix, *, ctx, model=1, fp32=False, estimator="fgra", group=None,
-                      matrix=False, hll_bias=None, max_block_pairs=1 << 25, threads=None, stats=None):
+                      matrix=False, hll_bias=None, max_block_pairs=1 << 25, threads=None, stats=None, max_dist=None):
     """The production form: this rank's bands of the lower triangle, streamed block by block from the GPU's pair tables through the
     C++ formatter into `<out_prefix>.band<i>` files (band i of 2 * world; concatenated in band order they are the body of `lash dist
-    --file-order`).  Memory is bounded by max_block_pairs whatever N is.  Returns the list of (band index, path, bytes)."""
+    --file-order`).  Memory is bounded by max_block_pairs whatever N is.  Returns the list of (band index, path, bytes).
+    max_dist: `lash dist --max-dist` — only the pairs with distance <= max_dist, filtered on the GPU (SketchSet.pair_block_within)."""
+    if max_dist is not None and matrix:
+        raise ValueError("--max-dist cannot be used with --dm (a square matrix cannot drop cells)")
     import torch.distributed as dist
     world, rank = dist.get_world_size(group), dist.get_rank(group)
     t0 = time.perf_counter()
@@ -168,6 +181,16 @@ def all_vs_all_stream(algo, p, k, local_images, counts, names, out_prefix, *, ct
     def gpu_block(i):
         _, b0, b1 = blocks[i]
         tg = time.perf_counter()
+        if max_dist is not None:
+            try:
+                st = s.pair_block_within(b0, b1, max_dist, k, n_cols=b1, triangle=True, model=model, fp32=fp32, estimator=estimator, hll_bias=hll_bias)
+            except LashError as e:
+                if e.code != _lib.ERANGE:
+                    raise
+                raise LashError(e.code, "union of %s and %s: cardinality estimate <= 5 * 2^p needs the HLL++ bias tables of streaming_algorithms"
+                                % (names[b0 + e.pair // b1], names[e.pair % b1])) from None
+            gpu_s[0] += time.perf_counter() - tg
+            return st
         st = s.pair_block(b0, b1, n_cols=b1, triangle=True, estimator=estimator, out=pin[i & 1])
         if a == _lib.HMH:
             ec = s.hmh_expected_collisions(b0, b1, n_cols=b1)
@@ -186,7 +209,10 @@ def all_vs_all_stream(algo, p, k, local_images, counts, names, out_prefix, *, ct
             st = fut.result()
             fut = ex.submit(gpu_block, i + 1) if i + 1 < len(blocks) else None
             th = time.perf_counter()
-            fds[band][2] += fmt.block(a, p, k, model, fp32, hll_bias, b0, b1, st, b1, matrix, threads, fds[band][1])
+            if max_dist is not None:
+                fds[band][2] += fmt.within(b0, b1, max_dist, st, fds[band][1])
+            else:
+                fds[band][2] += fmt.block(a, p, k, model, fp32, hll_bias, b0, b1, st, b1, matrix, threads, fds[band][1])
             t_host += time.perf_counter() - th
             pairs += sum(range(b0 + 1, b1 + 1))
     for band, (path, fd, written) in fds.items():
@@ -225,6 +251,13 @@ def _read_plain(path):
     return gzip.decompress(data) if data[:2] == b"\x1f\x8b" else data
 
 
+def _finite(v):
+    d = float(v)
+    if not np.isfinite(d):
+        raise ValueError(v)
+    return d
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description="sketch + all-vs-all dist over the ranks of a torch.distributed job")
     ap.add_argument("-f", "--file", required=True, help="list of FASTA/FASTQ files (plain or .gz), one per line")
@@ -238,11 +271,14 @@ def main(argv=None):
     ap.add_argument("-t", "--threads", type=int, default=0, help="host threads of this rank for the row arithmetic and text (default: its share of the cores)")
     ap.add_argument("--fp32", action="store_true")
     ap.add_argument("--dm", action="store_true")
+    ap.add_argument("--max-dist", type=_finite, default=None, help="print only the pairs whose distance is <= D (not with --dm)")
     ap.add_argument("--backend", default=None, help="nccl (one GPU per rank, default) or gloo (ranks may share a GPU; images gathered on the host)")
     ap.add_argument("--device", type=int, default=None, help="GPU of this rank (default LOCAL_RANK; with --backend gloo several ranks may name the same one)")
     ap.add_argument("--hll-bias", default=os.environ.get("LASH_HLL_BIAS"), help="HLL++ bias tables (tools/ref_probe/extract_hll_bias.py); without them "
                     "hll estimates <= 5 * 2^p are refused")
     args = ap.parse_args(argv)
+    if args.max_dist is not None and args.dm:
+        ap.error("--max-dist cannot be used with --dm (a square matrix cannot drop cells)")
     import torch
     import torch.distributed as dist
     rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
@@ -270,7 +306,7 @@ def main(argv=None):
         local_images = local_images.cuda(device)
     parts = all_vs_all_stream(algo, p, args.kmer, local_images, [b - a for a, b in blocks], names, args.output_file, ctx=ctx, model=args.model,
                               fp32=args.fp32, estimator=args.estimator, matrix=args.dm, hll_bias=HllBias(args.hll_bias) if args.hll_bias else None,
-                              threads=args.threads or None)
+                              threads=args.threads or None, max_dist=args.max_dist)
     del parts
     dist.barrier()
     if rank == 0:

@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "../../include/lash_gfx950.h"
+#include "dist_pair.h"
 #include "lash_common.h"
 
 namespace {
@@ -71,38 +72,13 @@ double hmh_approx_expected_collisions(double n, double m)
     return lash::hmh_ec_cell_walk(n, m);
 }
 
-// streaming_algorithms 0.3.3 len() thresholds (HLL++, Heule et al.), p = 4..18
-constexpr double HLL_THRESHOLD[15] = {10, 20, 40, 80, 220, 400, 900, 1800, 3100, 6500, 11500, 20000, 50000, 120000, 350000};
-
-double hll_alpha(int p)
-{
-    switch (p) {
-    case 4: return 0.673;
-    case 5: return 0.697;
-    case 6: return 0.709;
-    default: return 0.7213 / (1.0 + 1.079 / (double)(1u << p));
-    }
-}
-
 }  // namespace
 
 namespace lash {
 
-bool hmh_ec_closed_form(double n, double m, double *out)
-{
-    // (constants: 2^(2^q + r) = 2^74, 2^(p + 5) = 2^19, 2^(p - r) = 16; the crate writes them as powf calls)
-    if (n < m) std::swap(n, m);
-    if (n > 18889465931478580854784.0) { *out = 1.8446744073709552e19; return true; }                 // u64::MAX
-    if (n > 524288.0) {
-        const double t = (1.0 + n) / m;
-        const double d = (4.0 * n / m) / (t * t);
-        *out = 0.169919487159739093975315012348 * 16.0 * d + 0.5;
-        return true;
-    }
-    return false;
-}
+bool hmh_ec_closed_form(double n, double m, double *out) { return pairmath::hmh_ec_closed_form(n, m, out); }
 
-double hmh_ec_from_cell_sum(double x) { return (x * (double)HP + 0.5) / (double)HP; }
+double hmh_ec_from_cell_sum(double x) { return pairmath::hmh_ec_from_cell_sum(x); }
 
 // hyperminhash's cardinality() from the histogram of the registers' 6-bit leading-zero fields (lash_sketch_set_cardinalities:
 // the histogram comes from the GPU).  The crate adds 2^-lz register by register; while no register has lz > 39 every partial
@@ -159,36 +135,38 @@ bool hll_estimate_bias(const lash_hll_bias *t, int p, double e, double &out)
 
 bool hll_len(int p, uint64_t zero, double sum, const lash_hll_bias *tables, double &out)
 {
-    const double m = (double)(1u << p);
-    if (zero > 0) {
-        const double h = m * std::log(m / (double)zero);
-        if (h <= HLL_THRESHOLD[p - 4]) { out = h; return true; }
-    }
-    const double e = hll_alpha(p) * m * m / sum;
-    if (e <= 5.0 * m) {                                              // bias-corrected regime
-        double b;
-        if (!hll_estimate_bias(tables, p, e, b)) return false;       // tables absent: refuse
-        out = e - b;
-        return true;
-    }
-    out = e;
+    const int regime = lash::pairmath::hll_len_regime(p, zero, sum, &out);
+    if (regime != lash::pairmath::HLL_BIAS) return true;
+    double b;                                                        // bias-corrected regime
+    if (!hll_estimate_bias(tables, p, out, b)) return false;         // tables absent: refuse
+    out = out - b;
     return true;
-}
-
-template <class T>
-T compute_distance(T frac, int k, int model)
-{
-    const T kk = (T)k;
-    // frac == 0 (no similarity left after the collision correction: nearly every pair of an all-vs-all): both models give exactly 1 —
-    // -ln(0) / k = +inf -> min(.., 1) = 1;  1 - 0^(1/k) = 1 — without the libm call (glibc's pow(0, y) alone is 45 ns)
-    if (frac == (T)0) return (T)1;
-    if (model == 1) { const T d = -std::log(frac) / kk; return d < (T)1 ? d : (T)1; }      // (-frac.ln() / k).min(1)
-    return (T)1 - std::pow(frac, (T)1 / kk);
 }
 
 }  // namespace
 
 namespace lash {
+
+bool dist_pair_host(int algo, int p, int k, int model, int fp32, double ref_card, double qry_card, uint32_t c_or_zero, uint32_t n_count,
+                    double sum_or_union, const lash_hll_bias *tables, const double *hmh_ec, double *out)
+{
+    double sim = 0.0;
+    if (algo == LASH_HLL) {                                                                   // utils.rs:352-365
+        double u;
+        if (!hll_len(p, c_or_zero, sum_or_union, tables, u)) return false;
+        sim = pairmath::union_similarity(ref_card, qry_card, u);
+    } else if (algo == LASH_ULL) {                                                            // utils.rs:256-274
+        sim = pairmath::union_similarity(ref_card, qry_card, sum_or_union);
+    } else {
+        const double c = (double)c_or_zero, n = (double)n_count;
+        double ec = 0.0;
+        if (c != 0.0)                                                 // O(1) unless both sketches are small: then the caller's, if given
+            if (!pairmath::hmh_ec_closed_form(qry_card, ref_card, &ec)) ec = hmh_ec ? *hmh_ec : hmh_ec_cell_walk(qry_card, ref_card);
+        sim = pairmath::hmh_similarity(c, n, ec);                                             // Sketch::similarity
+    }
+    *out = pairmath::distance_from_similarity(sim, algo == LASH_ULL, k, model, fp32 != 0);
+    return true;
+}
 
 int hll_cardinality_from_hist(const uint32_t *hist256, int p, const lash_hll_bias *tables, double *out)
 {
@@ -279,28 +257,11 @@ int lash_dist_rows(int algo, int p, int k, int model, int fp32, uint32_t n_ref, 
     for (uint32_t i = 0; i < n_ref; ++i) {
         for (uint32_t j = 0; j < n_qry; ++j) {
             const uint64_t at = (uint64_t)i * n_qry + j;
-            double sim = 0.0;
-            if (algo == LASH_HLL) {                                                               // utils.rs:352-365
-                double u;
-                if (!hll_len(p, c_or_zero[at], sum_or_union[at], tables, u)) { if (bad_pair) *bad_pair = at; return LASH_ERANGE; }
-                sim = (ref_card[i] + qry_card[j] - u) / u;
-            } else if (algo == LASH_ULL) {                                                        // utils.rs:256-274
-                const double u = sum_or_union[at];
-                sim = (ref_card[i] + qry_card[j] - u) / u;
-            } else {
-                const double c = (double)c_or_zero[at], n = (double)n_counts[at];
-                if (c != 0.0) {                                                                   // Sketch::similarity
-                    double ec;                                            // O(1) unless both sketches are small: then the caller's, if given
-                    if (!lash::hmh_ec_closed_form(qry_card[j], ref_card[i], &ec)) ec = hmh_ec ? hmh_ec[at] : lash::hmh_ec_cell_walk(qry_card[j], ref_card[i]);
-                    sim = c < ec ? 0.0 : (c - ec) / n;
-                }
+            if (!lash::dist_pair_host(algo, p, k, model, fp32, ref_card[i], qry_card[j], c_or_zero ? c_or_zero[at] : 0, n_counts ? n_counts[at] : 0,
+                                      sum_or_union ? sum_or_union[at] : 0.0, tables, hmh_ec ? &hmh_ec[at] : nullptr, &out_dist[at])) {
+                if (bad_pair) *bad_pair = at;
+                return LASH_ERANGE;
             }
-            // hmh / hll: `.max(0.0)` (utils.rs:164, 362) — f64::max drops a NaN; ull: `if similarity < 0.0 {0.0} else {similarity}`
-            // (utils.rs:272-273) keeps it: two empty sketches give 0/0, model 1 then prints 1 (f64::min drops the NaN), model 0 NaN
-            if (algo == LASH_ULL) sim = sim < 0.0 ? 0.0 : sim;
-            else if (!(sim >= 0.0)) sim = 0.0;
-            const double frac = 2.0 * sim / (1.0 + sim);                                          // utils.rs:165-167
-            out_dist[at] = fp32 ? (double)compute_distance<float>((float)frac, k, model) : compute_distance<double>(frac, k, model);
         }
     }
     return LASH_OK;

@@ -1,0 +1,280 @@
+// dist_filter.hip — `lash dist --max-dist D`: the pairs of a block whose distance can be <= D, found and compacted on the GPU while
+// the block's pair statistics are still in HBM, so that only they come back to the host (include/lash_gfx950.h:
+// lash_sketch_set_pair_block_within).  An all-vs-all of 10^5 sketches is 5 * 10^9 pairs; printing all of them is ~250 GB of text
+// bound by the host, a cutoff keeps a few per row.
+//
+// Two passes over a block of rows [r0, r1) x columns [0, n_cols), row-major:
+//   mark   a workgroup owns a tile of WF_TILE consecutive columns of one row (tiles in row-major order); each wave evaluates
+//          64 pairs at a time, __ballot()s the candidates into one 64-bit mask word and the workgroup writes its count.
+//          Triangle blocks: tiles that start beyond the row's diagonal write 0 and return (as the pair kernels skip them).
+//   scan   one workgroup turns the per-tile counts into exclusive offsets (plain sums in a fixed order: deterministic).
+//   write  every candidate lands at its tile's offset + the mask bits below it (v_mbcnt), so the output is row-major whatever
+//          order the workgroups run in.  No atomics.
+// A candidate is written with its statistics (and, for small HyperMinHash pairs, the expected-collision cell sum), and the host
+// evaluates it exactly with the code lash_dist_rows runs: the kernel only has to be sure not to miss a pair.
+//
+// Why "d_dev <= D + margin" cannot miss one.  Up to the final log / pow, the device evaluates the same expressions as the host
+// (dist_pair.h: +, -, *, / with contraction off, the same f64 inputs — cardinalities, C / N / zero / sum / union estimates, and
+// for small HyperMinHash pairs the same collision_gemm_kernel cell sums), so the similarity is bit-identical — with one exception:
+// HLL++ linear counting, m ln(m / zero), calls log.  ocml's f64 log is within 1 ulp, glibc's within 1 ulp, so the two can differ
+// by 2 ulp (2^-51 relative); the kernel shrinks its union estimate by 2^-44 (128x that) before the inclusion-exclusion, which can
+// only raise the similarity, and treats an estimate within 2^-40 of the linear-counting threshold as a candidate outright (the host
+// might fall on the other side).  The HLL++ bias-table regime (raw estimate <= 5m) is host-only arithmetic: always a candidate.
+// What remains is the distance's own libm call on the same frac:
+//   f64:  -ln(f) / k with d <= 1 has |ln f| <= k <= 32: ulp(32) / k ~ 2^-47 per ulp; 1 - f^(1/k): ulp(1) = 2^-52.  A few ulp each
+//         side: < 2^-44.  margin 2^-40.
+//   fp32: the same in float (ocml's logf / powf: <= 2 ulp; glibc's correctly rounded or 1 ulp): ulp(1.0f) = 2^-23 per ulp of
+//         d ~ 1, so a few ulp each side: < 2^-19.  margin 2^-16 (1.5e-5).
+// NaN distances (ull, two empty sketches, model 0) are candidates too; the host drops them (NaN never passes).
+#include "lash_ctx.h"
+#include "dist_pair.h"
+
+namespace lash {
+
+constexpr uint32_t WF_TILE = 1024;                       // columns per tile: 256 lanes x 4 steps
+constexpr uint32_t WF_WORDS = WF_TILE / 64;              // mask words per tile
+
+// one candidate: block row, set column, the pair's statistics; ec_x: the small-pair cell sum of hmh, else NaN
+struct WithinPair {
+    uint32_t row, col, c_or_zero, n;
+    double sum_or_union, ec_x;
+};
+
+struct WithinArgs {
+    int algo, p, k, model, fp32;
+    double limit;                                        // D + margin
+    uint32_t nr, n_cols, tiles_x;
+    uint64_t n_tiles;
+    int64_t tri;                                         // r0 for a triangle block, else -1
+    const double *row_card, *col_card;                   // row_card: the block's first row
+    const uint32_t *c_or_zero, *n_counts;                // [nr][n_cols]
+    const double *sum_or_union;
+    const int32_t *row_small, *col_small;                // position in the set's small_idx, or -1 (row_small: the block's first row)
+    const double *X;                                     // EcBlock (nrs == 0: none)
+    uint32_t nrs, q_step, nqs, rbase;
+};
+
+__device__ __forceinline__ uint32_t row_end(const WithinArgs &a, uint32_t r)
+{
+    if (a.tri < 0) return a.n_cols;
+    const int64_t e = a.tri + (int64_t)r + 1;                                          // printed columns of row r
+    return e < (int64_t)a.n_cols ? (uint32_t)e : a.n_cols;
+}
+
+__device__ bool within_candidate(const WithinArgs &a, uint32_t r, uint32_t q)
+{
+    const uint64_t at = (uint64_t)r * a.n_cols + q;
+    const double rc = a.row_card[r], qc = a.col_card[q];
+    double sim;
+    if (a.algo == LASH_HLL) {
+        const uint32_t zero = a.c_or_zero[at];
+        double u;
+        const int regime = pairmath::hll_len_regime(a.p, zero, a.sum_or_union[at], &u);
+        if (regime == pairmath::HLL_BIAS) return true;                                 // host-only arithmetic (and maybe LASH_ERANGE)
+        if (zero > 0) {
+            const double m = (double)(1u << a.p), thr = pairmath::hll_threshold(a.p);
+            const double h = m * log(m / (double)zero);
+            if (fabs(h - thr) <= thr * 0x1p-40) return true;                            // the host's log may fall on the other side
+            if (regime == pairmath::HLL_LINEAR) u *= 1.0 - 0x1p-44;                    // no larger than the host's
+        }
+        sim = pairmath::union_similarity(rc, qc, u);
+    } else if (a.algo == LASH_ULL) {
+        sim = pairmath::union_similarity(rc, qc, a.sum_or_union[at]);
+    } else {
+        const double c = (double)a.c_or_zero[at], n = (double)a.n_counts[at];
+        double ec = 0.0;
+        if (c != 0.0 && !pairmath::hmh_ec_closed_form(qc, rc, &ec)) {
+            const int32_t rs = a.row_small[r], cs = a.col_small[q];
+            if (rs < 0 || cs < 0 || a.nrs == 0) return true;                            // (only NaN cardinalities get here)
+            const uint32_t ri = (uint32_t)rs - a.rbase, q0 = (uint32_t)cs / a.q_step * a.q_step, nq = min(a.q_step, a.nqs - q0);
+            ec = pairmath::hmh_ec_from_cell_sum(a.X[(uint64_t)a.nrs * q0 + (uint64_t)ri * nq + ((uint32_t)cs - q0)]);
+        }
+        sim = pairmath::hmh_similarity(c, n, ec);
+    }
+    const double d = pairmath::distance_from_similarity(sim, a.algo == LASH_ULL, a.k, a.model, a.fp32 != 0);
+    return !(d > a.limit);                                                              // (NaN: a candidate)
+}
+
+__global__ void __launch_bounds__(256) within_mark_kernel(WithinArgs a, uint64_t *__restrict__ mask, uint32_t *__restrict__ tile_count)
+{
+    __shared__ uint32_t wsum[4];
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    for (uint64_t tile = blockIdx.x; tile < a.n_tiles; tile += gridDim.x) {
+        const uint32_t r = (uint32_t)(tile / a.tiles_x), c0 = (uint32_t)(tile % a.tiles_x) * WF_TILE, c_end = row_end(a, r);
+        if (c0 >= c_end) {                                                              // wholly above the diagonal
+            if (threadIdx.x == 0) tile_count[tile] = 0;
+            continue;
+        }
+        uint32_t cnt = 0;
+        for (uint32_t step = 0; step < 4; ++step) {
+            const uint32_t word = step * 4u + wave, q = c0 + word * 64u + lane;
+            const bool keep = q < c_end && within_candidate(a, r, q);
+            const uint64_t bits = __ballot(keep);
+            if (lane == 0) mask[tile * WF_WORDS + word] = bits;
+            cnt += (uint32_t)__popcll(bits);
+        }
+        if (lane == 0) wsum[wave] = cnt;
+        __syncthreads();
+        if (threadIdx.x == 0) tile_count[tile] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+        __syncthreads();
+    }
+}
+
+// offsets[t] = sum of counts[0 .. t), offsets[n] = the total.  One workgroup: thread i sums a contiguous run of tiles, the 1024
+// run sums are scanned in LDS, then every thread writes its run's offsets.
+__global__ void __launch_bounds__(1024) within_scan_kernel(const uint32_t *__restrict__ counts, uint64_t n, uint64_t *__restrict__ offsets)
+{
+    __shared__ uint64_t part[1024];
+    const uint64_t per = (n + 1023u) / 1024u, b = threadIdx.x * per, e = min(n, b + per);
+    uint64_t s = 0;
+    for (uint64_t i = b; i < e; ++i) s += counts[i];
+    part[threadIdx.x] = s;
+    __syncthreads();
+    for (uint32_t d = 1; d < 1024u; d <<= 1) {                                          // inclusive Hillis-Steele
+        const uint64_t v = threadIdx.x >= d ? part[threadIdx.x - d] : 0;
+        __syncthreads();
+        part[threadIdx.x] += v;
+        __syncthreads();
+    }
+    uint64_t at = threadIdx.x ? part[threadIdx.x - 1] : 0;
+    for (uint64_t i = b; i < e; ++i) { offsets[i] = at; at += counts[i]; }
+    if (threadIdx.x == 1023u) offsets[n] = part[1023];
+}
+
+__global__ void __launch_bounds__(256) within_write_kernel(WithinArgs a, const uint64_t *__restrict__ mask, const uint32_t *__restrict__ tile_count,
+                                                           const uint64_t *__restrict__ offsets, WithinPair *__restrict__ out)
+{
+    __shared__ uint32_t before[WF_WORDS];
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    for (uint64_t tile = blockIdx.x; tile < a.n_tiles; tile += gridDim.x) {
+        if (tile_count[tile] == 0) continue;                                            // (uniform across the workgroup)
+        if (threadIdx.x == 0) {
+            uint32_t s = 0;
+            for (uint32_t w = 0; w < WF_WORDS; ++w) { before[w] = s; s += (uint32_t)__popcll(mask[tile * WF_WORDS + w]); }
+        }
+        __syncthreads();
+        const uint32_t r = (uint32_t)(tile / a.tiles_x), c0 = (uint32_t)(tile % a.tiles_x) * WF_TILE;
+        const uint64_t base = offsets[tile];
+        for (uint32_t step = 0; step < 4; ++step) {
+            const uint32_t word = step * 4u + wave;
+            const uint64_t bits = mask[tile * WF_WORDS + word];
+            if (!((bits >> lane) & 1u)) continue;
+            const uint32_t below = __builtin_amdgcn_mbcnt_hi((uint32_t)(bits >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bits, 0u));
+            const uint32_t q = c0 + word * 64u + lane;
+            const uint64_t at = (uint64_t)r * a.n_cols + q;
+            WithinPair w;
+            w.row = r;
+            w.col = q;
+            w.c_or_zero = a.c_or_zero ? a.c_or_zero[at] : 0u;
+            w.n = a.n_counts ? a.n_counts[at] : 0u;
+            w.sum_or_union = a.sum_or_union ? a.sum_or_union[at] : 0.0;
+            w.ec_x = __builtin_nan("");
+            if (a.algo == LASH_HMH && a.nrs) {
+                const int32_t rs = a.row_small[r], cs = a.col_small[q];
+                if (rs >= 0 && cs >= 0) {
+                    const uint32_t ri = (uint32_t)rs - a.rbase, q0 = (uint32_t)cs / a.q_step * a.q_step, nq = min(a.q_step, a.nqs - q0);
+                    w.ec_x = a.X[(uint64_t)a.nrs * q0 + (uint64_t)ri * nq + ((uint32_t)cs - q0)];
+                }
+            }
+            out[base + before[word] + below] = w;
+        }
+        __syncthreads();
+    }
+}
+
+}  // namespace lash
+
+namespace {
+
+uint32_t grid_for(uint64_t n_tiles) { return (uint32_t)std::min<uint64_t>(n_tiles, 1u << 20); }
+
+}  // namespace
+
+extern "C" {
+
+int lash_sketch_set_pair_block_within(lash_ctx *ctx, const lash_sketch_set *ref, uint32_t r0, uint32_t r1, const lash_sketch_set *qry,
+                                      uint32_t n_cols, int triangle, int k, int model, int fp32, int ull_estimator, const lash_hll_bias *tables,
+                                      double max_dist, uint32_t *out_row, uint32_t *out_col, double *out_dist, uint64_t cap, uint64_t *n_kept,
+                                      uint64_t *bad_pair, uint64_t *n_candidates)
+{
+    if (n_kept) *n_kept = 0;
+    if (n_candidates) *n_candidates = 0;
+    if (!ctx || !ref || !qry || !n_kept || r0 > r1 || r1 > ref->n || n_cols > qry->n || k < 1 || k > 32 || (model != 0 && model != 1))
+        return LASH_EINVAL;
+    if (std::isnan(max_dist) || (cap && (!out_row || !out_col || !out_dist))) return LASH_EINVAL;
+    if (ref->card.size() != ref->n || qry->card.size() != qry->n) return LASH_EINVAL;          // lash_sketch_set_cardinalities first
+    const uint32_t nr = r1 - r0;
+    if (nr == 0 || n_cols == 0) return LASH_OK;
+    (void)hipSetDevice(ctx->device);
+    int rc;
+    const int algo = ref->algo;
+    const uint64_t np = (uint64_t)nr * n_cols;
+    // the block's statistics: [sum_or_union f64 | c_or_zero u32 | n u32], as lash_sketch_set_pair_block
+    if ((rc = reserve(ctx, ctx->st_img, np * 16 + 64))) return rc;
+    double *d_u = static_cast<double *>(ctx->st_img.ptr);
+    uint32_t *d_c = reinterpret_cast<uint32_t *>(d_u + np), *d_n = d_c + np;
+    if ((rc = lash_sketch_set_pair_block_device(ctx, ref, r0, r1, qry, n_cols, triangle, ull_estimator, d_c, d_n, d_u))) return rc;
+    EcBlock eb;
+    if (algo == LASH_HMH && (rc = lash_set_ec_block(ctx, ref, r0, r1, qry, n_cols, eb))) return rc;
+
+    WithinArgs a{};
+    a.algo = algo; a.p = ref->p; a.k = k; a.model = model; a.fp32 = fp32 ? 1 : 0;
+    a.limit = max_dist + (fp32 ? 0x1p-16 : 0x1p-40);                                 // the margin: see the top of this file
+    a.nr = nr; a.n_cols = n_cols;
+    a.tiles_x = (n_cols + WF_TILE - 1) / WF_TILE;
+    a.n_tiles = (uint64_t)nr * a.tiles_x;
+    a.tri = triangle ? (int64_t)r0 : -1;
+    a.row_card = static_cast<const double *>(ref->d_card.ptr) + r0;
+    a.col_card = static_cast<const double *>(qry->d_card.ptr);
+    a.c_or_zero = algo == LASH_ULL ? nullptr : d_c;
+    a.n_counts = algo == LASH_HMH ? d_n : nullptr;
+    a.sum_or_union = algo == LASH_HMH ? nullptr : d_u;
+    a.row_small = static_cast<const int32_t *>(ref->d_small.ptr) + r0;
+    a.col_small = static_cast<const int32_t *>(qry->d_small.ptr);
+    a.X = eb.X; a.nrs = eb.nrs; a.q_step = eb.q_step; a.nqs = eb.nqs; a.rbase = eb.rbase;
+    if (eb.nqs == 0) a.nrs = 0;
+
+    // scratch: [offsets u64 (n_tiles + 1) | mask u64 (n_tiles * WF_WORDS) | counts u32 (n_tiles)]
+    const uint64_t nt = a.n_tiles;
+    if ((rc = reserve(ctx, ctx->wf_scratch, (nt + 1) * 8 + nt * WF_WORDS * 8 + nt * 4 + 64))) return rc;
+    uint64_t *d_off = static_cast<uint64_t *>(ctx->wf_scratch.ptr), *d_mask = d_off + nt + 1;
+    uint32_t *d_cnt = reinterpret_cast<uint32_t *>(d_mask + nt * WF_WORDS);
+    hipLaunchKernelGGL(within_mark_kernel, dim3(grid_for(nt)), dim3(256), 0, ctx->stream, a, d_mask, d_cnt);
+    HIPCHK(ctx, hipGetLastError());
+    hipLaunchKernelGGL(within_scan_kernel, dim3(1), dim3(1024), 0, ctx->stream, d_cnt, nt, d_off);
+    HIPCHK(ctx, hipGetLastError());
+    uint64_t n_cand = 0;
+    HIPCHK(ctx, hipMemcpyAsync(&n_cand, d_off + nt, 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    std::vector<WithinPair> cand(n_cand);
+    if (n_cand) {
+        if ((rc = reserve(ctx, ctx->wf_out, n_cand * sizeof(WithinPair)))) return rc;
+        WithinPair *d_out = static_cast<WithinPair *>(ctx->wf_out.ptr);
+        hipLaunchKernelGGL(within_write_kernel, dim3(grid_for(nt)), dim3(256), 0, ctx->stream, a, d_mask, d_cnt, d_off, d_out);
+        HIPCHK(ctx, hipGetLastError());
+        HIPCHK(ctx, hipMemcpyAsync(cand.data(), d_out, n_cand * sizeof(WithinPair), hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    if (n_candidates) *n_candidates = n_cand;
+
+    // exact: the host arithmetic of lash_dist_rows, pair by pair, in row-major order (so the first refused pair is the one it reports)
+    uint64_t kept = 0;
+    for (const WithinPair &w : cand) {
+        const uint32_t row = r0 + w.row;
+        double ec, d;
+        const double *ecp = nullptr;
+        if (algo == LASH_HMH && !std::isnan(w.ec_x)) { ec = hmh_ec_from_cell_sum(w.ec_x); ecp = &ec; }
+        if (!dist_pair_host(algo, ref->p, k, model, fp32, ref->card[row], qry->card[w.col], w.c_or_zero, w.n, w.sum_or_union, tables, ecp, &d)) {
+            if (bad_pair) *bad_pair = (uint64_t)w.row * n_cols + w.col;
+            *n_kept = kept;
+            return LASH_ERANGE;
+        }
+        if (!(d <= max_dist)) continue;
+        if (kept < cap) { out_row[kept] = row; out_col[kept] = w.col; out_dist[kept] = d; }
+        ++kept;
+    }
+    *n_kept = kept;
+    return LASH_OK;
+}
+
+}  // extern "C"

@@ -17,6 +17,8 @@
 // restates that order, so rows, columns and the (Reference, Query) orientation of each triangle pair come out as the
 // reference's `-t 1` run writes them.  --file-order keeps list-file order instead.
 // Several GPUs (--devices 0,1,..): blocks of reference rows are handed to one worker per device and written in order.
+// --max-dist D (not upstream): a block's pairs are filtered on the device (lash_sketch_set_pair_block_within) and only the rows with
+// d <= D are formatted — the same rows in the same order as without the option, minus the others.
 #include "dist.hpp"
 
 #include <dirent.h>
@@ -157,6 +159,14 @@ std::string run_dist(const DistOptions &opt)
     std::vector<uint32_t> row_id, col_id;
     name_ids(row_name, col_name, row_id, col_id);
     const std::vector<std::string> col_tab = opt.matrix ? std::vector<std::string>() : tabbed_names(col_name);
+    // --max-dist: the column carrying each row's name (a name is one entry per side, so at most one), found once — those pairs print 0
+    std::vector<uint32_t> same_col;
+    if (opt.has_max_dist) {
+        std::vector<uint32_t> col_of(row_name.size() + col_name.size(), NO_COLUMN);
+        for (uint32_t j = 0; j < nq; ++j) col_of[col_id[j]] = j;
+        same_col.resize(nr);
+        for (uint32_t i = 0; i < nr; ++i) same_col[i] = col_of[row_id[i]];
+    }
 
     const char *bias_msg = ": cardinality estimate <= 5 * 2^p needs the HLL++ bias tables of streaming_algorithms, which are "
                            "not built in (pass --hll-bias <file from tools/ref_probe/extract_hll_bias.py>, or sketch with a smaller -p)";
@@ -262,6 +272,8 @@ std::string run_dist(const DistOptions &opt)
         double *U = nullptr, *EC = nullptr;
         size_t cap = 0, ec_cap = 0;
         RowText row_text;                                        // the block's text; its memory is reused from block to block
+        std::vector<uint32_t> w_row, w_col;                      // --max-dist: the block's survivors
+        std::vector<double> w_dist;
         auto grow = [&](size_t np) {
             if (np <= cap) return true;
             lash_host_free_pinned(C); lash_host_free_pinned(N); lash_host_free_pinned(U);
@@ -281,7 +293,22 @@ std::string run_dist(const DistOptions &opt)
             { std::lock_guard<std::mutex> lk(wmu); skip = !fail.empty(); }
             bool have_ec = false;
             row_text.off.clear(); row_text.len.clear();
-            if (my_fail.empty() && !skip) {
+            if (my_fail.empty() && !skip && opt.has_max_dist) {
+                // pair statistics, expected collisions and the cutoff on the device; only the survivors come back
+                uint64_t kept = 0, bad = 0;
+                if (w_row.empty()) { w_row.resize(1u << 16); w_col.resize(1u << 16); w_dist.resize(1u << 16); }
+                for (;;) {
+                    rc = lash_sketch_set_pair_block_within(ctx, ds->ref, i0, i1, ds->qry, n_cols, same_files ? 1 : 0, k, opt.model, opt.fp32 ? 1 : 0,
+                                                           ull_est, bias, opt.max_dist, w_row.data(), w_col.data(), w_dist.data(), w_row.size(),
+                                                           &kept, &bad, nullptr);
+                    if (rc != LASH_OK || kept <= w_row.size()) break;
+                    w_row.resize(kept + kept / 4); w_col.resize(w_row.size()); w_dist.resize(w_row.size());
+                }
+                if (rc == LASH_ERANGE) my_fail = "union of " + row_name[i0 + bad / n_cols] + " and " + col_name[bad % n_cols] + bias_msg;
+                else if (rc != LASH_OK) my_fail = std::string(lash_strerror(rc)) + " " + lash_ctx_last_error(ctx);
+                else format_block_within(i0, i1, same_files, nq, opt.max_dist, w_row.data(), w_col.data(), w_dist.data(), kept, same_col.data(),
+                                         row_name, col_tab, row_text);
+            } else if (my_fail.empty() && !skip) {
                 const size_t np = (size_t)(i1 - i0) * n_cols;
                 if (!grow(np)) my_fail = "out of page-locked host memory";
                 else {
@@ -297,7 +324,7 @@ std::string run_dist(const DistOptions &opt)
                     if (rc != LASH_OK) my_fail = std::string(lash_strerror(rc)) + " " + lash_ctx_last_error(ctx);
                 }
             }
-            if (my_fail.empty() && !skip) {
+            if (my_fail.empty() && !skip && !opt.has_max_dist) {
                 BlockTables bt;
                 bt.c_or_zero = C; bt.n_counts = N; bt.sum_or_union = U; bt.hmh_ec = have_ec ? EC : nullptr; bt.ld = n_cols;
                 my_fail = dist_block_rows(algo_id, prec, k, opt.model, opt.fp32, bias, i0, i1, same_files, nq, rcard.data(), qcard.data(), bt, row_name,

@@ -32,6 +32,19 @@ void name_ids(const std::vector<std::string> &row_name, const std::vector<std::s
     for (size_t j = 0; j < col_name.size(); ++j) col_id[j] = id_of(col_name[j]);
 }
 
+namespace {
+
+// "{:.6}" (main.rs:456,461): std::to_chars(fixed, 6) is correctly rounded like Rust's formatter, several times faster than printf
+char *put_dist(char *p, double d)
+{
+    if (d == 1.0) { memcpy(p, "1.000000", 8); return p + 8; }                  // unrelated genomes: most of an all-vs-all
+    if (d == 0.0) { memcpy(p, "0.000000", 8); return p + 8; }
+    if (d != d) { memcpy(p, "NaN", 3); return p + 3; }                          // Rust's Display (ull, model 0, two empty sketches)
+    return std::to_chars(p, p + 26, d, std::chars_format::fixed, 6).ptr;
+}
+
+}  // namespace
+
 size_t row_text_bound(const std::string &rname, const std::vector<std::string> &qtab, uint32_t n_print, bool matrix)
 {
     if (matrix) return 1 + rname.size() + (size_t)n_print * 28;
@@ -44,7 +57,6 @@ size_t format_row(char *dst, const std::string &rname, const std::vector<std::st
                   const uint32_t *col_id, bool matrix)
 {
     if (n_print == 0) return 0;                                                  // (a row with no column prints nothing, main.rs:443)
-    // "{:.6}" (main.rs:456,461): std::to_chars(fixed, 6) is correctly rounded like Rust's formatter, several times faster than printf
     char *p = dst;
     if (matrix) { *p++ = '\n'; memcpy(p, rname.data(), rname.size()); p += rname.size(); }
     for (uint32_t c = 0; c < n_print; ++c) {
@@ -54,13 +66,43 @@ size_t format_row(char *dst, const std::string &rname, const std::vector<std::st
             memcpy(p, rname.data(), rname.size()); p += rname.size();
             memcpy(p, qtab[c].data(), qtab[c].size()); p += qtab[c].size();
         }
-        if (d == 1.0) { memcpy(p, "1.000000", 8); p += 8; }                      // unrelated genomes: most of an all-vs-all
-        else if (d == 0.0) { memcpy(p, "0.000000", 8); p += 8; }
-        else if (d != d) { memcpy(p, "NaN", 3); p += 3; }                         // Rust's Display (ull, model 0, two empty sketches)
-        else p = std::to_chars(p, p + 26, d, std::chars_format::fixed, 6).ptr;
+        p = put_dist(p, d);
         if (!matrix) *p++ = '\n';
     }
     return (size_t)(p - dst);
+}
+
+void format_block_within(uint32_t i0, uint32_t i1, bool triangle, uint32_t n_cols_total, double max_dist, const uint32_t *row, const uint32_t *col,
+                         const double *dist, uint64_t n, const uint32_t *same_col, const std::vector<std::string> &row_name,
+                         const std::vector<std::string> &col_tab, RowText &text)
+{
+    size_t bound = 0;
+    for (uint64_t s = 0; s < n; ++s) bound += row_name[row[s]].size() + col_tab[col[s]].size() + 28;
+    for (uint32_t i = i0; i < i1; ++i)
+        if (same_col[i] != NO_COLUMN) bound += row_name[i].size() + col_tab[same_col[i]].size() + 28;
+    if (text.buf.size() < bound) text.buf.resize(bound + bound / 8);
+    char *const dst = text.buf.data();
+    char *p = dst;
+    auto emit = [&](uint32_t i, uint32_t c, double d) {
+        memcpy(p, row_name[i].data(), row_name[i].size()); p += row_name[i].size();
+        memcpy(p, col_tab[c].data(), col_tab[c].size()); p += col_tab[c].size();
+        p = put_dist(p, d);
+        *p++ = '\n';
+    };
+    uint64_t s = 0;
+    for (uint32_t i = i0; i < i1; ++i) {
+        const uint32_t n_print = triangle ? std::min(i + 1, n_cols_total) : n_cols_total;              // utils.rs:158-160
+        const uint32_t same = same_col[i] < n_print ? same_col[i] : NO_COLUMN;
+        uint32_t pending = same != NO_COLUMN && 0.0 <= max_dist ? same : NO_COLUMN;                 // prints 0 (main.rs:452-453)
+        for (; s < n && row[s] == i; ++s) {
+            if (col[s] == same) continue;                                                           // (decided above)
+            if (pending < col[s]) { emit(i, pending, 0.0); pending = NO_COLUMN; }
+            emit(i, col[s], dist[s]);
+        }
+        if (pending != NO_COLUMN) emit(i, pending, 0.0);
+    }
+    text.off.assign(1, 0);
+    text.len.assign(1, (size_t)(p - dst));
 }
 
 void append_row(std::string &out, const std::string &rname, const std::vector<std::string> &qtab, uint32_t n_print, const double *dist,

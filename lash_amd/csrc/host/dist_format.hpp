@@ -47,6 +47,14 @@ struct RowText {
     const char *data(size_t r) const { return buf.data() + off[r]; }
     size_t size(size_t r) const { return len[r]; }
 };
+// --max-dist: the list-form text of rows [i0, i1) (one slot of `text`) from lash_sketch_set_pair_block_within's survivors — n pairs
+// (row[s], col[s], dist[s]) in (row, col) order, set rows — merged with each row's same-name column same_col[i] (NO_COLUMN: none), which
+// prints 0 and so passes exactly when 0 <= max_dist whatever its own distance.  The rows print what dist_block_rows would, minus the
+// pairs that fail d <= max_dist.
+constexpr uint32_t NO_COLUMN = 0xFFFFFFFFu;
+void format_block_within(uint32_t i0, uint32_t i1, bool triangle, uint32_t n_cols_total, double max_dist, const uint32_t *row, const uint32_t *col,
+                         const double *dist, uint64_t n, const uint32_t *same_col, const std::vector<std::string> &row_name,
+                         const std::vector<std::string> &col_tab, RowText &text);
 std::string dist_block_rows(int algo, int p, int k, int model, bool fp32, const void *hll_bias, uint32_t i0, uint32_t i1, bool triangle,
                             uint32_t n_cols_total, const double *row_card, const double *col_card, const BlockTables &t,
                             const std::vector<std::string> &row_name, const std::vector<std::string> &col_name,

@@ -213,7 +213,7 @@ char *lash_host_zstd_read(const char *path, uint8_t **out, uint64_t *n)
 struct lash_host_formatter {
     std::vector<std::string> row_names, col_names, col_tab;
     std::vector<double> row_card, col_card;
-    std::vector<uint32_t> row_id, col_id;
+    std::vector<uint32_t> row_id, col_id, same_col;   // same_col[i]: the column carrying row i's name, or NO_COLUMN
     std::string err;
     lashhost::RowText text;              // the last block's text (memory kept from block to block)
 };
@@ -229,6 +229,9 @@ lash_host_formatter *lash_host_formatter_create(const char *const *row_names, co
     f->col_card.assign(col_card, col_card + n_cols);
     name_ids(f->row_names, f->col_names, f->row_id, f->col_id);
     f->col_tab = tabbed_names(f->col_names);
+    std::vector<uint32_t> col_of(n_rows + n_cols, NO_COLUMN);
+    for (uint32_t j = 0; j < n_cols; ++j) col_of[f->col_id[j]] = j;
+    for (uint32_t i = 0; i < n_rows; ++i) f->same_col.push_back(col_of[f->row_id[i]]);
     return f;
 }
 
@@ -237,17 +240,9 @@ const char *lash_host_formatter_error(const lash_host_formatter *f) { return f ?
 
 // rows [i0, i1) from their pair tables (row-major, pitch ld; see lash_dist_rows for which a sketch type uses) to `fd`.
 // Returns the bytes written, or -1 (lash_host_formatter_error says why).
-int64_t lash_host_formatter_block(lash_host_formatter *f, int algo, int p, int k, int model, int fp32, const void *hll_bias, uint32_t i0, uint32_t i1,
-                                  int triangle, const uint32_t *c_or_zero, const uint32_t *n_counts, const double *sum_or_union, const double *hmh_ec,
-                                  uint64_t ld, int matrix, int threads, int fd)
+static int64_t write_text(lash_host_formatter *f, int fd)
 {
-    if (!f || i0 > i1 || i1 > f->row_names.size()) return -1;
-    BlockTables t;
-    t.c_or_zero = c_or_zero; t.n_counts = n_counts; t.sum_or_union = sum_or_union; t.hmh_ec = hmh_ec; t.ld = ld;
-    RowText &text = f->text;                                                     // (one caller at a time: lash_amd/allpairs.py formats blocks in order)
-    f->err = dist_block_rows(algo, p, k, model, fp32 != 0, hll_bias, i0, i1, triangle != 0, (uint32_t)f->col_names.size(), f->row_card.data(),
-                             f->col_card.data(), t, f->row_names, f->col_names, f->col_tab, f->row_id.data(), f->col_id.data(), matrix != 0, threads, text);
-    if (!f->err.empty()) return -1;
+    const RowText &text = f->text;
     int64_t total = 0;
     for (size_t r = 0; r < text.rows(); ++r) {
         size_t at = 0;
@@ -259,6 +254,31 @@ int64_t lash_host_formatter_block(lash_host_formatter *f, int algo, int p, int k
         total += (int64_t)text.size(r);
     }
     return total;
+}
+
+// --max-dist: rows [i0, i1) from lash_sketch_set_pair_block_within's n survivors (set rows, columns, distances in (row, col) order)
+// to `fd` (format_block_within: the same-name columns print 0).  Returns the bytes written, or -1.
+int64_t lash_host_formatter_within(lash_host_formatter *f, uint32_t i0, uint32_t i1, int triangle, double max_dist, const uint32_t *row,
+                                   const uint32_t *col, const double *dist, uint64_t n, int fd)
+{
+    if (!f || i0 > i1 || i1 > f->row_names.size()) return -1;
+    format_block_within(i0, i1, triangle != 0, (uint32_t)f->col_names.size(), max_dist, row, col, dist, n, f->same_col.data(), f->row_names,
+                        f->col_tab, f->text);
+    return write_text(f, fd);
+}
+
+int64_t lash_host_formatter_block(lash_host_formatter *f, int algo, int p, int k, int model, int fp32, const void *hll_bias, uint32_t i0, uint32_t i1,
+                                  int triangle, const uint32_t *c_or_zero, const uint32_t *n_counts, const double *sum_or_union, const double *hmh_ec,
+                                  uint64_t ld, int matrix, int threads, int fd)
+{
+    if (!f || i0 > i1 || i1 > f->row_names.size()) return -1;
+    BlockTables t;
+    t.c_or_zero = c_or_zero; t.n_counts = n_counts; t.sum_or_union = sum_or_union; t.hmh_ec = hmh_ec; t.ld = ld;
+    RowText &text = f->text;                                                     // (one caller at a time: lash_amd/allpairs.py formats blocks in order)
+    f->err = dist_block_rows(algo, p, k, model, fp32 != 0, hll_bias, i0, i1, triangle != 0, (uint32_t)f->col_names.size(), f->row_card.data(),
+                             f->col_card.data(), t, f->row_names, f->col_names, f->col_tab, f->row_id.data(), f->col_id.data(), matrix != 0, threads, text);
+    if (!f->err.empty()) return -1;
+    return write_text(f, fd);
 }
 
 }  // extern "C"

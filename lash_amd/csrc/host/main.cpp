@@ -4,10 +4,11 @@
 //   lash dist   -q PREFIX -r PREFIX [-o dist] [-t N] [-e fgra|ml] [-m 1|0] [--fp32] [--dm]   (main.rs:107-176, 280-617)
 // Extras that do not exist upstream: --gpus N / --device D / --devices LIST (which GPUs to use, one worker each), --batch-mb M, --stream-mb M (files
 // larger than M MiB are streamed in chunks with on-device accumulation), --hmh-x-low; dist: --device D, --block-rows N,
-// --file-order (rows / columns in list-file order instead of the reference's seeded hash-map order)
-// (reference rows per GPU call); both: --layout SPEC (or $LASH_LAYOUT): the crate-internal rules as data, see `lash_layout`
+// --file-order (rows / columns in list-file order instead of the reference's seeded hash-map order), --max-dist D (print only
+// the pairs with distance <= D) (reference rows per GPU call); both: --layout SPEC (or $LASH_LAYOUT): the crate-internal rules as data, see `lash_layout`
 // in include/lash_gfx950.h.
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -52,6 +53,7 @@ void usage()
             "  -q, --query <prefix>  -r, --reference <prefix>  -o, --output_file <name> [default: dist]\n"
             "  -t, --threads <n>  -e, --estimator <fgra|ml>  -m, --model <1|0>  --fp32  --dm\n"
             "      --file-order   rows and columns in list-file order (default: the reference's hash-map key order)\n"
+            "      --max-dist <D> print only the pairs whose distance is <= D (same rows, same order; not with --dm)\n"
             "      --hll-bias <file>  HLL++ bias tables (tools/ref_probe/extract_hll_bias.py) [default: $LASH_HLL_BIAS];\n"
             "                     without them hll estimates <= 5 * 2^p are refused\n");
 }
@@ -198,6 +200,15 @@ int cmd_dist(int argc, char **argv)
             if (c == std::string::npos) break;
             at = c + 1;
         }
+    }
+    if (a.kv.count("max-dist")) {
+        const std::string &v = a.kv["max-dist"];
+        char *e = nullptr;
+        const double d = v.empty() ? NAN : strtod(v.c_str(), &e);
+        if (!e || *e != 0 || !std::isfinite(d)) { fprintf(stderr, "error: invalid value '%s' for --max-dist: a finite number is required\n", v.c_str()); return 2; }
+        if (opt.matrix) { fprintf(stderr, "error: --max-dist cannot be used with --dm (a square matrix cannot drop cells)\n"); return 2; }
+        opt.has_max_dist = true;
+        opt.max_dist = d;
     }
     err = layout_from_option(a.kv.count("layout") ? a.kv["layout"] : "", opt.layout);
     if (!err.empty()) { fprintf(stderr, "error: %s\n", err.c_str()); return 2; }

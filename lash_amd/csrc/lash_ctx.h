@@ -5,6 +5,7 @@
 
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -116,9 +117,22 @@ struct lash_sketch_set {
     std::vector<uint32_t> small_idx;
     DevBuf ec_vec;
     bool have_ec_vec = false;
+    // the same on the device, for lash_sketch_set_pair_block_within: d_card [n] f64; d_small [n] i32 = position in small_idx or -1
+    DevBuf d_card, d_small;
 };
 
 int lash_set_build_planes(lash_ctx *ctx, lash_sketch_set *s, bool want_T);   // sketch_set.hip
+
+// HyperMinHash: the 65 536-cell sums of the block's small pairs (rows [r0, r1) of ref x columns [0, n_cols) of qry, both sketches
+// <= 2^19 distinct k-mers) as f64 matrix products into ctx->ec_x, asynchronous on the context's stream (sketch_set.hip).  The small
+// columns go in chunks of q_step; chunk q0 is an [nrs][min(q_step, nqs - q0)] matrix at X + nrs * q0.  Small row i of the block is
+// ref->small_idx[rbase + i], small column j is qry->small_idx[j].  nrs == 0 or nqs == 0: no small pair, X not written.
+struct EcBlock {
+    uint32_t nrs = 0, nqs = 0, q_step = 0, rbase = 0;
+    const double *X = nullptr;
+};
+int lash_set_ec_block(lash_ctx *ctx, const lash_sketch_set *ref, uint32_t r0, uint32_t r1, const lash_sketch_set *qry, uint32_t n_cols,
+                      EcBlock &eb);
 
 struct lash_ctx {
     int device = 0;
@@ -156,6 +170,7 @@ struct lash_ctx {
     DevBuf hll_bm_ref, hll_bm_qry, hll_lohi;   // lash_hll_pair_union_stats*: threshold bitmaps [n][band][m/32], range of register values
     DevBuf ec_ref, ec_qry, ec_x, ec_card;   // lash_hmh_pair_expected_collisions: cell vectors [n][65536] f64, products, cardinalities
     std::vector<double> ec_qry_cards;    // the small query cardinalities whose vectors ec_qry holds (reused across row blocks)
+    DevBuf wf_scratch, wf_out;           // lash_sketch_set_pair_block_within: [offsets | masks | tile counts], the compacted candidates
     DevBuf hll_flags;                    // [hll_flags_n] per genome of the last HyperLogLog sketch call: a register > 53 - p
     uint32_t hll_flags_n = 0;            // (lash_ctx_hll_inexact_sums)
     bool hll_flags_on_host = false;      // the list below stands for the flags (hll_replay_sums has dealt with the others)

@@ -115,6 +115,48 @@ int lash_set_build_planes(lash_ctx *ctx, lash_sketch_set *s, bool want_T)
     return LASH_OK;
 }
 
+int lash_set_ec_block(lash_ctx *ctx, const lash_sketch_set *ref, uint32_t r0, uint32_t r1, const lash_sketch_set *qry, uint32_t n_cols,
+                      EcBlock &eb)
+{
+    eb = EcBlock();
+    // the block's small rows, the small columns below n_cols (small_idx ascends)
+    const auto rb = std::lower_bound(ref->small_idx.begin(), ref->small_idx.end(), r0), re = std::lower_bound(rb, ref->small_idx.end(), r1);
+    const uint32_t nrs = (uint32_t)(re - rb);
+    const uint32_t nqs = (uint32_t)(std::lower_bound(qry->small_idx.begin(), qry->small_idx.end(), n_cols) - qry->small_idx.begin());
+    if (nrs == 0 || nqs == 0) return LASH_OK;
+    (void)hipSetDevice(ctx->device);
+    constexpr size_t VEC = 65536 * sizeof(double);
+    int rc;
+    // the query vectors: the set's (prepare), or made here 4 096 at a time when they did not fit
+    const uint32_t q_step = qry->have_ec_vec ? nqs : 4096u;
+    std::vector<double> cards((size_t)nrs + (qry->have_ec_vec ? 0 : nqs));
+    for (uint32_t i = 0; i < nrs; ++i) cards[i] = ref->card[rb[i]];
+    if (!qry->have_ec_vec)
+        for (uint32_t j = 0; j < nqs; ++j) cards[nrs + j] = qry->card[qry->small_idx[j]];
+    if ((rc = reserve(ctx, ctx->ec_ref, (size_t)nrs * VEC))) return rc;
+    if ((rc = reserve(ctx, ctx->ec_card, cards.size() * 8))) return rc;
+    if ((rc = reserve(ctx, ctx->ec_x, (size_t)nrs * nqs * 8))) return rc;
+    if (!qry->have_ec_vec && (rc = reserve(ctx, ctx->ec_qry, (size_t)std::min(q_step, nqs) * VEC))) return rc;
+    double *d_card = static_cast<double *>(ctx->ec_card.ptr), *X = static_cast<double *>(ctx->ec_x.ptr);
+    if ((rc = upload(ctx, d_card, cards.data(), cards.size() * 8))) return rc;          // (pinned staging: `cards` may go at once)
+    HIPCHK(ctx, launch_collision_vectors(d_card, nrs, static_cast<double *>(ctx->ec_ref.ptr), ctx->stream));
+    for (uint32_t q0 = 0; q0 < nqs; q0 += q_step) {
+        const uint32_t nq = std::min(q_step, nqs - q0);
+        const double *d_B = static_cast<const double *>(qry->ec_vec.ptr);
+        if (!qry->have_ec_vec) {
+            HIPCHK(ctx, launch_collision_vectors(d_card + nrs + q0, nq, static_cast<double *>(ctx->ec_qry.ptr), ctx->stream));
+            d_B = static_cast<const double *>(ctx->ec_qry.ptr);
+        }
+        HIPCHK(ctx, launch_collision_gemm(static_cast<const double *>(ctx->ec_ref.ptr), nrs, d_B, nq, X + (size_t)nrs * q0, ctx->stream));
+    }
+    eb.nrs = nrs;
+    eb.nqs = nqs;
+    eb.q_step = q_step;
+    eb.rbase = (uint32_t)(rb - ref->small_idx.begin());
+    eb.X = X;
+    return LASH_OK;
+}
+
 namespace {
 
 int hll_range(lash_ctx *ctx, lash_sketch_set *s)
@@ -215,7 +257,7 @@ void lash_sketch_set_free(lash_ctx *ctx, lash_sketch_set *s)
     if (!s) return;
     (void)hipSetDevice(s->device);
     if (ctx && ctx->stream) (void)hipStreamSynchronize(ctx->stream);
-    for (DevBuf *b : {&s->images, &s->S, &s->T, &s->nzcount, &s->lohi, &s->bm, &s->ec_vec}) release(*b);
+    for (DevBuf *b : {&s->images, &s->S, &s->T, &s->nzcount, &s->lohi, &s->bm, &s->ec_vec, &s->d_card, &s->d_small}) release(*b);
     delete s;
 }
 
@@ -257,11 +299,18 @@ int lash_sketch_set_cardinalities(lash_ctx *ctx, lash_sketch_set *s, int ull_est
     s->card.assign(out_card, out_card + s->n);
     s->small_idx.clear();
     s->have_ec_vec = false;
+    std::vector<int32_t> small_pos(s->n, -1);
     if (s->algo == LASH_HMH) {
         double dummy;
         for (uint32_t i = 0; i < s->n; ++i)
-            if (!hmh_ec_closed_form(out_card[i], out_card[i], &dummy)) s->small_idx.push_back(i);
+            if (!hmh_ec_closed_form(out_card[i], out_card[i], &dummy)) { small_pos[i] = (int32_t)s->small_idx.size(); s->small_idx.push_back(i); }
     }
+    // (the device copies the --max-dist filter reads: lash_sketch_set_pair_block_within)
+    if ((rc = reserve(ctx, s->d_card, (size_t)s->n * 8))) return rc;
+    if ((rc = reserve(ctx, s->d_small, (size_t)s->n * 4))) return rc;
+    HIPCHK(ctx, hipMemcpyAsync(s->d_card.ptr, out_card, (size_t)s->n * 8, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(s->d_small.ptr, small_pos.data(), (size_t)s->n * 4, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return LASH_OK;
 }
 
@@ -383,47 +432,23 @@ int lash_sketch_set_hmh_expected_collisions(lash_ctx *ctx, const lash_sketch_set
     if (n_small_pairs) *n_small_pairs = 0;
     if (!ctx || !ref || !qry || ref->algo != LASH_HMH || qry->algo != LASH_HMH || r0 > r1 || r1 > ref->n || n_cols > qry->n) return LASH_EINVAL;
     if (ref->card.size() != ref->n || qry->card.size() != qry->n) return LASH_EINVAL;          // lash_sketch_set_cardinalities first
-    // the block's small rows, the small columns below n_cols (small_idx ascends)
-    const auto rb = std::lower_bound(ref->small_idx.begin(), ref->small_idx.end(), r0), re = std::lower_bound(rb, ref->small_idx.end(), r1);
-    const uint32_t nrs = (uint32_t)(re - rb);
-    const uint32_t nqs = (uint32_t)(std::lower_bound(qry->small_idx.begin(), qry->small_idx.end(), n_cols) - qry->small_idx.begin());
-    if (nrs == 0 || nqs == 0) return LASH_OK;
+    EcBlock eb;
+    int rc = lash_set_ec_block(ctx, ref, r0, r1, qry, n_cols, eb);
+    if (rc) return rc;
+    if (eb.nrs == 0 || eb.nqs == 0) return LASH_OK;
     if (!out_ec) return LASH_EINVAL;
-    (void)hipSetDevice(ctx->device);
-    constexpr size_t VEC = 65536 * sizeof(double);
-    int rc;
-    std::vector<double> cards(nrs), x;
-    for (uint32_t i = 0; i < nrs; ++i) cards[i] = ref->card[rb[i]];
-    if ((rc = reserve(ctx, ctx->ec_ref, (size_t)nrs * VEC))) return rc;
-    if ((rc = reserve(ctx, ctx->ec_card, (size_t)(nrs + 4096) * 8))) return rc;
-    double *d_card = static_cast<double *>(ctx->ec_card.ptr);
-    HIPCHK(ctx, hipMemcpyAsync(d_card, cards.data(), (size_t)nrs * 8, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, launch_collision_vectors(d_card, nrs, static_cast<double *>(ctx->ec_ref.ptr), ctx->stream));
-    // the query vectors: the set's (prepare), or made here 4 096 at a time when they did not fit
-    const uint32_t q_step = qry->have_ec_vec ? nqs : 4096u;
-    std::vector<double> qc;
-    for (uint32_t q0 = 0; q0 < nqs; q0 += q_step) {
-        const uint32_t nq = std::min(q_step, nqs - q0);
-        const double *d_B = static_cast<const double *>(qry->ec_vec.ptr);
-        if (!qry->have_ec_vec) {
-            qc.resize(nq);
-            for (uint32_t j = 0; j < nq; ++j) qc[j] = qry->card[qry->small_idx[q0 + j]];
-            if ((rc = reserve(ctx, ctx->ec_qry, (size_t)nq * VEC))) return rc;
-            HIPCHK(ctx, hipMemcpyAsync(d_card + nrs, qc.data(), (size_t)nq * 8, hipMemcpyHostToDevice, ctx->stream));
-            HIPCHK(ctx, launch_collision_vectors(d_card + nrs, nq, static_cast<double *>(ctx->ec_qry.ptr), ctx->stream));
-            d_B = static_cast<const double *>(ctx->ec_qry.ptr);
-        }
-        if ((rc = reserve(ctx, ctx->ec_x, (size_t)nrs * nq * 8))) return rc;
-        HIPCHK(ctx, launch_collision_gemm(static_cast<const double *>(ctx->ec_ref.ptr), nrs, d_B, nq, static_cast<double *>(ctx->ec_x.ptr), ctx->stream));
-        x.resize((size_t)nrs * nq);
-        HIPCHK(ctx, hipMemcpyAsync(x.data(), ctx->ec_x.ptr, x.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-        for (uint32_t i = 0; i < nrs; ++i) {
-            double *row = out_ec + (size_t)(rb[i] - r0) * n_cols;
-            for (uint32_t j = 0; j < nq; ++j) row[qry->small_idx[q0 + j]] = hmh_ec_from_cell_sum(x[(size_t)i * nq + j]);
+    std::vector<double> x((size_t)eb.nrs * eb.nqs);
+    HIPCHK(ctx, hipMemcpyAsync(x.data(), eb.X, x.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    for (uint32_t q0 = 0; q0 < eb.nqs; q0 += eb.q_step) {
+        const uint32_t nq = std::min(eb.q_step, eb.nqs - q0);
+        const double *chunk = x.data() + (size_t)eb.nrs * q0;
+        for (uint32_t i = 0; i < eb.nrs; ++i) {
+            double *row = out_ec + (size_t)(ref->small_idx[eb.rbase + i] - r0) * n_cols;
+            for (uint32_t j = 0; j < nq; ++j) row[qry->small_idx[q0 + j]] = hmh_ec_from_cell_sum(chunk[(size_t)i * nq + j]);
         }
     }
-    if (n_small_pairs) *n_small_pairs = (uint64_t)nrs * nqs;
+    if (n_small_pairs) *n_small_pairs = (uint64_t)eb.nrs * eb.nqs;
     return LASH_OK;
 }
 

@@ -505,6 +505,37 @@ class SketchSet:
         self._ctx._check(self._lib.lash_sketch_set_hmh_expected_collisions(self._ctx._h, self._h, int(r0), int(r1), q._h, nc, out.ctypes.data, C.byref(cnt)))
         return out if cnt.value else None
 
+    def pair_block_within(self, r0, r1, max_dist, k, qry=None, n_cols=None, triangle=False, model=1, fp32=False, estimator="fgra",
+                          hll_bias=None, cap=None, stats=None):
+        """`lash dist --max-dist`: the pairs of rows [r0, r1) x columns [0, n_cols) whose distance d (lash_dist_rows' number, before the
+        "same name -> 0" rule) passes d <= max_dist, as numpy arrays (row, col, dist) in (row, col) order — filtered on the GPU, each
+        survivor evaluated exactly on the host (lash_sketch_set_pair_block_within).  cap: at most that many (default: all, growing the
+        buffers as needed).  stats: optional dict, gets n_kept (the full count) and n_candidates (the pairs the filter kernel let through).
+        cardinalities() must have run on both sets."""
+        q = qry or self
+        nc = q.n if n_cols is None else int(n_cols)
+        size = (1 << 12) if cap is None else int(cap)
+        while True:
+            row, col = np.empty(size, np.uint32), np.empty(size, np.uint32)
+            dist = np.empty(size, np.float64)
+            kept, bad, cand = C.c_uint64(), C.c_uint64(), C.c_uint64()
+            rc = self._lib.lash_sketch_set_pair_block_within(self._ctx._h, self._h, int(r0), int(r1), q._h, nc, 1 if triangle else 0, int(k), int(model),
+                                                             1 if fp32 else 0, ULL_ESTIMATORS[estimator], _bias_handle(hll_bias), float(max_dist),
+                                                             row.ctypes.data, col.ctypes.data, dist.ctypes.data, size, C.byref(kept), C.byref(bad),
+                                                             C.byref(cand))
+            if rc == _lib.ERANGE:
+                e = LashError(rc, self._lib.lash_strerror(rc).decode() + " (pair %d)" % bad.value)
+                e.pair = bad.value                                   # (row - r0) * n_cols + col
+                raise e
+            self._ctx._check(rc)
+            if cap is not None or kept.value <= size:
+                break
+            size = kept.value
+        if stats is not None:
+            stats.update(n_kept=kept.value, n_candidates=cand.value)
+        n = min(kept.value, size)
+        return row[:n], col[:n], dist[:n]
+
     def pair_block(self, r0, r1, qry=None, n_cols=None, triangle=False, estimator="fgra", out=None):
         """statistics of rows [r0, r1) against columns [0, n_cols) of `qry` (default: this set) as the dict lash_dist_rows takes.
         `out`: optional dict of preallocated (e.g. pinned) flat arrays 'c', 'n' (uint32), 'u' (float64) of >= (r1-r0)*n_cols."""
