@@ -506,20 +506,12 @@ int lash_sketch_batch_device(lash_ctx *ctx, const lash_params *prm, const uint8_
             identity = identity && genome_rec_off[g] == g && genome_rec_off[g + 1] == (uint64_t)g + 1;
         }
         if (all_small) {
-            ctx->hll_flags_n = 0;
-            ctx->hll_flags_on_host = false;
-            if (prm->algo == LASH_HLL) {                                // (every genome's flag is written by the kernel: nothing to clear)
-                if ((rc = reserve(ctx, ctx->hll_flags, (size_t)n_genomes * 4))) return rc;
-                ctx->hll_flags_n = n_genomes;
-            }
-            if (ev) HIPCHK(ctx, hipEventRecord(ev->e[2], ctx->stream));
-            rc = sole_run(ctx, prm, sp, smax, d_seq, genome_byte_off[n_genomes], d_rec_off, n_rec, any_multi, identity, genome_byte_off, nullptr, n_genomes,
-                          d_out_images, nullptr);
+            rc = sole_call(ctx, prm, sp, n_genomes, ev, [&] {
+                return sole_run(ctx, prm, sp, smax, d_seq, genome_byte_off[n_genomes], d_rec_off, n_rec, any_multi, identity, genome_byte_off, nullptr,
+                                n_genomes, d_out_images, nullptr);
+            });
             if (rc) return rc;
-            if (ev) { HIPCHK(ctx, hipEventRecord(ev->e[3], ctx->stream)); HIPCHK(ctx, hipEventRecord(ev->e[4], ctx->stream)); ev->done = true; }
             ctx->last_sole_only = true;
-            ctx->last.sketch_launches += 1;
-            ctx->last.sketch_workgroups = (uint32_t)std::min<uint64_t>((uint64_t)ctx->cu_count * sp.wg_per_cu, n_genomes);
             ctx->cur_ev = nullptr;
             return LASH_OK;
         }

@@ -1,11 +1,13 @@
 // lash_internal.h — what the host-side translation units of liblash_gfx950.so share (round 6: lash_api.hip was 2 400 lines; it is now
 //   lash_api.hip         library / context / layout entries, the sketch entries (record batches, packed genomes, raw files), the strict FASTX parse
-//   lash_plan.hip        what a sketch call queues: pack, persistent small-genome launch, work-item planning, binned / global tables, amino acids
+//   lash_plan.hip        what a sketch call queues: pack, persistent small-genome launch, binned / global tables, the pure work-item planner
+//                        (plan_items), the stages the nucleotide (sketch_from) and amino-acid (sketch_aa) paths share
 //   lash_hll_replay.hip  HyperLogLog's incremental `sum` in its order-dependent corner, replayed from prefix sketches
 //   lash_dist_api.hip    merge of serialized sketches and the pair-statistics entries of `dist`
 //   sketch_set.hip       resident sketch sets).
 // Everything here lives in namespace lashi (lash_ctx.h) and is called only from inside the library.
 #pragma once
+#include <functional>
 #include <utility>
 #include <vector>
 
@@ -22,6 +24,7 @@ uint64_t sole_max_bytes(const lash_ctx *ctx, const lash_params *prm, const SoleP
 int sole_run(lash_ctx *ctx, const lash_params *prm, const SolePlan &sp, uint64_t max_len, const uint8_t *d_seq, uint64_t seq_bytes,
              const uint64_t *d_rec_off, uint64_t n_rec, bool any_multi, bool rec_identity, const uint64_t *genome_byte_off, const lash_packed *pk,
              uint32_t n_genomes, uint8_t *d_out_images, uint32_t *per_genome_ndel);
+int sole_call(lash_ctx *ctx, const lash_params *prm, const SolePlan &sp, uint32_t n_genomes, EvSet *ev, const std::function<int()> &run);
 int sketch_from(lash_ctx *ctx, const lash_params *prm, const lash_packed *pk, uint8_t *d_out_images, EvSet *ev, bool allow_bins = true);
 int sketch_aa(lash_ctx *ctx, const lash_params *prm, const uint8_t *d_seq, const uint64_t *d_rec_off, uint64_t n_rec,
               const uint64_t *genome_rec_off, const uint64_t *genome_byte_off, uint32_t n_genomes, uint8_t *d_out_images, bool allow_bins = true);

@@ -1,5 +1,6 @@
-// lash_plan.hip — what a sketch call queues: packing raw bytes, the persistent small-genome launch, work-item planning for the sliced
-// kernels (slices, tail split, launch order, deferral), binned / global register tables, the amino-acid branch.  Split out of lash_api.hip
+// lash_plan.hip — what a sketch call queues: packing raw bytes, the persistent small-genome launch, binned / global register tables, work-item
+// planning for the sliced kernels (plan_items: slices, tail split, launch order, deferral; host-only), the stages the nucleotide and the
+// amino-acid branch share (plan choice, buffers, launch dispatch, finalize) and the two branches themselves.  Split out of lash_api.hip
 // in round 6; the extern "C" entries that call in are in lash_api.hip.  Reference: the per-file closure of sketch_files
 // (/root/reference/src/utils.rs:452-508).
 #include "lash_ctx.h"
@@ -282,7 +283,7 @@ static size_t bins_partials(const SketchPlan &plan, const lash_params *prm, size
     if (!plan.bins) return n_items + 1;
     return bins_write_images(prm) ? 1 : n_genomes + 1;
 }
-// the launches of one call, group by group: launch(sa, first item, items) queues the sketch kernels of an item range
+// the launches of one call, group by group: launch(sa, items) queues the sketch kernels of an item range
 template <class Launch>
 static int bins_run(lash_ctx *ctx, const SketchPlan &plan, const lash_params *prm, SketchArgs sa, const BinsRun &br, const std::vector<uint32_t> &item_begin,
                     uint32_t n_items, const uint32_t *d_item_begin, Launch launch)
@@ -313,7 +314,7 @@ static int bins_run(lash_ctx *ctx, const SketchPlan &plan, const lash_params *pr
         sa.bin_genomes = br.d_table + g0;
         sa.bin_genome0 = g0;
         sa.item_base = item_begin[g0];
-        int rc = launch(sa, item_begin[g0], item_begin[g1] - item_begin[g0]);
+        int rc = launch(sa, item_begin[g1] - item_begin[g0]);
         if (rc) return rc;
         BinApplyArgs ba{};
         ba.lists = sa.bin_lists; ba.cnt = br.d_cnt; ba.slab = sa.bin_slab; ba.spill = br.d_spill; ba.genomes = sa.bin_genomes;
@@ -351,6 +352,49 @@ static int global_run(lash_ctx *ctx, const SketchPlan &plan, SketchArgs sa, uint
         sa.item_base = i0;
         if ((rc = launch(sa, n))) return rc;
     }
+    return LASH_OK;
+}
+
+// The sketch launches of a call, whatever the route: binned (group by group), a table in global memory per item (chunk by chunk) or one
+// launch over all items.  launch(sa, n) queues the sketch kernels of n items from sa.item_base on.
+template <class Launch>
+static int launch_items(lash_ctx *ctx, const SketchPlan &plan, const lash_params *prm, const SketchArgs &sa, const BinsRun &br,
+                        const std::vector<uint32_t> &item_begin, const uint32_t *d_item_begin, Launch launch)
+{
+    const uint32_t n_items = item_begin.back();
+    if (plan.bins) return bins_run(ctx, plan, prm, sa, br, item_begin, n_items, d_item_begin, launch);
+    if (!plan.use_lds) return global_run(ctx, plan, sa, n_items, launch);
+    return launch(sa, n_items);
+}
+
+// ---- what the launches of a call share -----------------------------------------------------------------------------------------
+// The fields every launch that writes images takes alike (SketchArgs, SoleArgs, FinalizeArgs): where the images go, what their headers hold,
+// and the HyperLogLog corner flags (arm_hll_flags comes first)
+template <class Args>
+static void image_fields(Args &a, const lash_ctx *ctx, const lash_params *prm, uint8_t *images)
+{
+    a.images = images;
+    a.image_bytes = ::image_bytes(ctx->layout, prm->algo, prm->p);
+    const double alpha = hll_alpha(prm->p);
+    memcpy(&a.alpha_bits, &alpha, 8);
+    a.accumulate = (prm->flags & LASH_F_ACCUMULATE) ? 1 : 0;
+    a.hll_corner = prm->algo == LASH_HLL ? static_cast<uint32_t *>(ctx->hll_flags.ptr) : nullptr;
+    a.lay = layout_dev(ctx->layout, prm->algo);
+    a.k = prm->k;
+    a.p = prm->p;
+}
+
+// which genomes of the call end with a register above 53 - p (write_hll_header; lash_ctx_hll_inexact_sums).  clear: the sliced kernels only
+// raise flags; the persistent kernel writes every genome's flag itself
+static int arm_hll_flags(lash_ctx *ctx, const lash_params *prm, uint32_t n_genomes, bool clear)
+{
+    ctx->hll_flags_n = 0;
+    ctx->hll_flags_on_host = false;
+    if (prm->algo != LASH_HLL) return LASH_OK;
+    int rc;
+    if ((rc = reserve(ctx, ctx->hll_flags, (size_t)n_genomes * 4))) return rc;
+    if (clear) HIPCHK(ctx, hipMemsetAsync(ctx->hll_flags.ptr, 0, (size_t)n_genomes * 4, ctx->stream));
+    ctx->hll_flags_n = n_genomes;
     return LASH_OK;
 }
 
@@ -486,19 +530,9 @@ int sole_run(lash_ctx *ctx, const lash_params *prm, const SolePlan &sp, uint64_t
         sa.genomes = pk->d_descs;
         sa.nvalid = pk->d_nvalid;
     }
-    sa.images = d_out_images;
-    sa.image_bytes = image_bytes;
-    {
-        const double alpha0 = hll_alpha(prm->p);
-        memcpy(&sa.alpha_bits, &alpha0, 8);
-    }
-    sa.accumulate = (prm->flags & LASH_F_ACCUMULATE) ? 1 : 0;
-    sa.hll_corner = prm->algo == LASH_HLL ? static_cast<uint32_t *>(ctx->hll_flags.ptr) : nullptr;
+    image_fields(sa, ctx, prm, d_out_images);
     sa.bitflip = prm->algo == LASH_HMH ? xxh3_bitflip128(prm->seed) : xxh3_bitflip64(prm->seed);
-    sa.lay = layout_dev(ctx->layout, prm->algo);
     sa.nreg32 = prm->algo == LASH_HMH ? HMH_M : prm->algo == LASH_HLL ? (1u << prm->p) : (2u << prm->p);
-    sa.k = prm->k;
-    sa.p = prm->p;
     HIPCHK(ctx, launch_sole(sp, prm->algo, prm->k, x_low, packed, sa, n_wg, ctx->stream));
     unsigned long long *ctr = static_cast<unsigned long long *>(ctx->counter.ptr);
     HIPCHK(ctx, launch_sole_census(sa.wg_counts, n_wg, ctr, ctr + 1, sa.ticket, ctx->stream));
@@ -506,87 +540,80 @@ int sole_run(lash_ctx *ctx, const lash_params *prm, const SolePlan &sp, uint64_t
     return LASH_OK;
 }
 
-int sketch_from(lash_ctx *ctx, const lash_params *prm, const lash_packed *pk, uint8_t *d_out_images, EvSet *ev, bool allow_bins)
+// A call the persistent kernel takes whole (lash_sketch_batch_device: nothing but small genomes; sketch_from: a packed batch of them): the
+// corner flags, the stage events and the counters around run(), which queues sole_run
+int sole_call(lash_ctx *ctx, const lash_params *prm, const SolePlan &sp, uint32_t n_genomes, EvSet *ev, const std::function<int()> &run)
 {
-    const uint32_t n_genomes = pk->n_genomes;
-    // Genomes of at most sole_max bytes go to the persistent kernel (sole_kernels.hip), the others are cut into work items as ever;
-    // blen() is a genome's length as the planning below sees it (0 = not this launch's)
-    const SolePlan sole_plan = make_sole_plan(prm->algo, prm->p, n_genomes, (uint32_t)ctx->cu_count);
-    uint64_t sole_max = sole_max_bytes(ctx, prm, sole_plan);
-    if (pk->direct && n_genomes && pk->h_descs[n_genomes - 1].byte_off + pk->h_descs[n_genomes - 1].byte_len < 16) sole_max = 0;   // (the kernel loads 16 bytes at a time, from inside the buffer)
-    auto blen = [&](uint32_t g) -> uint64_t { return pk->byte_len[g] <= sole_max && sole_max ? 0 : pk->byte_len[g]; };
-    uint32_t n_sole = 0;
-    if (sole_max) for (uint32_t g = 0; g < n_genomes; ++g) n_sole += pk->byte_len[g] <= sole_max;
-    const bool x_low = rule_variant(ctx->layout, prm->algo, prm->flags);   // (HyperMinHash x = low half / HyperLogLog bucket = top bits)
-    // what the persistent kernel's launch needs from a batch in direct mode (ASCII in the caller's buffer)
-    std::vector<uint64_t> sole_gbo;
-    auto sole_launch = [&](uint32_t *ndel) -> int {
-        if (pk->direct) {
-            sole_gbo.resize((size_t)n_genomes + 1);
-            for (uint32_t g = 0; g < n_genomes; ++g) sole_gbo[g] = pk->h_descs[g].byte_off;
-            sole_gbo[n_genomes] = pk->h_descs[n_genomes - 1].byte_off + pk->h_descs[n_genomes - 1].byte_len;
-            bool identity = pk->n_rec == n_genomes;                        // genome g IS record g (then the resident record offsets serve as byte offsets)
-            for (uint32_t g = 0; g < n_genomes && identity; ++g) identity = pk->h_descs[g].rec_begin == g && pk->h_descs[g].rec_end == g + 1u;
-            return sole_run(ctx, prm, sole_plan, sole_max, pk->d_seq, sole_gbo[n_genomes], pk->d_rec_off, pk->n_rec, pk->any_multi, identity, sole_gbo.data(),
-                            nullptr, n_genomes, d_out_images, ndel);
-        }
-        return sole_run(ctx, prm, sole_plan, sole_max, nullptr, 0, nullptr, 0, false, false, nullptr, pk, n_genomes, d_out_images, nullptr);
-    };
-    if (n_sole == n_genomes && n_genomes && !pk->direct) {
-        // a packed batch of small genomes only (lash_sketch_packed_device, raw files, LASH_F_NO_DIRECT): no work items at all
-        int rc;
-        ctx->hll_flags_n = 0;
-        ctx->hll_flags_on_host = false;
-        if (prm->algo == LASH_HLL) {                                    // (every genome's flag is written by the kernel: nothing to clear)
-            if ((rc = reserve(ctx, ctx->hll_flags, (size_t)n_genomes * 4))) return rc;
-            ctx->hll_flags_n = n_genomes;
-        }
-        if (ev) HIPCHK(ctx, hipEventRecord(ev->e[2], ctx->stream));
-        if ((rc = sole_launch(nullptr))) return rc;
-        if (ev) { HIPCHK(ctx, hipEventRecord(ev->e[3], ctx->stream)); HIPCHK(ctx, hipEventRecord(ev->e[4], ctx->stream)); ev->done = true; }
-        ctx->last_packed.push_back(pk);
-        ctx->last.sketch_launches += 1;
-        ctx->last.sketch_workgroups = (uint32_t)std::min<uint64_t>((uint64_t)ctx->cu_count * sole_plan.wg_per_cu, n_genomes);
-        return LASH_OK;
-    }
-    uint64_t total_bytes = 0;
-    for (uint32_t g = 0; g < n_genomes; ++g) total_bytes += blen(g);
-    const bool small_items = n_genomes > n_sole && total_bytes / (n_genomes - n_sole) < 100000u;
-    SketchPlan plan = make_sketch_plan(prm->algo, prm->k, prm->p, x_low, small_items, allow_bins);
-    if (plan.bins) {
-        // a binned launch keeps ~4.6 bytes per input byte of one genome group in HBM: a single genome beyond the budget (a multi-Gbp
-        // input in one call, which the CLI would have streamed in chunks) takes the table-in-global-memory path instead
-        const uint64_t budget = bins_budget_bytes(ctx);
-        uint64_t big = 0;
-        for (uint32_t g = 0; g < n_genomes; ++g) big = std::max<uint64_t>(big, pk->byte_len[g]);
-        if (big * 5 + (uint64_t)plan.nreg32 * 4 + (64u << 20) > budget)
-            plan = make_sketch_plan(prm->algo, prm->k, prm->p, x_low, small_items, false);
-    }
-    const uint64_t image_bytes = ::image_bytes(ctx->layout, prm->algo, prm->p);
+    int rc;
+    if ((rc = arm_hll_flags(ctx, prm, n_genomes, false))) return rc;
+    if (ev) HIPCHK(ctx, hipEventRecord(ev->e[2], ctx->stream));
+    if ((rc = run())) return rc;
+    if (ev) { HIPCHK(ctx, hipEventRecord(ev->e[3], ctx->stream)); HIPCHK(ctx, hipEventRecord(ev->e[4], ctx->stream)); ev->done = true; }
+    ctx->last.sketch_launches += 1;
+    ctx->last.sketch_workgroups = (uint32_t)std::min<uint64_t>((uint64_t)ctx->cu_count * sp.wg_per_cu, n_genomes);
+    return LASH_OK;
+}
 
-    // ---- plan work items: slices of genomes, enough of them to keep every CU's workgroup slots busy ----
-    const bool defer_eligible = prm->algo == LASH_HMH && plan.use_lds && plan.parts_log2 == 0;   // (see plan_d below)
-    const uint32_t lds_wg = plan.lds_bytes + ((pk->direct || defer_eligible || plan.bytes) ? sketch_direct_stage_bytes(plan) : 0u);   // + the waves' staging areas / lists
-    const uint32_t wg_per_cu = plan.use_lds ? std::max(1u, (160u * 1024u) / std::max(lds_wg, 1u)) : 4u;   // 64 KiB + census -> 2
-    const uint64_t slots = (uint64_t)ctx->cu_count * std::min(wg_per_cu, 2048u / plan.threads);
-    uint64_t total_words = 0;
-    for (uint32_t g = 0; g < n_genomes; ++g) total_words += (blen(g) + 15) / 16;
+// ---- work items of the sliced kernels: slices of genomes, enough of them to keep every CU's workgroup slots busy ------------------
+
+// knob values, 0 = the default below.  LASH_SLICE_FACTOR, LASH_ITEM_CAP_WORDS and LASH_TAIL_SPLIT are read once per
+// process; LASH_TAIL_GEO and LASH_DEFER_MIN on every call (the tests flip them in-process)
+struct PlanKnobs {
+    uint64_t slice_factor, item_cap_words;
+    uint32_t tail_split;
+    bool tail_geo;                // A/B knob: 0 = the uniform split of rounds 3-5
+    int64_t defer_min;            // bases per work item; < 0: never
+};
+static PlanKnobs plan_knobs()
+{
+    static const uint64_t slice_factor = getenv("LASH_SLICE_FACTOR") ? std::max(1, atoi(getenv("LASH_SLICE_FACTOR"))) : 0;
+    static const uint64_t item_cap = getenv("LASH_ITEM_CAP_WORDS") ? std::max(1024, atoi(getenv("LASH_ITEM_CAP_WORDS"))) : 0;
+    static const uint32_t tail_split = getenv("LASH_TAIL_SPLIT") ? (uint32_t)std::max(1, atoi(getenv("LASH_TAIL_SPLIT"))) : 0u;
+    const char *dm_env = getenv("LASH_DEFER_MIN");
+    return PlanKnobs{slice_factor, item_cap, tail_split, !(getenv("LASH_TAIL_GEO") && atoi(getenv("LASH_TAIL_GEO")) == 0),
+                     dm_env ? atoll(dm_env) : 600000};
+}
+
+// HyperMinHash launches that may defer their signatures (process_word_defer, ItemPlan::defer)
+static bool may_defer(const SketchPlan &plan) { return plan.algo == LASH_HMH && plan.use_lds && plan.parts_log2 == 0; }
+
+// what a call launches (the amino-acid branch fills the first three fields itself)
+struct ItemPlan {
+    std::vector<WorkItem> items;
+    std::vector<uint32_t> item_begin;   // [n_genomes + 1]: genome g's items are [item_begin[g], item_begin[g + 1])
+    uint32_t max_slices = 0;            // most slices any genome is cut into
+    bool all_sole = false;              // every genome has exactly one work item
+    std::vector<uint32_t> order;        // launch order (SketchArgs::item_order), or empty: index order
+    std::vector<uint32_t> handover;     // direct mode: GenomeDesc::handover per genome
+    uint64_t n_coarse = 0;              // slices as first cut, before the tail split
+    uint64_t total_words = 0;           // 16-byte words of all the launch's genomes
+    bool defer = false;                 // SketchPlan::defer of the launch
+};
+
+// blen[g]: genome g's bytes as this launch sees them (0 = not this launch's: the persistent kernel takes it); slots: the workgroups the chip
+// runs at a time.  Pure: no HIP call, no context.
+static ItemPlan plan_items(const std::vector<uint64_t> &blen, const SketchPlan &plan, uint64_t slots, bool direct, bool stream_first,
+                           const PlanKnobs &knobs)
+{
+    const uint32_t n_genomes = (uint32_t)blen.size();
+    const bool defer_eligible = may_defer(plan);
+    ItemPlan ip;
+    for (uint64_t b : blen) ip.total_words += (b + 15) / 16;
     const uint64_t step = (uint64_t)plan.threads * SKETCH_WORDS_PER_THREAD;
     const uint64_t min_slice = step * 8;                           // amortise the LDS clear + flush
-    static const uint64_t slice_factor_env = getenv("LASH_SLICE_FACTOR") ? std::max(1, atoi(getenv("LASH_SLICE_FACTOR"))) : 0;
     uint64_t len_lo = ~0ull, len_hi = 0;
-    for (uint32_t g = 0; g < n_genomes; ++g) { len_lo = std::min<uint64_t>(len_lo, blen(g)); len_hi = std::max<uint64_t>(len_hi, blen(g)); }
+    for (uint64_t b : blen) { len_lo = std::min(len_lo, b); len_hi = std::max(len_hi, b); }
     const bool equal_genomes = n_genomes > 0 && len_hi <= len_lo + len_lo / 4;
     // HyperMinHash launches that may defer their signatures (below) like long items — a slice starts with an empty table, and the share
     // of k-mers that pass the filter is 2.8 % over a whole 5 Mbp genome, 7.7 % over a third of one — and the split tail (below) has
     // taken over what the many small slices were for: 2x the slots there (1 000 x 5 Mbp: 4.39 -> 4.33 ms, round 3), and for batches of
     // EQUAL genomes 1x: BASELINE configs[1], 1 000 x 5 Mbp, runs whole genomes in two rounds instead of thirds in six (4.12 -> 3.95 ms,
     // profiles/r04/cfg1_slicing.txt; a collection of unequal genomes loses a third with that: it needs the item cap below)
-    const uint64_t slice_factor = slice_factor_env ? slice_factor_env : (defer_eligible ? (equal_genomes ? 1 : 2) : 4);   // tuning knob: the
+    const uint64_t slice_factor = knobs.slice_factor ? knobs.slice_factor : (defer_eligible ? (equal_genomes ? 1 : 2) : 4);   // tuning knob: the
     // sketch time is flat from 2x to 24x the slots (4.87-4.91 ms on the default bench), the finalize time grows with it
-    uint64_t target = total_words / (slots * slice_factor) + 1;
+    uint64_t target = ip.total_words / (slots * slice_factor) + 1;
     // a table in global memory per work item (UltraLogLog p >= 23: 64 .. 512 MiB each, zeroed before and read back after): few, long items
-    if (!plan.use_lds) target = total_words / std::max<uint64_t>(1, slots / 4) + 1;
+    if (!plan.use_lds) target = ip.total_words / std::max<uint64_t>(1, slots / 4) + 1;
     target = std::max(target, min_slice);
     {
         // When some genome is cut anyway (so partials and the finalize pass exist whatever the slicing), items of at most 1 MiB: a
@@ -594,25 +621,18 @@ int sketch_from(lash_ctx *ctx, const lash_params *prm, const lash_packed *pk, ui
         // items each — would run on a fraction of the chip (2 000 mixed genomes: that launch 1.6 ms -> 0.5 ms).
         // (2 MiB where the launch may defer signatures: that kernel wants long items — the same collection 7.83 -> 7.50 ms, while the
         // HyperLogLog kernel loses with the larger items, 8.09 -> 8.49 ms)
-        static const uint64_t cap_env = getenv("LASH_ITEM_CAP_WORDS") ? std::max(1024, atoi(getenv("LASH_ITEM_CAP_WORDS"))) : 0;
-        const uint64_t cap = cap_env ? cap_env : (defer_eligible ? 131072 : 65536);
+        const uint64_t cap = knobs.item_cap_words ? knobs.item_cap_words : (defer_eligible ? 131072 : 65536);
         // (only for batches of unequal genomes: a batch of equal ones keeps its few large items — when those are soft-masked they all
         // are, every item is busy in both launches, and smaller items only add ramp-up: -3 % on bench.py --dirty lower)
         bool any_cut = false;
-        uint64_t lo = ~0ull, hi = 0;
-        for (uint32_t g = 0; g < n_genomes; ++g) {
-            any_cut = any_cut || (((blen(g) + 15) / 16 + 3) & ~3ull) > target;
-            lo = std::min<uint64_t>(lo, blen(g)); hi = std::max<uint64_t>(hi, blen(g));
-        }
-        if (any_cut && hi > lo + lo / 4) target = std::max(min_slice, std::min(target, cap));
+        for (uint64_t b : blen) any_cut = any_cut || (((b + 15) / 16 + 3) & ~3ull) > target;
+        if (any_cut && !equal_genomes) target = std::max(min_slice, std::min(target, cap));
     }
-    std::vector<WorkItem> items;
-    uint32_t max_slices = 0;                                       // most slices any genome is cut into
-    bool all_sole = plan.parts_log2 == 0 && plan.use_lds && !plan.bins && n_genomes > 0;   // every genome has exactly one work item
-    std::vector<uint32_t> item_begin(n_genomes + 1, 0);
-    items.reserve(n_genomes * 2);
+    ip.all_sole = plan.parts_log2 == 0 && plan.use_lds && !plan.bins && n_genomes > 0;
+    ip.item_begin.assign(n_genomes + 1, 0);
+    ip.items.reserve(n_genomes * 2);
     auto slicing = [&](uint32_t g, uint64_t &nw, uint64_t &ns, uint64_t &per) {
-        nw = ((blen(g) + 15) / 16 + 3) & ~3ull;
+        nw = ((blen[g] + 15) / 16 + 3) & ~3ull;
         ns = nw ? (nw + target - 1) / target : 0;
         per = nw ? (((nw + ns - 1) / ns) + 3) & ~3ull : 0;
     };
@@ -620,33 +640,31 @@ int sketch_from(lash_ctx *ctx, const lash_params *prm, const lash_packed *pk, ui
     // few items it holds (600 x 5 Mbp in 2 400 items = 4.7 rounds took the time of 5; 12 500 whole genomes 24.4 -> 25).  The last
     // round's worth of slices is therefore cut into quarters: the launch ends on a quarter-round boundary instead.  Index order is
     // launch order, so the small items are the ones handed out last.
-    static const uint32_t tail_split_env = getenv("LASH_TAIL_SPLIT") ? (uint32_t)std::max(1, atoi(getenv("LASH_TAIL_SPLIT"))) : 0u;
     // (halves where whole genomes may defer signatures: a quarter of a genome fills its table four times over)
     // (none where every genome goes straight to stream_sketch_kernel — recent batches were soft-masked: a wave of that kernel walks a
     //  contiguous sixteenth of its item and pays per part: its ring's warm-up, the look-ahead past its part, a last batch under a
     //  mask.  10 kb blocks 2.94 -> 2.80 ms, 2.5 kb blocks 3.39 -> 3.27 ms per 1 000 x 5 Mbp)
-    const uint32_t tail_split = tail_split_env ? tail_split_env : (pk->direct && pk->stream_first ? 1u : (defer_eligible && equal_genomes ? 2u : 4u));
+    const uint32_t tail_split = knobs.tail_split ? knobs.tail_split : (direct && stream_first ? 1u : (defer_eligible && equal_genomes ? 2u : 4u));
     const uint64_t tail_min = min_slice / 8;                        // 32 kb of sequence: 15 us of a workgroup's time
-    const bool tail_geo = !(getenv("LASH_TAIL_GEO") && atoi(getenv("LASH_TAIL_GEO")) == 0);   // A/B knob (read per call): 0 = the uniform split of rounds 3-5
-    uint64_t n_coarse = 0, fine_from = ~0ull;
+    uint64_t fine_from = ~0ull;
     uint64_t c_lo = ~0ull, c_hi = 0;                               // smallest and largest slice
     for (uint32_t g = 0; g < n_genomes; ++g) {
         uint64_t nw, ns, per;
         slicing(g, nw, ns, per);
         if (!nw) continue;
         const uint64_t cnt = (nw + per - 1) / per, last = nw - (cnt - 1) * per;
-        n_coarse += cnt;
+        ip.n_coarse += cnt;
         c_lo = std::min(c_lo, last); c_hi = std::max(c_hi, cnt > 1 ? per : last);
     }
     const bool unequal = c_hi > c_lo + c_lo / 4;                   // then the launch goes longest first (below) and ends on its small items anyway
     // (two or three rounds' worth in quarters, or halves / eighths: the same within noise)
-    if (plan.use_lds && tail_split > 1 && n_coarse > slots && !unequal) fine_from = n_coarse - slots;
+    if (plan.use_lds && tail_split > 1 && ip.n_coarse > slots && !unequal) fine_from = ip.n_coarse - slots;
     uint64_t ci = 0;                                               // coarse slice counter over the batch
     for (uint32_t g = 0; g < n_genomes; ++g) {
-        item_begin[g] = (uint32_t)items.size();
+        ip.item_begin[g] = (uint32_t)ip.items.size();
         uint64_t nw, ns, per;
         slicing(g, nw, ns, per);
-        if (nw == 0) { all_sole = false; continue; }               // no work item at all: finalize writes the empty image (or it is the
+        if (nw == 0) { ip.all_sole = false; continue; }            // no work item at all: finalize writes the empty image (or it is the
                                                                    // persistent kernel's: FinalizeArgs::skip_max_len)
         uint32_t s = 0;
         const bool whole = ns == 1 && plan.parts_log2 == 0 && plan.use_lds && !plan.bins;
@@ -660,93 +678,285 @@ int sketch_from(lash_ctx *ctx, const lash_params *prm, const lash_packed *pk, ui
                 // (profiles/r06/dirty_2500000_trace.txt: the last items started at 2.5 of 3.5 ms).  Ever smaller items towards the end
                 // bound that tail whatever the bytes cost; on clean input it is neutral (12 500 x 5 Mbp, 1 000 x 5 Mbp: profiles/r06/tail_geo_ab.txt)
                 uint64_t split = tail_split;
-                const uint64_t from_end = n_coarse - 1 - ci;
-                if (tail_geo && from_end < slots / 2) split *= 2;
-                if (tail_geo && from_end < slots / 4) split *= 2;
+                const uint64_t from_end = ip.n_coarse - 1 - ci;
+                if (knobs.tail_geo && from_end < slots / 2) split *= 2;
+                if (knobs.tail_geo && from_end < slots / 4) split *= 2;
                 while (split > 1 && (e - b) / split < tail_min) split /= 2;
                 if (split > 1) sub = ((((e - b) + split - 1) / split) + 3) & ~3ull;
             }
             const bool sole = whole && sub == e - b;
             for (uint64_t bb = b; bb < e; bb += sub, ++s)
                 for (uint32_t part = 0; part < (1u << plan.parts_log2); ++part)               // slice index | pass << 16
-                    items.push_back(WorkItem{g, (uint32_t)bb, (uint32_t)std::min(e, bb + sub), (s & 0x7FFFu) | (part << 16) | (sole ? ITEM_SOLE : 0u)});
+                    ip.items.push_back(WorkItem{g, (uint32_t)bb, (uint32_t)std::min(e, bb + sub), (s & 0x7FFFu) | (part << 16) | (sole ? ITEM_SOLE : 0u)});
         }
-        max_slices = std::max<uint32_t>(max_slices, s);
-        if (s != 1) all_sole = false;
+        ip.max_slices = std::max<uint32_t>(ip.max_slices, s);
+        if (s != 1) ip.all_sole = false;
     }
-    item_begin[n_genomes] = (uint32_t)items.size();
-    const uint32_t n_items = (uint32_t)items.size();
-    if (pk->direct) {
+    ip.item_begin[n_genomes] = (uint32_t)ip.items.size();
+    const uint32_t n_items = (uint32_t)ip.items.size();
+    if (direct) {
         // how many waves must judge a genome too dirty before it is handed over: one for a genome of a few items, 1 in 32 for a 3 Gbp
         // read set cut into thousands (where SOME wave always meets four reads with an N among its first tiles)
-        lash_packed *mpk = const_cast<lash_packed *>(pk);
+        ip.handover.resize(n_genomes);
         for (uint32_t g = 0; g < n_genomes; ++g)
-            mpk->h_descs[g].handover = std::max<uint32_t>(1u, (item_begin[g + 1] - item_begin[g]) * (plan.threads / 64u) / 32u);
+            ip.handover[g] = std::max<uint32_t>(1u, (ip.item_begin[g + 1] - ip.item_begin[g]) * (plan.threads / 64u) / 32u);
     }
     // Launch order: longest items first when their sizes differ (a collection of 0.6 .. 12 Mbp genomes lost 11 % to the tail of a
     // launch in genome order: the hardware hands workgroups out in index order, and a 3.6 MB item that starts last runs alone).
     // A bucket sort on the size's leading bits: O(items), stable inside a bucket (neighbouring items still share cache lines).
-    std::vector<uint32_t> order;
-    {
-        if (n_items > slots && unequal && !plan.bins && plan.use_lds) { // (binned / global-table launches run their items range by range, in order)
-            auto bucket = [&](uint32_t n) {                             // 8 buckets per octave, larger sizes first
-                const uint32_t e = 31u - (uint32_t)__builtin_clz(n | 1u);
-                const uint32_t m = e >= 3 ? (n >> (e - 3)) & 7u : 0u;
-                return 255u - (e * 8u + m);
-            };
-            uint32_t count[257] = {0};
-            for (const WorkItem &w : items) ++count[bucket(w.word_end - w.word_begin) + 1];
-            for (int b = 0; b < 256; ++b) count[b + 1] += count[b];
-            order.resize(n_items);
-            for (uint32_t i = 0; i < n_items; ++i) order[count[bucket(items[i].word_end - items[i].word_begin)]++] = i;
-        }
+    if (n_items > slots && unequal && !plan.bins && plan.use_lds) {     // (binned / global-table launches run their items range by range, in order)
+        auto bucket = [&](uint32_t n) {                                 // 8 buckets per octave, larger sizes first
+            const uint32_t e = 31u - (uint32_t)__builtin_clz(n | 1u);
+            const uint32_t m = e >= 3 ? (n >> (e - 3)) & 7u : 0u;
+            return 255u - (e * 8u + m);
+        };
+        uint32_t count[257] = {0};
+        for (const WorkItem &w : ip.items) ++count[bucket(w.word_end - w.word_begin) + 1];
+        for (int b = 0; b < 256; ++b) count[b + 1] += count[b];
+        ip.order.resize(n_items);
+        for (uint32_t i = 0; i < n_items; ++i) ip.order[count[bucket(ip.items[i].word_end - ip.items[i].word_begin)]++] = i;
     }
     // HyperMinHash with deferred signatures (process_word_defer) pays off when a work item's table fills up early in the item, i.e.
     // when items are long: the share of k-mers that can still change their bucket is 2.8 % at 5 Mbp per item, 10 % at 1 Mbp
     // (profiles/r03/defer/ab.txt: -12 % of the kernel's time at 5 Mbp per item, -5.5 % at 1 Mbp, -3 % at 1.25 Mbp slices, +3 % at
     // 0.73 Mbp, +17 % at 0.26 Mbp; with round 4's threshold words and per-lane stacks, profiles/r04/defer/items.txt: -13.8 % at
     // 2 Mbp, -6.5 % at 1 Mbp, -2.6 % at 750 kbp, -0.7 % at 600 kbp, +1 % at 500 kbp, +6.5 % at 400 kbp, +19 % at 200 kbp)
-    SketchPlan plan_d = plan;
-    {
-        const char *dm_env = getenv("LASH_DEFER_MIN");                       // (read per call: the tests flip it in-process)
-        const int64_t defer_min = dm_env ? atoll(dm_env) : 600000;          // bases per work item; < 0: never
-        // (judged on the slices as first cut: the quarters at the launch's tail would pull the mean of a few-round launch under the line)
-        plan_d.defer = defer_eligible && n_coarse > 0 && defer_min >= 0 && total_words * 16 / n_coarse >= (uint64_t)defer_min;
+    // (judged on the slices as first cut: the quarters at the launch's tail would pull the mean of a few-round launch under the line)
+    ip.defer = defer_eligible && ip.n_coarse > 0 && knobs.defer_min >= 0 && ip.total_words * 16 / ip.n_coarse >= (uint64_t)knobs.defer_min;
+    return ip;
+}
+
+// ---- the stages both sliced paths (nucleotides, amino acids) queue ---------------------------------------------------------------
+// The sketch plan.  A binned launch keeps ~4.6 bytes per input byte of one genome group in HBM: a single genome beyond the budget (a
+// multi-Gbp input in one call, which the CLI would have streamed in chunks) takes the table-in-global-memory path instead.  largest_hbm:
+// the caller's estimate of what its largest genome takes.
+static SketchPlan choose_plan(lash_ctx *ctx, const lash_params *prm, bool small_items, bool allow_bins, uint64_t largest_hbm)
+{
+    const bool x_low = rule_variant(ctx->layout, prm->algo, prm->flags);   // (HyperMinHash x = low half / HyperLogLog bucket = top bits)
+    SketchPlan plan = make_sketch_plan(prm->algo, prm->k, prm->p, x_low, small_items, allow_bins);
+    if (plan.bins && largest_hbm + (uint64_t)plan.nreg32 * 4 + (64u << 20) > bins_budget_bytes(ctx))
+        plan = make_sketch_plan(prm->algo, prm->k, prm->p, x_low, small_items, false);
+    return plan;
+}
+
+// Room for what the sketch stage leaves (partials, per-item k-mer counts, the census counter) and, for a binned launch, its lists
+// (bins_prepare; entries[g]: an upper bound of what genome g's items push).  br.fits == false: a genome whose lists outgrow the budget
+// after all (choose_plan's estimate is coarser than bins_prepare's sizing: ADVICE r4) — the caller plans the call again without bins, a
+// table in global memory per work item.  Nothing has been queued yet.
+static int reserve_stage(lash_ctx *ctx, const lash_params *prm, const SketchPlan &plan, const ItemPlan &ip, const std::vector<uint64_t> &entries,
+                         BinsRun &br)
+{
+    const size_t n_items = ip.items.size(), n_genomes = ip.item_begin.size() - 1;
+    const size_t n_virtual = plan.bins ? n_genomes : 0;               // binned launches: one k-mer count per genome behind the items'
+    int rc;
+    if ((rc = reserve(ctx, ctx->partials, bins_partials(plan, prm, n_items, n_genomes) * plan.partial_stride))) return rc;
+    if ((rc = reserve(ctx, ctx->item_kmers, (n_items + n_virtual + 1) * 4))) return rc;
+    if ((rc = reserve(ctx, ctx->counter, 256))) return rc;
+    return plan.bins ? bins_prepare(ctx, plan, entries, (uint32_t)n_genomes, br) : LASH_OK;
+}
+
+static SketchArgs sketch_args(const lash_ctx *ctx, const lash_params *prm, const SketchPlan &plan, const WorkItem *d_items, uint8_t *images)
+{
+    SketchArgs sa{};
+    image_fields(sa, ctx, prm, images);
+    sa.bitflip = prm->algo == LASH_HMH ? xxh3_bitflip128(prm->seed) : xxh3_bitflip64(prm->seed);
+    sa.items = d_items;
+    sa.partials = static_cast<uint8_t *>(ctx->partials.ptr);
+    sa.gregs = static_cast<uint32_t *>(ctx->gregs.ptr);
+    sa.item_kmers = static_cast<uint32_t *>(ctx->item_kmers.ptr);
+    sa.partial_stride = plan.partial_stride;
+    sa.nreg32 = plan.nreg32 >> plan.parts_log2;                 // register words of one pass
+    return sa;
+}
+
+// Reduce + finalize: the partials into the images, or the census alone where every genome's one work item wrote its image.  fa: the call's
+// items, genome_item_begin, nvalid and skip fields; group_above: slices per genome from which groups of them are folded first.
+static int finalize_run(lash_ctx *ctx, const lash_params *prm, const SketchPlan &plan, const BinsRun &br, const ItemPlan &ip, FinalizeArgs fa,
+                        uint32_t group_above, uint8_t *images)
+{
+    const uint32_t n_items = (uint32_t)ip.items.size(), n_genomes = (uint32_t)ip.item_begin.size() - 1;
+    uint32_t max_slices = ip.max_slices;
+    image_fields(fa, ctx, prm, images);
+    fa.partials = static_cast<const uint8_t *>(ctx->partials.ptr);
+    fa.item_kmers = static_cast<const uint32_t *>(ctx->item_kmers.ptr);
+    if (plan.bins) {                                               // one partial per genome (bins_apply_kernel), its k-mer count behind the items'
+        fa.item_kmers += n_items;
+        fa.items = br.d_vitems;
+        fa.genome_item_begin = br.d_vbegin;
+        max_slices = 1;
     }
+    fa.kmer_counter = static_cast<unsigned long long *>(ctx->counter.ptr);
+    fa.partial_stride = plan.partial_stride;
+    fa.partial_base_off = 0;
+    fa.algo = prm->algo;
+    fa.parts_log2 = plan.parts_log2;
+    fa.src_images = 0;
+    // one finalize workgroup walks all of a genome's partials: fine for a handful of slices, 20 ms for the 4 096 slices of
+    // a metagenome-sized input (BASELINE configs[4]) -> fold groups of 32 slices first (until <= 16 heads remain)
+    // (from 9 slices on: finalize_kernel's walk is serial — a dependent load per slice and word — and the tail quarters give a
+    // genome up to 16: 300 x 5 Mbp, finalize stage 0.27 -> 0.15 ms)
+    fa.group = 0;
+    if (max_slices > group_above && n_genomes <= 65535u)
+        for (fa.group = 32u; (max_slices + fa.group - 1) / fa.group > 16u; fa.group *= 32u) {}
+    if (plan.bins && bins_write_images(prm)) {
+        // bins_apply_kernel wrote the images, headers and census itself
+    } else if (ip.all_sole) {
+        HIPCHK(ctx, launch_census(fa, n_genomes, ctx->stream));            // every image was written by its one work item
+    } else {
+        HIPCHK(ctx, launch_reduce_groups(fa, n_genomes, max_slices, ctx->stream));
+        HIPCHK(ctx, launch_finalize(fa, n_genomes, ctx->stream));
+    }
+    return LASH_OK;
+}
+
+// diagnostic, LASH_ITEM_TRACE=file (tools/item_trace.py): when and where every workgroup of a direct launch ran, appended as text
+static int item_trace_begin(lash_ctx *ctx, uint32_t n_items, SketchArgs &sa)
+{
+    if (!getenv("LASH_ITEM_TRACE") || !n_items) return LASH_OK;
+    HIPCHK(ctx, hipMalloc(&sa.item_trace, (size_t)n_items * 32));
+    HIPCHK(ctx, hipMemsetAsync(sa.item_trace, 0, (size_t)n_items * 32, ctx->stream));
+    return LASH_OK;
+}
+static int item_trace_end(lash_ctx *ctx, const ItemPlan &ip, uint32_t threads, SketchArgs &sa)
+{
+    if (!sa.item_trace) return LASH_OK;
+    const uint32_t n_items = (uint32_t)ip.items.size();
+    std::vector<unsigned long long> h((size_t)n_items * 4);
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    HIPCHK(ctx, hipMemcpy(h.data(), sa.item_trace, h.size() * 8, hipMemcpyDeviceToHost));
+    (void)hipFree(sa.item_trace);
+    sa.item_trace = nullptr;
+    if (FILE *f = fopen(getenv("LASH_ITEM_TRACE"), "a")) {
+        fprintf(f, "# launch: %u items, %u threads, order %s; columns: slot item genome word_begin word_end start_10ns end_10ns hw_id xcc_id\n",
+                n_items, threads, ip.order.empty() ? "item" : "longest first");
+        for (uint32_t b = 0; b < n_items; ++b) {
+            const uint32_t i = ip.order.empty() ? b : ip.order[b];
+            const WorkItem &w = ip.items[i];
+            fprintf(f, "%u %u %u %u %u %llu %llu %u %u\n", b, i, w.genome, w.word_begin, w.word_end, h[4ull * i], h[4ull * i + 1],
+                    (unsigned)(h[4ull * i + 2] & 0xFFFFFFFFu), (unsigned)(h[4ull * i + 2] >> 32));
+        }
+        fclose(f);
+    }
+    return LASH_OK;
+}
+
+// The persistent kernel over the small genomes of a batch: from the caller's ASCII in direct mode, else from the packed words.  ndel: see
+// sole_run (direct mode only)
+static int sole_batch(lash_ctx *ctx, const lash_params *prm, const SolePlan &sp, uint64_t sole_max, const lash_packed *pk, uint8_t *images,
+                      uint32_t *ndel)
+{
+    const uint32_t n = pk->n_genomes;
+    if (!pk->direct) return sole_run(ctx, prm, sp, sole_max, nullptr, 0, nullptr, 0, false, false, nullptr, pk, n, images, nullptr);
+    std::vector<uint64_t> gbo((size_t)n + 1);
+    for (uint32_t g = 0; g < n; ++g) gbo[g] = pk->h_descs[g].byte_off;
+    gbo[n] = pk->h_descs[n - 1].byte_off + pk->h_descs[n - 1].byte_len;
+    bool identity = pk->n_rec == n;                               // genome g IS record g (then the resident record offsets serve as byte offsets)
+    for (uint32_t g = 0; g < n && identity; ++g) identity = pk->h_descs[g].rec_begin == g && pk->h_descs[g].rec_end == g + 1u;
+    return sole_run(ctx, prm, sp, sole_max, pk->d_seq, gbo[n], pk->d_rec_off, pk->n_rec, pk->any_multi, identity, gbo.data(), nullptr, n, images, ndel);
+}
+
+// Direct mode: the direct pass (ASCII in; sparse and coarse dirt handled in place), then stream_sketch_kernel over the genomes it flagged,
+// compacted on the fly.  Launches that run their items in ranges (bins, global tables) run both kernels range by range; a plain launch runs
+// the second one behind the dirty-tile probe.  direct_ms: the direct launch alone, or every range's two.  Leaves sa with the direct pass's
+// flags and counters (sa.ndel / ndel2 for the persistent kernel).
+static int direct_launches(lash_ctx *ctx, const lash_params *prm, const SketchPlan &plan, lash_packed *pk, const ItemPlan &ip, SketchArgs &sa,
+                           const BinsRun &br, const uint32_t *d_item_begin, EvSet *ev)
+{
+    const uint32_t n_items = (uint32_t)ip.items.size(), n_genomes = pk->n_genomes;
+    const bool ranged = plan.bins || !plan.use_lds, direct_pass = !pk->stream_first, timed = ev && (ranged || direct_pass);
+    sa.seq = pk->d_seq;
+    sa.brk_bytes = static_cast<const uint32_t *>(pk->brk_bytes.ptr);
+    sa.dirty = pk->d_dirty;
+    sa.rec_off = pk->d_rec_off;
+    sa.nonuniform = pk->d_dirty + 3 * (size_t)n_genomes + 1;
+    sa.nslow = pk->d_dirty + n_genomes + 1;
+    sa.ndel = sa.nslow + n_genomes;
+    sa.ndel2 = pk->d_dirty + 4 * (size_t)n_genomes + 2;
+    int rc;
+    if (pk->stream_first)   // recent batches were full of finely fragmented dirt: every genome goes straight to the compacting kernel
+        HIPCHK(ctx, hipMemsetAsync(pk->d_dirty, 0x01, (size_t)n_genomes * 4, ctx->stream));
+    if (direct_pass && !ranged && (rc = item_trace_begin(ctx, n_items, sa))) return rc;
+    if (timed) HIPCHK(ctx, hipEventRecord(ev->e[6], ctx->stream));
+    rc = launch_items(ctx, plan, prm, sa, br, ip.item_begin, d_item_begin, [&](const SketchArgs &a, uint32_t cnt) -> int {
+        if (direct_pass) HIPCHK(ctx, launch_sketch(plan, a, cnt, ctx->stream, true));
+        if (ranged) HIPCHK(ctx, launch_sketch_stream(plan, a, cnt, ctx->stream));
+        return LASH_OK;
+    });
+    if (rc) return rc;
+    if (timed) { HIPCHK(ctx, hipEventRecord(ev->e[5], ctx->stream)); ev->direct = true; }
+    if ((rc = item_trace_end(ctx, ip, plan.threads, sa))) return rc;
+    if (direct_pass) {
+        if ((rc = probe_dirty(ctx, pk, ctx->stream))) return rc;
+        ctx->last.direct_launches += n_items ? 1 : 0;
+        ctx->last.defer_launches += (n_items && plan.defer) ? 1 : 0;
+    }
+    if (!ranged) HIPCHK(ctx, launch_sketch_stream(plan, sa, n_items, ctx->stream));
+    return LASH_OK;
+}
+
+int sketch_from(lash_ctx *ctx, const lash_params *prm, const lash_packed *pk, uint8_t *d_out_images, EvSet *ev, bool allow_bins)
+{
+    const uint32_t n_genomes = pk->n_genomes;
+    lash_packed *mpk = const_cast<lash_packed *>(pk);
+    // Genomes of at most sole_max bytes go to the persistent kernel (sole_kernels.hip), the others are cut into work items as ever;
+    // blen[g] is a genome's length as the planning sees it (0 = not this launch's)
+    const SolePlan sole_plan = make_sole_plan(prm->algo, prm->p, n_genomes, (uint32_t)ctx->cu_count);
+    uint64_t sole_max = sole_max_bytes(ctx, prm, sole_plan);
+    if (pk->direct && n_genomes && pk->h_descs[n_genomes - 1].byte_off + pk->h_descs[n_genomes - 1].byte_len < 16) sole_max = 0;   // (the kernel loads 16 bytes at a time, from inside the buffer)
+    std::vector<uint64_t> blen(n_genomes);
+    uint32_t n_sole = 0;
+    uint64_t total_bytes = 0, largest = 0;
+    for (uint32_t g = 0; g < n_genomes; ++g) {
+        const bool sole = sole_max && pk->byte_len[g] <= sole_max;
+        blen[g] = sole ? 0 : pk->byte_len[g];
+        n_sole += sole;
+        total_bytes += blen[g];
+        largest = std::max<uint64_t>(largest, pk->byte_len[g]);
+    }
+    int rc;
+    if (n_sole == n_genomes && n_genomes && !pk->direct) {
+        // a packed batch of small genomes only (lash_sketch_packed_device, raw files, LASH_F_NO_DIRECT): no work items at all
+        if ((rc = sole_call(ctx, prm, sole_plan, n_genomes, ev, [&] { return sole_batch(ctx, prm, sole_plan, sole_max, pk, d_out_images, nullptr); })))
+            return rc;
+        ctx->last_packed.push_back(pk);
+        return LASH_OK;
+    }
+    const bool small_items = n_genomes > n_sole && total_bytes / (n_genomes - n_sole) < 100000u;
+    SketchPlan plan = choose_plan(ctx, prm, small_items, allow_bins, largest * 5);
+    const uint32_t lds_wg = plan.lds_bytes + ((pk->direct || may_defer(plan) || plan.bytes) ? sketch_direct_stage_bytes(plan) : 0u);   // + the waves' staging areas / lists
+    const uint32_t wg_per_cu = plan.use_lds ? std::max(1u, (160u * 1024u) / std::max(lds_wg, 1u)) : 4u;   // 64 KiB + census -> 2
+    const uint64_t slots = (uint64_t)ctx->cu_count * std::min(wg_per_cu, 2048u / plan.threads);
+    const ItemPlan ip = plan_items(blen, plan, slots, pk->direct, pk->stream_first, plan_knobs());
+    const uint32_t n_items = (uint32_t)ip.items.size();
+    plan.defer = ip.defer;
+    if (pk->direct)
+        for (uint32_t g = 0; g < n_genomes; ++g) mpk->h_descs[g].handover = ip.handover[g];
     TRACE("sketch: planned");
 
-    int rc;
-    const size_t n_virtual = plan.bins ? n_genomes : 0;               // binned launches: one k-mer count per genome behind the items'
-    if ((rc = reserve(ctx, ctx->partials, bins_partials(plan, prm, n_items, n_genomes) * plan.partial_stride))) return rc;
-    if ((rc = reserve(ctx, ctx->item_kmers, (size_t)(n_items + n_virtual + 1) * 4))) return rc;
-    if ((rc = reserve(ctx, ctx->counter, 256))) return rc;
-    BinsRun bins_run_state;
+    std::vector<uint64_t> entries;
     if (plan.bins) {
         // entries a genome's work items push: 16 per lane and word for every tile a wave takes part in (masked positions and the
         // idle lanes of a busy wave included); what dirt adds on top (junction walks, a second pass by the compacting kernel) goes to
         // the genome's fallback table if its lists run full
-        std::vector<uint64_t> entries(n_genomes, 0);
+        entries.assign(n_genomes, 0);
         const uint64_t tile_words = (uint64_t)plan.threads * SKETCH_WORDS_PER_THREAD;
-        for (const WorkItem &w : items) entries[w.genome] += ((w.word_end - w.word_begin + tile_words - 1) / tile_words) * tile_words * 16;
-        if ((rc = bins_prepare(ctx, plan, entries, n_genomes, bins_run_state))) return rc;
-        // a genome whose lists outgrow the budget after all (the estimate above is coarser than bins_prepare's sizing: ADVICE r4): the
-        // call is planned again without bins — a table in global memory per work item, as the comment above promises.  Nothing has
-        // been queued yet.
-        if (!bins_run_state.fits) return sketch_from(ctx, prm, pk, d_out_images, ev, false);
+        for (const WorkItem &w : ip.items) entries[w.genome] += ((w.word_end - w.word_begin + tile_words - 1) / tile_words) * tile_words * 16;
     }
+    BinsRun br;
+    if ((rc = reserve_stage(ctx, prm, plan, ip, entries, br))) return rc;
+    if (!br.fits) return sketch_from(ctx, prm, pk, d_out_images, ev, false);
     const WorkItem *d_items;
     const uint32_t *d_item_begin, *d_item_order = nullptr;
     {
-        std::vector<Section> sec = {{items.data(), (size_t)n_items * sizeof(WorkItem), 0},
-                                    {item_begin.data(), (size_t)(n_genomes + 1) * 4, 0}};
-        lash_packed *mpk = const_cast<lash_packed *>(pk);
+        std::vector<Section> sec = {{ip.items.data(), (size_t)n_items * sizeof(WorkItem), 0},
+                                    {ip.item_begin.data(), (size_t)(n_genomes + 1) * 4, 0}};
         if (pk->direct) {                                          // everything this call needs in ONE copy
             sec.push_back({pk->h_descs.data(), pk->h_descs.size() * sizeof(GenomeDesc), 0});
             sec.push_back({pk->h_tile_begin.data(), pk->h_tile_begin.size() * 4, 0});
             sec.push_back({pk->h_nvalid.data(), pk->h_nvalid.size() * 8, 0});
         }
         const size_t order_sec = sec.size();
-        if (!order.empty()) sec.push_back({order.data(), order.size() * 4, 0});
+        if (!ip.order.empty()) sec.push_back({ip.order.data(), ip.order.size() * 4, 0});
         const size_t total = layout_sections(sec);
         DevBuf &dst = pk->direct ? mpk->tables : ctx->items;
         if ((rc = reserve(ctx, dst, total + 256))) return rc;
@@ -755,7 +965,7 @@ int sketch_from(lash_ctx *ctx, const lash_params *prm, const lash_packed *pk, ui
         uint8_t *tb = static_cast<uint8_t *>(dst.ptr);
         d_items = reinterpret_cast<const WorkItem *>(tb + sec[0].off);
         d_item_begin = reinterpret_cast<const uint32_t *>(tb + sec[1].off);
-        d_item_order = order.empty() ? nullptr : reinterpret_cast<const uint32_t *>(tb + sec[order_sec].off);
+        d_item_order = ip.order.empty() ? nullptr : reinterpret_cast<const uint32_t *>(tb + sec[order_sec].off);
         if (pk->direct) {
             mpk->d_descs = reinterpret_cast<GenomeDesc *>(tb + sec[2].off);
             mpk->d_tile_begin = reinterpret_cast<uint32_t *>(tb + sec[3].off);
@@ -780,176 +990,39 @@ int sketch_from(lash_ctx *ctx, const lash_params *prm, const lash_packed *pk, ui
     }
     TRACE("sketch: items uploaded");
 
-    SketchArgs sa{};
+    if ((rc = arm_hll_flags(ctx, prm, n_genomes, true))) return rc;
+    SketchArgs sa = sketch_args(ctx, prm, plan, d_items, d_out_images);
     sa.words = static_cast<const uint32_t *>(pk->words.ptr);
     sa.brk = static_cast<const uint32_t *>(pk->brk.ptr);
     sa.zero_words = reinterpret_cast<const uint32_t *>(static_cast<const uint8_t *>(ctx->counter.ptr) + 16);   // zeroed once, never written
     sa.genomes = pk->d_descs;
     sa.nvalid = pk->d_nvalid;
-    sa.items = d_items;
     sa.item_order = d_item_order;
-    sa.partials = static_cast<uint8_t *>(ctx->partials.ptr);
-    sa.gregs = static_cast<uint32_t *>(ctx->gregs.ptr);
-    sa.item_kmers = static_cast<uint32_t *>(ctx->item_kmers.ptr);
     sa.safe = static_cast<const uint8_t *>(ctx->counter.ptr) + 128;
-    sa.images = d_out_images;
-    sa.image_bytes = image_bytes;
-    {
-        const double alpha0 = hll_alpha(prm->p);
-        memcpy(&sa.alpha_bits, &alpha0, 8);
-    }
-    sa.accumulate = (prm->flags & LASH_F_ACCUMULATE) ? 1 : 0;
-    sa.bitflip = prm->algo == LASH_HMH ? xxh3_bitflip128(prm->seed) : xxh3_bitflip64(prm->seed);
-    sa.lay = layout_dev(ctx->layout, prm->algo);
-    sa.partial_stride = plan.partial_stride;
-    sa.nreg32 = plan.nreg32 >> plan.parts_log2;                 // register words of one pass
-    sa.k = prm->k;
-    sa.p = prm->p;
-    ctx->hll_flags_n = 0;
-    ctx->hll_flags_on_host = false;
-    if (prm->algo == LASH_HLL) {                                // which genomes end with a register above 53 - p (write_hll_header)
-        if ((rc = reserve(ctx, ctx->hll_flags, (size_t)n_genomes * 4))) return rc;
-        HIPCHK(ctx, hipMemsetAsync(ctx->hll_flags.ptr, 0, (size_t)n_genomes * 4, ctx->stream));
-        sa.hll_corner = static_cast<uint32_t *>(ctx->hll_flags.ptr);
-        ctx->hll_flags_n = n_genomes;
-    }
     if (pk->direct) {
-        sa.seq = pk->d_seq;
-        sa.brk_bytes = static_cast<const uint32_t *>(pk->brk_bytes.ptr);
-        sa.dirty = pk->d_dirty;
-        sa.rec_off = pk->d_rec_off;
-        sa.nonuniform = pk->d_dirty + 3 * (size_t)n_genomes + 1;
-        sa.nslow = pk->d_dirty + n_genomes + 1;
-        sa.ndel = sa.nslow + n_genomes;
-        sa.ndel2 = pk->d_dirty + 4 * (size_t)n_genomes + 2;
-        if (pk->stream_first)   // recent batches were full of finely fragmented dirt: every genome goes straight to the compacting kernel
-            HIPCHK(ctx, hipMemsetAsync(pk->d_dirty, 0x01, (size_t)n_genomes * 4, ctx->stream));
-        if (!plan.use_lds) {
-            if (ev) HIPCHK(ctx, hipEventRecord(ev->e[6], ctx->stream));
-            rc = global_run(ctx, plan, sa, n_items, [&](const SketchArgs &a, uint32_t cnt) -> int {
-                if (!pk->stream_first) HIPCHK(ctx, launch_sketch(plan_d, a, cnt, ctx->stream, true));
-                HIPCHK(ctx, launch_sketch_stream(plan, a, cnt, ctx->stream));
-                return LASH_OK;
-            });
-            if (rc) return rc;
-            if (ev) { HIPCHK(ctx, hipEventRecord(ev->e[5], ctx->stream)); ev->direct = true; }
-            if (!pk->stream_first) {
-                if ((rc = probe_dirty(ctx, const_cast<lash_packed *>(pk), ctx->stream))) return rc;
-                ctx->last.direct_launches += n_items ? 1 : 0;
-            }
-        } else if (plan.bins) {
-            if (ev) HIPCHK(ctx, hipEventRecord(ev->e[6], ctx->stream));
-            rc = bins_run(ctx, plan, prm, sa, bins_run_state, item_begin, n_items, d_item_begin, [&](const SketchArgs &a, uint32_t, uint32_t cnt) -> int {
-                if (!pk->stream_first) HIPCHK(ctx, launch_sketch(plan_d, a, cnt, ctx->stream, true));
-                HIPCHK(ctx, launch_sketch_stream(plan, a, cnt, ctx->stream));
-                return LASH_OK;
-            });
-            if (rc) return rc;
-            if (ev) { HIPCHK(ctx, hipEventRecord(ev->e[5], ctx->stream)); ev->direct = true; }
-            if (!pk->stream_first) {
-                if ((rc = probe_dirty(ctx, const_cast<lash_packed *>(pk), ctx->stream))) return rc;
-                ctx->last.direct_launches += n_items ? 1 : 0;
-            }
-        } else {
-            if (!pk->stream_first) {
-                // diagnostic, LASH_ITEM_TRACE=file (tools/item_trace.py): when and where every workgroup of this launch ran, appended as text
-                const char *trace_path = getenv("LASH_ITEM_TRACE");
-                unsigned long long *d_trace = nullptr;
-                if (trace_path && n_items) {
-                    HIPCHK(ctx, hipMalloc(&d_trace, (size_t)n_items * 32));
-                    HIPCHK(ctx, hipMemsetAsync(d_trace, 0, (size_t)n_items * 32, ctx->stream));
-                    sa.item_trace = d_trace;
-                }
-                if (ev) HIPCHK(ctx, hipEventRecord(ev->e[6], ctx->stream));       // direct_ms: this one launch
-                HIPCHK(ctx, launch_sketch(plan_d, sa, n_items, ctx->stream, true)); // ASCII in; sparse and coarse dirt handled in place
-                if (ev) { HIPCHK(ctx, hipEventRecord(ev->e[5], ctx->stream)); ev->direct = true; }
-                if (d_trace) {
-                    std::vector<unsigned long long> h((size_t)n_items * 4);
-                    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-                    HIPCHK(ctx, hipMemcpy(h.data(), d_trace, h.size() * 8, hipMemcpyDeviceToHost));
-                    (void)hipFree(d_trace);
-                    sa.item_trace = nullptr;
-                    if (FILE *f = fopen(trace_path, "a")) {
-                        fprintf(f, "# launch: %u items, %u threads, order %s; columns: slot item genome word_begin word_end start_10ns end_10ns hw_id xcc_id\n",
-                                n_items, plan_d.threads, order.empty() ? "item" : "longest first");
-                        for (uint32_t b = 0; b < n_items; ++b) {
-                            const uint32_t i = order.empty() ? b : order[b];
-                            fprintf(f, "%u %u %u %u %u %llu %llu %u %u\n", b, i, items[i].genome, items[i].word_begin, items[i].word_end, h[4ull * i], h[4ull * i + 1],
-                                    (unsigned)(h[4ull * i + 2] & 0xFFFFFFFFu), (unsigned)(h[4ull * i + 2] >> 32));
-                        }
-                        fclose(f);
-                    }
-                }
-                if ((rc = probe_dirty(ctx, const_cast<lash_packed *>(pk), ctx->stream))) return rc;
-                ctx->last.direct_launches += n_items ? 1 : 0;
-                ctx->last.defer_launches += (n_items && plan_d.defer) ? 1 : 0;
-            }
-            HIPCHK(ctx, launch_sketch_stream(plan_d, sa, n_items, ctx->stream));    // the flagged genomes, compacted on the fly
-        }
-    } else if (plan.bins) {
-        rc = bins_run(ctx, plan, prm, sa, bins_run_state, item_begin, n_items, d_item_begin, [&](const SketchArgs &a, uint32_t, uint32_t cnt) -> int {
-            HIPCHK(ctx, launch_sketch(plan_d, a, cnt, ctx->stream));
+        if ((rc = direct_launches(ctx, prm, plan, mpk, ip, sa, br, d_item_begin, ev))) return rc;
+    } else {
+        rc = launch_items(ctx, plan, prm, sa, br, ip.item_begin, d_item_begin, [&](const SketchArgs &a, uint32_t cnt) -> int {
+            HIPCHK(ctx, launch_sketch(plan, a, cnt, ctx->stream));
             return LASH_OK;
         });
         if (rc) return rc;
-    } else if (!plan.use_lds) {
-        rc = global_run(ctx, plan, sa, n_items, [&](const SketchArgs &a, uint32_t cnt) -> int { HIPCHK(ctx, launch_sketch(plan_d, a, cnt, ctx->stream)); return LASH_OK; });
-        if (rc) return rc;
-    } else {
-        HIPCHK(ctx, launch_sketch(plan_d, sa, n_items, ctx->stream));
-        ctx->last.defer_launches += (n_items && plan_d.defer) ? 1 : 0;
+        ctx->last.defer_launches += (n_items && plan.defer) ? 1 : 0;
     }
     // the small genomes, whole, on resident workgroups.  Their deleted-byte counts go where lash_ctx_get_timing() will look: with the learnt
     // stream_first every genome's flag is up (d_dirty = 0x01..) and the statistic subtracts ndel2, else ndel
-    if (n_sole && (rc = sole_launch(pk->direct ? (pk->stream_first ? sa.ndel2 : sa.ndel) : nullptr))) return rc;
+    if (n_sole && (rc = sole_batch(ctx, prm, sole_plan, sole_max, pk, d_out_images, pk->stream_first ? sa.ndel2 : sa.ndel))) return rc;
     if (ev) HIPCHK(ctx, hipEventRecord(ev->e[3], ctx->stream));
     TRACE("sketch: launched");
 
     FinalizeArgs fa{};
-    fa.partials = static_cast<const uint8_t *>(ctx->partials.ptr);
     fa.items = d_items;
     fa.genome_item_begin = d_item_begin;
     fa.nvalid = pk->d_nvalid;
-    fa.item_kmers = static_cast<const uint32_t *>(ctx->item_kmers.ptr);
-    if (plan.bins) {                                               // one partial per genome (bins_apply_kernel), its k-mer count behind the items'
-        fa.item_kmers += n_items;
-        fa.items = bins_run_state.d_vitems;
-        fa.genome_item_begin = bins_run_state.d_vbegin;
-        max_slices = 1;
-    }
-    fa.kmer_counter = static_cast<unsigned long long *>(ctx->counter.ptr);
-    fa.images = d_out_images;
-    fa.partial_stride = plan.partial_stride;
-    fa.partial_base_off = 0;
-    fa.image_bytes = image_bytes;
-    const double alpha = hll_alpha(prm->p);
-    memcpy(&fa.alpha_bits, &alpha, 8);
-    fa.algo = prm->algo;
-    fa.p = prm->p;
-    fa.k = prm->k;
-    fa.accumulate = (prm->flags & LASH_F_ACCUMULATE) ? 1 : 0;
-    fa.parts_log2 = plan.parts_log2;
-    fa.lay = sa.lay;
-    fa.src_images = 0;
-    fa.hll_corner = sa.hll_corner;
     fa.descs = n_sole ? pk->d_descs : nullptr;
     fa.skip_max_len = n_sole ? sole_max : 0;
-    // one finalize workgroup walks all of a genome's partials: fine for a handful of slices, 20 ms for the 4 096 slices of
-    // a metagenome-sized input (BASELINE configs[4]) -> fold groups of 32 slices first (until <= 16 heads remain)
-    fa.group = 0;
-    // (from 9 slices on: finalize_kernel's walk is serial — a dependent load per slice and word — and the tail quarters give a
-    // genome up to 16: 300 x 5 Mbp, finalize stage 0.27 -> 0.15 ms)
     // (the fold's grid spans every genome of the batch: with many thousands of genomes and ONE long one, wait for the 33rd slice as before)
-    if (max_slices > (n_genomes <= 4096u ? 8u : 32u) && n_genomes <= 65535u)
-        for (fa.group = 32u; (max_slices + fa.group - 1) / fa.group > 16u; fa.group *= 32u) {}
-    if (plan.bins && bins_write_images(prm)) {
-        // bins_apply_kernel wrote the images, headers and census itself
-    } else if (all_sole) {
-        HIPCHK(ctx, launch_census(fa, n_genomes, ctx->stream));            // every image was written by its one work item
-    } else {
-        HIPCHK(ctx, launch_reduce_groups(fa, n_genomes, max_slices, ctx->stream));
-        HIPCHK(ctx, launch_finalize(fa, n_genomes, ctx->stream));
-    }
+    if ((rc = finalize_run(ctx, prm, plan, br, ip, fa, n_genomes <= 4096u ? 8u : 32u, d_out_images))) return rc;
     if (ev) { HIPCHK(ctx, hipEventRecord(ev->e[4], ctx->stream)); ev->done = true; }
     TRACE("finalize: launched");
     ctx->last_packed.push_back(pk);
@@ -968,20 +1041,13 @@ int sketch_aa(lash_ctx *ctx, const lash_params *prm, const uint8_t *d_seq, const
     int rc;
     if (allow_bins && (rc = timing_begin(ctx))) return rc;            // (the second attempt keeps the first one's event set)
     EvSet *ev = ctx->cur_ev;
-    const bool x_low = rule_variant(ctx->layout, prm->algo, prm->flags);   // (HyperMinHash x = low half / HyperLogLog bucket = top bits)
-    SketchPlan plan = make_sketch_plan(prm->algo, prm->k, prm->p, x_low, false, allow_bins);
-    if (plan.bins) {                                                  // (as in sketch_from: one genome beyond the binned launch's budget)
-        const uint64_t budget = bins_budget_bytes(ctx);
-        uint64_t big = 0;
-        for (uint32_t g = 0; g < n_genomes; ++g)
-            big = std::max<uint64_t>(big, (genome_byte_off[g + 1] - genome_byte_off[g]) + 32 * (genome_rec_off[g + 1] - genome_rec_off[g]));
-        if (big * 6 + (uint64_t)plan.nreg32 * 4 + (64u << 20) > budget) plan = make_sketch_plan(prm->algo, prm->k, prm->p, x_low, false, false);
-    }
-    const uint64_t image_bytes = ::image_bytes(ctx->layout, prm->algo, prm->p);
+    uint64_t largest = 0;
+    for (uint32_t g = 0; g < n_genomes; ++g)
+        largest = std::max<uint64_t>(largest, (genome_byte_off[g + 1] - genome_byte_off[g]) + 32 * (genome_rec_off[g + 1] - genome_rec_off[g]));
+    const SketchPlan plan = choose_plan(ctx, prm, false, allow_bins, largest * 6);
     std::vector<GenomeDesc> descs(n_genomes, GenomeDesc{});
-    std::vector<WorkItem> items;
-    std::vector<uint32_t> item_begin(n_genomes + 1, 0);
-    uint32_t max_slices = 0;
+    ItemPlan ip;
+    ip.item_begin.assign(n_genomes + 1, 0);
     for (uint32_t g = 0; g < n_genomes; ++g) {
         if (genome_rec_off[g + 1] < genome_rec_off[g] || genome_rec_off[g + 1] > n_rec) return LASH_EINVAL;
         GenomeDesc &d = descs[g];
@@ -989,118 +1055,58 @@ int sketch_aa(lash_ctx *ctx, const lash_params *prm, const uint8_t *d_seq, const
         d.byte_len = genome_byte_off[g + 1] - genome_byte_off[g];
         d.rec_begin = genome_rec_off[g];
         d.rec_end = genome_rec_off[g + 1];
-        item_begin[g] = (uint32_t)items.size();
+        ip.item_begin[g] = (uint32_t)ip.items.size();
         const uint64_t nr = d.rec_end - d.rec_begin;
         if (nr > 0xFFFFFFFFull) return LASH_ELIMIT;
         uint32_t s = 0;
         for (uint64_t r0 = 0; r0 < nr; r0 += AA_RECORDS_PER_ITEM, ++s)
             for (uint32_t part = 0; part < (1u << plan.parts_log2); ++part)
-                items.push_back(WorkItem{g, (uint32_t)r0, (uint32_t)std::min<uint64_t>(nr, r0 + AA_RECORDS_PER_ITEM), (s & 0x7FFFu) | (part << 16)});
-        max_slices = std::max(max_slices, s);
+                ip.items.push_back(WorkItem{g, (uint32_t)r0, (uint32_t)std::min<uint64_t>(nr, r0 + AA_RECORDS_PER_ITEM), (s & 0x7FFFu) | (part << 16)});
+        ip.max_slices = std::max(ip.max_slices, s);
     }
-    item_begin[n_genomes] = (uint32_t)items.size();
-    const uint32_t n_items = (uint32_t)items.size();
-    const size_t n_virtual = plan.bins ? n_genomes : 0;
-    if ((rc = reserve(ctx, ctx->partials, bins_partials(plan, prm, n_items, n_genomes) * plan.partial_stride))) return rc;
-    if ((rc = reserve(ctx, ctx->item_kmers, (size_t)(n_items + n_virtual + 1) * 4))) return rc;
-    if ((rc = reserve(ctx, ctx->counter, 256))) return rc;
-    BinsRun bins_run_state;
+    ip.item_begin[n_genomes] = (uint32_t)ip.items.size();
+    const uint32_t n_items = (uint32_t)ip.items.size();
+    std::vector<uint64_t> entries;
     if (plan.bins) {
         // a lane pushes 16 entries per trip of its loop — 16 residues of a record, or the fetch of the next one — and the idle lanes of a
         // busy wave push along: residues + 32 per record, and a quarter on top
-        std::vector<uint64_t> entries(n_genomes);
+        entries.resize(n_genomes);
         for (uint32_t g = 0; g < n_genomes; ++g) {
             const uint64_t e = descs[g].byte_len + 32 * (descs[g].rec_end - descs[g].rec_begin);
             entries[g] = e + e / 4 + (uint64_t)plan.threads * 256;
         }
-        if ((rc = bins_prepare(ctx, plan, entries, n_genomes, bins_run_state))) return rc;
-        if (!bins_run_state.fits)                                    // (as in sketch_from: planned again without bins; nothing has been queued yet)
-            return sketch_aa(ctx, prm, d_seq, d_rec_off, n_rec, genome_rec_off, genome_byte_off, n_genomes, d_out_images, false);
     }
-    std::vector<Section> sec = {{items.data(), (size_t)n_items * sizeof(WorkItem), 0}, {item_begin.data(), (size_t)(n_genomes + 1) * 4, 0},
+    BinsRun br;
+    if ((rc = reserve_stage(ctx, prm, plan, ip, entries, br))) return rc;
+    if (!br.fits) return sketch_aa(ctx, prm, d_seq, d_rec_off, n_rec, genome_rec_off, genome_byte_off, n_genomes, d_out_images, false);
+    std::vector<Section> sec = {{ip.items.data(), (size_t)n_items * sizeof(WorkItem), 0}, {ip.item_begin.data(), (size_t)(n_genomes + 1) * 4, 0},
                                 {descs.data(), descs.size() * sizeof(GenomeDesc), 0}};
     const size_t total = layout_sections(sec);
     if ((rc = reserve(ctx, ctx->items, total + 256))) return rc;
     if ((rc = upload_sections(ctx, ctx->items.ptr, sec, total, ctx->stream))) return rc;
     uint8_t *tb = static_cast<uint8_t *>(ctx->items.ptr);
+    const uint32_t *d_item_begin = reinterpret_cast<const uint32_t *>(tb + sec[1].off);
     if (!ctx->counter_zeroed) {
         HIPCHK(ctx, hipMemsetAsync(ctx->counter.ptr, 0, 256, ctx->stream));
         ctx->counter_zeroed = true;
     }
     if (ev) HIPCHK(ctx, hipEventRecord(ev->e[2], ctx->stream));
-    SketchArgs sa{};
+    if ((rc = arm_hll_flags(ctx, prm, n_genomes, true))) return rc;
+    SketchArgs sa = sketch_args(ctx, prm, plan, reinterpret_cast<const WorkItem *>(tb + sec[0].off), d_out_images);
     sa.seq = d_seq;
     sa.rec_off = d_rec_off;
     sa.genomes = reinterpret_cast<const GenomeDesc *>(tb + sec[2].off);
-    sa.items = reinterpret_cast<const WorkItem *>(tb + sec[0].off);
-    sa.partials = static_cast<uint8_t *>(ctx->partials.ptr);
-    sa.gregs = static_cast<uint32_t *>(ctx->gregs.ptr);
-    sa.item_kmers = static_cast<uint32_t *>(ctx->item_kmers.ptr);
-    sa.images = d_out_images;
-    sa.image_bytes = image_bytes;
-    const double alpha = hll_alpha(prm->p);
-    memcpy(&sa.alpha_bits, &alpha, 8);
-    sa.accumulate = (prm->flags & LASH_F_ACCUMULATE) ? 1 : 0;
-    sa.bitflip = prm->algo == LASH_HMH ? xxh3_bitflip128(prm->seed) : xxh3_bitflip64(prm->seed);
-    sa.lay = layout_dev(ctx->layout, prm->algo);
-    sa.partial_stride = plan.partial_stride;
-    sa.nreg32 = plan.nreg32 >> plan.parts_log2;
-    sa.k = prm->k;
-    sa.p = prm->p;
-    ctx->hll_flags_n = 0;
-    ctx->hll_flags_on_host = false;
-    if (prm->algo == LASH_HLL) {
-        if ((rc = reserve(ctx, ctx->hll_flags, (size_t)n_genomes * 4))) return rc;
-        HIPCHK(ctx, hipMemsetAsync(ctx->hll_flags.ptr, 0, (size_t)n_genomes * 4, ctx->stream));
-        sa.hll_corner = static_cast<uint32_t *>(ctx->hll_flags.ptr);
-        ctx->hll_flags_n = n_genomes;
-    }
-    if (plan.bins) {
-        rc = bins_run(ctx, plan, prm, sa, bins_run_state, item_begin, n_items, reinterpret_cast<const uint32_t *>(tb + sec[1].off),
-                      [&](const SketchArgs &a, uint32_t, uint32_t cnt) -> int { HIPCHK(ctx, launch_sketch_aa(plan, a, cnt, ctx->stream)); return LASH_OK; });
-        if (rc) return rc;
-    } else if (!plan.use_lds) {
-        rc = global_run(ctx, plan, sa, n_items, [&](const SketchArgs &a, uint32_t cnt) -> int { HIPCHK(ctx, launch_sketch_aa(plan, a, cnt, ctx->stream)); return LASH_OK; });
-        if (rc) return rc;
-    } else {
-        HIPCHK(ctx, launch_sketch_aa(plan, sa, n_items, ctx->stream));
-    }
+    rc = launch_items(ctx, plan, prm, sa, br, ip.item_begin, d_item_begin, [&](const SketchArgs &a, uint32_t cnt) -> int {
+        HIPCHK(ctx, launch_sketch_aa(plan, a, cnt, ctx->stream));
+        return LASH_OK;
+    });
+    if (rc) return rc;
     if (ev) HIPCHK(ctx, hipEventRecord(ev->e[3], ctx->stream));
     FinalizeArgs fa{};
-    fa.partials = static_cast<const uint8_t *>(ctx->partials.ptr);
     fa.items = sa.items;
-    fa.genome_item_begin = reinterpret_cast<const uint32_t *>(tb + sec[1].off);
+    fa.genome_item_begin = d_item_begin;
     fa.nvalid = nullptr;                                           // every item is live
-    fa.item_kmers = static_cast<const uint32_t *>(ctx->item_kmers.ptr);
-    if (plan.bins) {
-        fa.item_kmers += n_items;
-        fa.items = bins_run_state.d_vitems;
-        fa.genome_item_begin = bins_run_state.d_vbegin;
-        max_slices = 1;
-    }
-    fa.kmer_counter = static_cast<unsigned long long *>(ctx->counter.ptr);
-    fa.images = d_out_images;
-    fa.partial_stride = plan.partial_stride;
-    fa.partial_base_off = 0;
-    fa.image_bytes = image_bytes;
-    memcpy(&fa.alpha_bits, &alpha, 8);
-    fa.algo = prm->algo;
-    fa.p = prm->p;
-    fa.k = prm->k;
-    fa.accumulate = sa.accumulate;
-    fa.parts_log2 = plan.parts_log2;
-    fa.lay = sa.lay;
-    fa.src_images = 0;
-    fa.hll_corner = sa.hll_corner;
-    fa.group = 0;
-    // (from 9 slices on: finalize_kernel's walk is serial — a dependent load per slice and word — and the tail quarters give a
-    // genome up to 16: 300 x 5 Mbp, finalize stage 0.27 -> 0.15 ms)
-    if (max_slices > 8u && n_genomes <= 65535u)
-        for (fa.group = 32u; (max_slices + fa.group - 1) / fa.group > 16u; fa.group *= 32u) {}
-    if (!(plan.bins && bins_write_images(prm))) {                      // (else bins_apply_kernel wrote the images, headers and census itself)
-        HIPCHK(ctx, launch_reduce_groups(fa, n_genomes, max_slices, ctx->stream));
-        HIPCHK(ctx, launch_finalize(fa, n_genomes, ctx->stream));
-    }
+    if ((rc = finalize_run(ctx, prm, plan, br, ip, fa, 8u, d_out_images))) return rc;
     if (ev) { HIPCHK(ctx, hipEventRecord(ev->e[4], ctx->stream)); ev->done = true; }
     ctx->cur_ev = nullptr;
     ctx->last.sketch_launches += n_items ? 1 : 0;
