@@ -392,6 +392,37 @@ int      lash_sketch_set_pair_block_within(lash_ctx *ctx, const lash_sketch_set 
                                            const lash_hll_bias *tables, double max_dist, uint32_t *out_row, uint32_t *out_col,
                                            double *out_dist, uint64_t cap, uint64_t *n_kept, uint64_t *bad_pair, uint64_t *n_candidates);
 
+/* pair_block_top: `lash dist --top K`.  A pair's rank key is (d, row, col): d its printed distance (lash_dist_rows' number, in f32
+ * under fp32, with the "same name -> 0" rule), then its position in the unfiltered output; NaN is never ranked.  N_K(X) = the K
+ * smallest keys among the pairs of name X: a column of a rectangular run; a row or a column of a triangle run.  The block runs as
+ * pair_block_within (statistics, expected collisions, then a selection on the device: dist_top.hip) and comes back as the exact
+ * (row, col, d) of a SUPERSET of the block's pairs that can be in some N_K given the bounds, in (row, col) order, NaN dropped, and
+ * with max_dist (NaN: none) only d <= max_dist.  top_k in [1, LASH_TOP_MAX].  same_col (may be NULL): per block row the column that
+ * carries the row's name (LASH_TOP_NO_COLUMN: none) — that pair's d is 0.  col_bound (per column) / row_bound (per block row,
+ * triangle only), may be NULL: the caller's current K-th key for that name (lash_top_bounds), or d = +inf.  cap / *n_kept /
+ * *bad_pair / *n_candidates (the pairs the device passed to the host) and LASH_ERANGE: as pair_block_within.
+ * lash_top: the host-side per-name lists that make N_K from those blocks (the command line and Python share it):
+ *   create   n_names: the columns (rectangular) or the set (triangle, rows and columns are the same names)
+ *   add      a block's result: each pair goes to its column's list and, in a triangle run, to its row's (the diagonal once)
+ *   bounds   col_bound [0, n_cols) and row_bound [r0, r1) for the next block (rectangular: row_bound gets +inf)
+ *   merge    another accumulator's lists (one per worker / device)
+ *   result   every kept pair, in (row, col) order, each once: the rows `--top` prints; *n the count (> cap: call again) */
+#define LASH_TOP_MAX 1024u
+#define LASH_TOP_NO_COLUMN 0xFFFFFFFFu
+typedef struct lash_top_key { double d; uint32_t row, col; } lash_top_key;
+int      lash_sketch_set_pair_block_top(lash_ctx *ctx, const lash_sketch_set *ref, uint32_t r0, uint32_t r1, const lash_sketch_set *qry,
+                                        uint32_t n_cols, int triangle, int k, int model, int fp32, int ull_estimator,
+                                        const lash_hll_bias *tables, uint32_t top_k, double max_dist, const uint32_t *same_col,
+                                        const lash_top_key *col_bound, const lash_top_key *row_bound, uint32_t *out_row, uint32_t *out_col,
+                                        double *out_dist, uint64_t cap, uint64_t *n_kept, uint64_t *bad_pair, uint64_t *n_candidates);
+typedef struct lash_top lash_top;
+int      lash_top_create(uint32_t n_names, uint32_t top_k, int triangle, lash_top **out);
+int      lash_top_add(lash_top *t, const uint32_t *row, const uint32_t *col, const double *dist, uint64_t n);
+int      lash_top_bounds(lash_top *t, uint32_t r0, uint32_t r1, uint32_t n_cols, lash_top_key *col_bound, lash_top_key *row_bound);
+int      lash_top_merge(lash_top *dst, const lash_top *src);
+int      lash_top_result(lash_top *t, uint32_t *out_row, uint32_t *out_col, double *out_dist, uint64_t cap, uint64_t *n);
+void     lash_top_free(lash_top *t);
+
 /* HyperMinHash sets: hyperminhash's expected_collisions(n, m) for the pairs of a block in which BOTH sketches hold at most 2^19
  * distinct k-mers (the regime in which the crate walks 65 536 cells per pair; lash_hmh_pair_expected_collisions below):
  * out_ec[(r - r0) * n_cols + c] for exactly those pairs — the other entries are left untouched, lash_dist_rows derives theirs in

@@ -106,6 +106,14 @@ PROTOTYPES = {
     "lash_sketch_set_pair_block_device": (_int, [_vp, _vp, _u32, _u32, _vp, _u32, _int, _int, _vp, _vp, _vp]),
     "lash_sketch_set_pair_block_within": (_int, [_vp, _vp, _u32, _u32, _vp, _u32, _int, _int, _int, _int, _int, _vp, C.c_double, _vp, _vp, _vp,
                                                   _u64, C.POINTER(_u64), C.POINTER(_u64), C.POINTER(_u64)]),
+    "lash_sketch_set_pair_block_top": (_int, [_vp, _vp, _u32, _u32, _vp, _u32, _int, _int, _int, _int, _int, _vp, _u32, C.c_double, _vp, _vp,
+                                               _vp, _vp, _vp, _vp, _u64, C.POINTER(_u64), C.POINTER(_u64), C.POINTER(_u64)]),
+    "lash_top_create": (_int, [_u32, _u32, _int, C.POINTER(_vp)]),
+    "lash_top_add": (_int, [_vp, _vp, _vp, _vp, _u64]),
+    "lash_top_bounds": (_int, [_vp, _u32, _u32, _u32, _vp, _vp]),
+    "lash_top_merge": (_int, [_vp, _vp]),
+    "lash_top_result": (_int, [_vp, _vp, _vp, _vp, _u64, C.POINTER(_u64)]),
+    "lash_top_free": (None, [_vp]),
     "lash_synth_genomes_device": (_int, [_vp, _u64, _u32, _u64, _vp]),
 }
 

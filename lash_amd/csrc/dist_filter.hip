@@ -26,72 +26,14 @@
 //   fp32: the same in float (ocml's logf / powf: <= 2 ulp; glibc's correctly rounded or 1 ulp): ulp(1.0f) = 2^-23 per ulp of
 //         d ~ 1, so a few ulp each side: < 2^-19.  margin 2^-16 (1.5e-5).
 // NaN distances (ull, two empty sketches, model 0) are candidates too; the host drops them (NaN never passes).
-#include "lash_ctx.h"
-#include "dist_pair.h"
+#include "dist_filter.h"
 
 namespace lash {
 
-constexpr uint32_t WF_TILE = 1024;                       // columns per tile: 256 lanes x 4 steps
-constexpr uint32_t WF_WORDS = WF_TILE / 64;              // mask words per tile
-
-// one candidate: block row, set column, the pair's statistics; ec_x: the small-pair cell sum of hmh, else NaN
-struct WithinPair {
-    uint32_t row, col, c_or_zero, n;
-    double sum_or_union, ec_x;
-};
-
-struct WithinArgs {
-    int algo, p, k, model, fp32;
-    double limit;                                        // D + margin
-    uint32_t nr, n_cols, tiles_x;
-    uint64_t n_tiles;
-    int64_t tri;                                         // r0 for a triangle block, else -1
-    const double *row_card, *col_card;                   // row_card: the block's first row
-    const uint32_t *c_or_zero, *n_counts;                // [nr][n_cols]
-    const double *sum_or_union;
-    const int32_t *row_small, *col_small;                // position in the set's small_idx, or -1 (row_small: the block's first row)
-    const double *X;                                     // EcBlock (nrs == 0: none)
-    uint32_t nrs, q_step, nqs, rbase;
-};
-
-__device__ __forceinline__ uint32_t row_end(const WithinArgs &a, uint32_t r)
-{
-    if (a.tri < 0) return a.n_cols;
-    const int64_t e = a.tri + (int64_t)r + 1;                                          // printed columns of row r
-    return e < (int64_t)a.n_cols ? (uint32_t)e : a.n_cols;
-}
-
 __device__ bool within_candidate(const WithinArgs &a, uint32_t r, uint32_t q)
 {
-    const uint64_t at = (uint64_t)r * a.n_cols + q;
-    const double rc = a.row_card[r], qc = a.col_card[q];
-    double sim;
-    if (a.algo == LASH_HLL) {
-        const uint32_t zero = a.c_or_zero[at];
-        double u;
-        const int regime = pairmath::hll_len_regime(a.p, zero, a.sum_or_union[at], &u);
-        if (regime == pairmath::HLL_BIAS) return true;                                 // host-only arithmetic (and maybe LASH_ERANGE)
-        if (zero > 0) {
-            const double m = (double)(1u << a.p), thr = pairmath::hll_threshold(a.p);
-            const double h = m * log(m / (double)zero);
-            if (fabs(h - thr) <= thr * 0x1p-40) return true;                            // the host's log may fall on the other side
-            if (regime == pairmath::HLL_LINEAR) u *= 1.0 - 0x1p-44;                    // no larger than the host's
-        }
-        sim = pairmath::union_similarity(rc, qc, u);
-    } else if (a.algo == LASH_ULL) {
-        sim = pairmath::union_similarity(rc, qc, a.sum_or_union[at]);
-    } else {
-        const double c = (double)a.c_or_zero[at], n = (double)a.n_counts[at];
-        double ec = 0.0;
-        if (c != 0.0 && !pairmath::hmh_ec_closed_form(qc, rc, &ec)) {
-            const int32_t rs = a.row_small[r], cs = a.col_small[q];
-            if (rs < 0 || cs < 0 || a.nrs == 0) return true;                            // (only NaN cardinalities get here)
-            const uint32_t ri = (uint32_t)rs - a.rbase, q0 = (uint32_t)cs / a.q_step * a.q_step, nq = min(a.q_step, a.nqs - q0);
-            ec = pairmath::hmh_ec_from_cell_sum(a.X[(uint64_t)a.nrs * q0 + (uint64_t)ri * nq + ((uint32_t)cs - q0)]);
-        }
-        sim = pairmath::hmh_similarity(c, n, ec);
-    }
-    const double d = pairmath::distance_from_similarity(sim, a.algo == LASH_ULL, a.k, a.model, a.fp32 != 0);
+    double sim, d;
+    if (!pair_distance_dev(a, r, q, &sim, &d)) return true;
     return !(d > a.limit);                                                              // (NaN: a candidate)
 }
 
@@ -190,6 +132,55 @@ uint32_t grid_for(uint64_t n_tiles) { return (uint32_t)std::min<uint64_t>(n_tile
 
 }  // namespace
 
+namespace lash {
+
+WithinArgs within_args(const lash_sketch_set *ref, uint32_t r0, uint32_t r1, const lash_sketch_set *qry, uint32_t n_cols, int triangle, int k,
+                       int model, int fp32, const uint32_t *d_c, const uint32_t *d_n, const double *d_u, const EcBlock &eb)
+{
+    const int algo = ref->algo;
+    const uint32_t nr = r1 - r0;
+    WithinArgs a{};
+    a.algo = algo; a.p = ref->p; a.k = k; a.model = model; a.fp32 = fp32 ? 1 : 0;
+    a.limit = 0.0;                                                                     // (the caller's)
+    a.nr = nr; a.n_cols = n_cols;
+    a.tiles_x = (n_cols + WF_TILE - 1) / WF_TILE;
+    a.n_tiles = (uint64_t)nr * a.tiles_x;
+    a.tri = triangle ? (int64_t)r0 : -1;
+    a.row_card = static_cast<const double *>(ref->d_card.ptr) + r0;
+    a.col_card = static_cast<const double *>(qry->d_card.ptr);
+    a.c_or_zero = algo == LASH_ULL ? nullptr : d_c;
+    a.n_counts = algo == LASH_HMH ? d_n : nullptr;
+    a.sum_or_union = algo == LASH_HMH ? nullptr : d_u;
+    a.row_small = static_cast<const int32_t *>(ref->d_small.ptr) + r0;
+    a.col_small = static_cast<const int32_t *>(qry->d_small.ptr);
+    a.X = eb.X; a.nrs = eb.nrs; a.q_step = eb.q_step; a.nqs = eb.nqs; a.rbase = eb.rbase;
+    if (eb.nqs == 0) a.nrs = 0;
+    return a;
+}
+
+int within_compact(lash_ctx *ctx, const WithinArgs &a, const uint64_t *d_mask, const uint32_t *d_cnt, uint64_t *d_off, std::vector<WithinPair> &cand)
+{
+    int rc;
+    const uint64_t nt = a.n_tiles;
+    hipLaunchKernelGGL(within_scan_kernel, dim3(1), dim3(1024), 0, ctx->stream, d_cnt, nt, d_off);
+    HIPCHK(ctx, hipGetLastError());
+    uint64_t n_cand = 0;
+    HIPCHK(ctx, hipMemcpyAsync(&n_cand, d_off + nt, 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    cand.resize(n_cand);
+    if (n_cand) {
+        if ((rc = reserve(ctx, ctx->wf_out, n_cand * sizeof(WithinPair)))) return rc;
+        WithinPair *d_out = static_cast<WithinPair *>(ctx->wf_out.ptr);
+        hipLaunchKernelGGL(within_write_kernel, dim3(grid_for(nt)), dim3(256), 0, ctx->stream, a, d_mask, d_cnt, d_off, d_out);
+        HIPCHK(ctx, hipGetLastError());
+        HIPCHK(ctx, hipMemcpyAsync(cand.data(), d_out, n_cand * sizeof(WithinPair), hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    return LASH_OK;
+}
+
+}  // namespace lash
+
 extern "C" {
 
 int lash_sketch_set_pair_block_within(lash_ctx *ctx, const lash_sketch_set *ref, uint32_t r0, uint32_t r1, const lash_sketch_set *qry,
@@ -217,22 +208,8 @@ int lash_sketch_set_pair_block_within(lash_ctx *ctx, const lash_sketch_set *ref,
     EcBlock eb;
     if (algo == LASH_HMH && (rc = lash_set_ec_block(ctx, ref, r0, r1, qry, n_cols, eb))) return rc;
 
-    WithinArgs a{};
-    a.algo = algo; a.p = ref->p; a.k = k; a.model = model; a.fp32 = fp32 ? 1 : 0;
+    WithinArgs a = within_args(ref, r0, r1, qry, n_cols, triangle, k, model, fp32, d_c, d_n, d_u, eb);
     a.limit = max_dist + (fp32 ? 0x1p-16 : 0x1p-40);                                 // the margin: see the top of this file
-    a.nr = nr; a.n_cols = n_cols;
-    a.tiles_x = (n_cols + WF_TILE - 1) / WF_TILE;
-    a.n_tiles = (uint64_t)nr * a.tiles_x;
-    a.tri = triangle ? (int64_t)r0 : -1;
-    a.row_card = static_cast<const double *>(ref->d_card.ptr) + r0;
-    a.col_card = static_cast<const double *>(qry->d_card.ptr);
-    a.c_or_zero = algo == LASH_ULL ? nullptr : d_c;
-    a.n_counts = algo == LASH_HMH ? d_n : nullptr;
-    a.sum_or_union = algo == LASH_HMH ? nullptr : d_u;
-    a.row_small = static_cast<const int32_t *>(ref->d_small.ptr) + r0;
-    a.col_small = static_cast<const int32_t *>(qry->d_small.ptr);
-    a.X = eb.X; a.nrs = eb.nrs; a.q_step = eb.q_step; a.nqs = eb.nqs; a.rbase = eb.rbase;
-    if (eb.nqs == 0) a.nrs = 0;
 
     // scratch: [offsets u64 (n_tiles + 1) | mask u64 (n_tiles * WF_WORDS) | counts u32 (n_tiles)]
     const uint64_t nt = a.n_tiles;
@@ -241,20 +218,9 @@ int lash_sketch_set_pair_block_within(lash_ctx *ctx, const lash_sketch_set *ref,
     uint32_t *d_cnt = reinterpret_cast<uint32_t *>(d_mask + nt * WF_WORDS);
     hipLaunchKernelGGL(within_mark_kernel, dim3(grid_for(nt)), dim3(256), 0, ctx->stream, a, d_mask, d_cnt);
     HIPCHK(ctx, hipGetLastError());
-    hipLaunchKernelGGL(within_scan_kernel, dim3(1), dim3(1024), 0, ctx->stream, d_cnt, nt, d_off);
-    HIPCHK(ctx, hipGetLastError());
-    uint64_t n_cand = 0;
-    HIPCHK(ctx, hipMemcpyAsync(&n_cand, d_off + nt, 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    std::vector<WithinPair> cand(n_cand);
-    if (n_cand) {
-        if ((rc = reserve(ctx, ctx->wf_out, n_cand * sizeof(WithinPair)))) return rc;
-        WithinPair *d_out = static_cast<WithinPair *>(ctx->wf_out.ptr);
-        hipLaunchKernelGGL(within_write_kernel, dim3(grid_for(nt)), dim3(256), 0, ctx->stream, a, d_mask, d_cnt, d_off, d_out);
-        HIPCHK(ctx, hipGetLastError());
-        HIPCHK(ctx, hipMemcpyAsync(cand.data(), d_out, n_cand * sizeof(WithinPair), hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    }
+    std::vector<WithinPair> cand;
+    if ((rc = within_compact(ctx, a, d_mask, d_cnt, d_off, cand))) return rc;
+    const uint64_t n_cand = cand.size();
     if (n_candidates) *n_candidates = n_cand;
 
     // exact: the host arithmetic of lash_dist_rows, pair by pair, in row-major order (so the first refused pair is the one it reports)

@@ -19,6 +19,9 @@
 // Several GPUs (--devices 0,1,..): blocks of reference rows are handed to one worker per device and written in order.
 // --max-dist D (not upstream): a block's pairs are filtered on the device (lash_sketch_set_pair_block_within) and only the rows with
 // d <= D are formatted — the same rows in the same order as without the option, minus the others.
+// --top K (not upstream): a block's pairs go through a selection on the device (lash_sketch_set_pair_block_top) and the survivors into
+// per-name lists on the host (lash_top_*, one per worker, merged at the end); N_K of a name is complete only after the last block, so the
+// kept rows are written once, at the end, in (row, col) order — the same rows in the same order as without the option, minus the others.
 #include "dist.hpp"
 
 #include <dirent.h>
@@ -159,9 +162,9 @@ std::string run_dist(const DistOptions &opt)
     std::vector<uint32_t> row_id, col_id;
     name_ids(row_name, col_name, row_id, col_id);
     const std::vector<std::string> col_tab = opt.matrix ? std::vector<std::string>() : tabbed_names(col_name);
-    // --max-dist: the column carrying each row's name (a name is one entry per side, so at most one), found once — those pairs print 0
+    // --max-dist / --top: the column carrying each row's name (a name is one entry per side, so at most one), found once — those pairs print 0
     std::vector<uint32_t> same_col;
-    if (opt.has_max_dist) {
+    if (opt.has_max_dist || opt.top) {
         std::vector<uint32_t> col_of(row_name.size() + col_name.size(), NO_COLUMN);
         for (uint32_t j = 0; j < nq; ++j) col_of[col_id[j]] = j;
         same_col.resize(nr);
@@ -259,8 +262,16 @@ std::string run_dist(const DistOptions &opt)
     std::condition_variable wcv;
     uint32_t next_to_write = 0;
     std::string fail;                                            // guarded by wmu
+    // --top: per worker, the lists of the K nearest of every name (the columns; in a triangle run the set) from the blocks it ran
+    std::vector<lash_top *> tops(devices.size(), nullptr);
+    std::atomic<uint64_t> top_candidates{0};                     // (LASH_CLI_TIMING: what the device passed to the host)
+    struct TopsGuard { std::vector<lash_top *> &t; ~TopsGuard() { for (lash_top *p : t) lash_top_free(p); } } tops_guard{tops};
+    if (opt.top)
+        for (lash_top *&t : tops)
+            if (lash_top_create(same_files ? nr : nq, opt.top, same_files ? 1 : 0, &t) != LASH_OK) return "cannot create the --top lists";
 
-    auto worker = [&](int device) {
+    auto worker = [&](size_t wi) {
+        const int device = devices[wi];
         const DevSets *ds = nullptr;
         for (const DevSets &d : dev_sets) if (d.device == device) ds = &d;
         lash_ctx *ctx = nullptr;
@@ -274,6 +285,7 @@ std::string run_dist(const DistOptions &opt)
         RowText row_text;                                        // the block's text; its memory is reused from block to block
         std::vector<uint32_t> w_row, w_col;                      // --max-dist: the block's survivors
         std::vector<double> w_dist;
+        std::vector<lash_top_key> col_bound, row_bound;          // --top: this worker's K-th key per name, for the next block
         auto grow = [&](size_t np) {
             if (np <= cap) return true;
             lash_host_free_pinned(C); lash_host_free_pinned(N); lash_host_free_pinned(U);
@@ -293,7 +305,26 @@ std::string run_dist(const DistOptions &opt)
             { std::lock_guard<std::mutex> lk(wmu); skip = !fail.empty(); }
             bool have_ec = false;
             row_text.off.clear(); row_text.len.clear();
-            if (my_fail.empty() && !skip && opt.has_max_dist) {
+            if (my_fail.empty() && !skip && opt.top) {
+                // pair statistics, expected collisions and the selection on the device; the survivors go to this worker's lists
+                uint64_t kept = 0, bad = 0, cand = 0;
+                if (w_row.empty()) { w_row.resize(1u << 16); w_col.resize(1u << 16); w_dist.resize(1u << 16); }
+                col_bound.resize(n_cols);
+                row_bound.resize(i1 - i0);
+                lash_top_bounds(tops[wi], i0, i1, n_cols, col_bound.data(), same_files ? row_bound.data() : nullptr);
+                for (;;) {
+                    rc = lash_sketch_set_pair_block_top(ctx, ds->ref, i0, i1, ds->qry, n_cols, same_files ? 1 : 0, k, opt.model, opt.fp32 ? 1 : 0, ull_est,
+                                                        bias, opt.top, opt.has_max_dist ? opt.max_dist : NAN, same_col.data() + i0, col_bound.data(),
+                                                        same_files ? row_bound.data() : nullptr, w_row.data(), w_col.data(), w_dist.data(), w_row.size(),
+                                                        &kept, &bad, &cand);
+                    if (rc != LASH_OK || kept <= w_row.size()) break;
+                    w_row.resize(kept + kept / 4); w_col.resize(w_row.size()); w_dist.resize(w_row.size());
+                }
+                top_candidates += cand;
+                if (rc == LASH_OK) rc = lash_top_add(tops[wi], w_row.data(), w_col.data(), w_dist.data(), kept);
+                if (rc == LASH_ERANGE) my_fail = "union of " + row_name[i0 + bad / n_cols] + " and " + col_name[bad % n_cols] + bias_msg;
+                else if (rc != LASH_OK) my_fail = std::string(lash_strerror(rc)) + " " + lash_ctx_last_error(ctx);
+            } else if (my_fail.empty() && !skip && opt.has_max_dist) {
                 // pair statistics, expected collisions and the cutoff on the device; only the survivors come back
                 uint64_t kept = 0, bad = 0;
                 if (w_row.empty()) { w_row.resize(1u << 16); w_col.resize(1u << 16); w_dist.resize(1u << 16); }
@@ -324,7 +355,7 @@ std::string run_dist(const DistOptions &opt)
                     if (rc != LASH_OK) my_fail = std::string(lash_strerror(rc)) + " " + lash_ctx_last_error(ctx);
                 }
             }
-            if (my_fail.empty() && !skip && !opt.has_max_dist) {
+            if (my_fail.empty() && !skip && !opt.has_max_dist && !opt.top) {
                 BlockTables bt;
                 bt.c_or_zero = C; bt.n_counts = N; bt.sum_or_union = U; bt.hmh_ec = have_ec ? EC : nullptr; bt.ld = n_cols;
                 my_fail = dist_block_rows(algo_id, prec, k, opt.model, opt.fp32, bias, i0, i1, same_files, nq, rcard.data(), qcard.data(), bt, row_name,
@@ -346,9 +377,31 @@ std::string run_dist(const DistOptions &opt)
     };
     {
         std::vector<std::thread> pool;
-        for (size_t d = 1; d < devices.size(); ++d) pool.emplace_back(worker, devices[d]);
-        worker(devices[0]);
+        for (size_t d = 1; d < devices.size(); ++d) pool.emplace_back(worker, d);
+        worker(0);
         for (auto &t : pool) t.join();
+    }
+    if (opt.top && fail.empty()) {
+        // --top: the workers' lists merged, the kept pairs in (row, col) order through the --max-dist formatter (every pair passes;
+        // same-name pairs are in the lists with d = 0 when they are among the K nearest)
+        for (size_t w = 1; w < tops.size() && fail.empty(); ++w)
+            if (lash_top_merge(tops[0], tops[w]) != LASH_OK) fail = "cannot merge the --top lists";
+        uint64_t n = 0;
+        std::vector<uint32_t> t_row, t_col;
+        std::vector<double> t_dist;
+        if (fail.empty() && lash_top_result(tops[0], nullptr, nullptr, nullptr, 0, &n) == LASH_OK) {
+            t_row.resize(n); t_col.resize(n); t_dist.resize(n);
+            if (lash_top_result(tops[0], t_row.data(), t_col.data(), t_dist.data(), n, &n) != LASH_OK) fail = "cannot read the --top lists";
+        }
+        if (fail.empty()) {
+            RowText text;
+            const std::vector<uint32_t> no_same(nr, NO_COLUMN);
+            format_block_within(0, nr, same_files, nq, HUGE_VAL, t_row.data(), t_col.data(), t_dist.data(), n, no_same.data(), row_name, col_tab, text);
+            for (size_t r = 0; r < text.rows(); ++r) fwrite(text.data(r), 1, text.size(r), out);
+            if (timing) fprintf(stderr, "[lash dist] --top: %llu candidates from the device, %llu rows kept\n",
+                                (unsigned long long)top_candidates.load(), (unsigned long long)n);
+            mark("--top: the kept rows written");
+        }
     }
     fclose(out);
     mark("all rows written");

@@ -19,6 +19,7 @@ struct DistOptions {
     uint32_t block_rows = 0;   // reference rows per GPU call; 0 = as many as keep the pair tables under ~0.5 GB
     bool has_max_dist = false; // --max-dist D: print only the rows whose distance d passes d <= D (list form only)
     double max_dist = 0.0;
+    uint32_t top = 0;          // --top K (1..LASH_TOP_MAX): print only the rows in some name's K nearest (list form only); 0 = off
     std::string hll_bias_file; // --hll-bias / $LASH_HLL_BIAS: HLL++ bias tables (lash_hll_bias_load); empty = that regime is refused
     lash_layout layout;        // --layout / $LASH_LAYOUT (include/lash_gfx950.h)
     DistOptions() { lash_layout_default(&layout); }

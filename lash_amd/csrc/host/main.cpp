@@ -5,7 +5,7 @@
 // Extras that do not exist upstream: --gpus N / --device D / --devices LIST (which GPUs to use, one worker each), --batch-mb M, --stream-mb M (files
 // larger than M MiB are streamed in chunks with on-device accumulation), --hmh-x-low; dist: --device D, --block-rows N,
 // --file-order (rows / columns in list-file order instead of the reference's seeded hash-map order), --max-dist D (print only
-// the pairs with distance <= D) (reference rows per GPU call); both: --layout SPEC (or $LASH_LAYOUT): the crate-internal rules as data, see `lash_layout`
+// the pairs with distance <= D), --top K (only each name's K nearest) (reference rows per GPU call); both: --layout SPEC (or $LASH_LAYOUT): the crate-internal rules as data, see `lash_layout`
 // in include/lash_gfx950.h.
 #include <chrono>
 #include <cmath>
@@ -54,6 +54,8 @@ void usage()
             "  -t, --threads <n>  -e, --estimator <fgra|ml>  -m, --model <1|0>  --fp32  --dm\n"
             "      --file-order   rows and columns in list-file order (default: the reference's hash-map key order)\n"
             "      --max-dist <D> print only the pairs whose distance is <= D (same rows, same order; not with --dm)\n"
+            "      --top <K>      print only each query's K nearest (triangle runs: a pair in either name's K nearest; the\n"
+            "                     name itself counts, so use K+1 for K others), K 1-1024; same rows, same order; not with --dm\n"
             "      --hll-bias <file>  HLL++ bias tables (tools/ref_probe/extract_hll_bias.py) [default: $LASH_HLL_BIAS];\n"
             "                     without them hll estimates <= 5 * 2^p are refused\n");
 }
@@ -209,6 +211,16 @@ int cmd_dist(int argc, char **argv)
         if (opt.matrix) { fprintf(stderr, "error: --max-dist cannot be used with --dm (a square matrix cannot drop cells)\n"); return 2; }
         opt.has_max_dist = true;
         opt.max_dist = d;
+    }
+    if (a.kv.count("top")) {
+        const std::string &v = a.kv["top"];
+        uint64_t n = 0;
+        if (!to_u64(v, n) || n < 1 || n > LASH_TOP_MAX) {
+            fprintf(stderr, "error: invalid value '%s' for --top: an integer from 1 to %u is required\n", v.c_str(), LASH_TOP_MAX);
+            return 2;
+        }
+        if (opt.matrix) { fprintf(stderr, "error: --top cannot be used with --dm (a square matrix cannot drop cells)\n"); return 2; }
+        opt.top = (uint32_t)n;
     }
     err = layout_from_option(a.kv.count("layout") ? a.kv["layout"] : "", opt.layout);
     if (!err.empty()) { fprintf(stderr, "error: %s\n", err.c_str()); return 2; }

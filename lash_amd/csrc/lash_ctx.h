@@ -171,6 +171,7 @@ struct lash_ctx {
     DevBuf ec_ref, ec_qry, ec_x, ec_card;   // lash_hmh_pair_expected_collisions: cell vectors [n][65536] f64, products, cardinalities
     std::vector<double> ec_qry_cards;    // the small query cardinalities whose vectors ec_qry holds (reused across row blocks)
     DevBuf wf_scratch, wf_out;           // lash_sketch_set_pair_block_within: [offsets | masks | tile counts], the compacted candidates
+    DevBuf top_buf;                      // lash_sketch_set_pair_block_top: [cutoff keys | interval keys | same_col] (dist_top.hip)
     DevBuf hll_flags;                    // [hll_flags_n] per genome of the last HyperLogLog sketch call: a register > 53 - p
     uint32_t hll_flags_n = 0;            // (lash_ctx_hll_inexact_sums)
     bool hll_flags_on_host = false;      // the list below stands for the flags (hll_replay_sums has dealt with the others)

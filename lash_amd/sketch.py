@@ -536,6 +536,66 @@ class SketchSet:
         n = min(kept.value, size)
         return row[:n], col[:n], dist[:n]
 
+    def pair_block_top(self, r0, r1, top, k, qry=None, n_cols=None, triangle=False, max_dist=None, same_col=None, col_bound=None,
+                       row_bound=None, model=1, fp32=False, estimator="fgra", hll_bias=None, cap=None, stats=None):
+        """`lash dist --top`: the pairs of rows [r0, r1) x columns [0, n_cols) that can still be among some name's `top` nearest, as numpy
+        arrays (row, col, dist) in (row, col) order, each evaluated exactly on the host (lash_sketch_set_pair_block_top): a superset of
+        the block's part of every name's N_K given the bounds.  same_col: per block row the column with the row's name (its pair is 0),
+        0xFFFFFFFF for none; col_bound / row_bound: TOP_KEY arrays (TopK.bounds), or None.  max_dist: also d <= max_dist.  cap / stats /
+        LashError.pair as pair_block_within."""
+        q = qry or self
+        nc = q.n if n_cols is None else int(n_cols)
+        sc = None if same_col is None else np.ascontiguousarray(same_col, dtype=np.uint32)
+        cb = None if col_bound is None else np.ascontiguousarray(col_bound, dtype=TOP_KEY)
+        rb = None if row_bound is None else np.ascontiguousarray(row_bound, dtype=TOP_KEY)
+        assert sc is None or len(sc) >= int(r1) - int(r0)
+        assert cb is None or len(cb) >= nc
+        assert rb is None or len(rb) >= int(r1) - int(r0)
+        size = (1 << 12) if cap is None else int(cap)
+        while True:
+            row, col = np.empty(size, np.uint32), np.empty(size, np.uint32)
+            dist = np.empty(size, np.float64)
+            kept, bad, cand = C.c_uint64(), C.c_uint64(), C.c_uint64()
+            rc = self._lib.lash_sketch_set_pair_block_top(self._ctx._h, self._h, int(r0), int(r1), q._h, nc, 1 if triangle else 0, int(k), int(model),
+                                                          1 if fp32 else 0, ULL_ESTIMATORS[estimator], _bias_handle(hll_bias), int(top),
+                                                          float("nan") if max_dist is None else float(max_dist),
+                                                          None if sc is None else sc.ctypes.data, None if cb is None else cb.ctypes.data,
+                                                          None if rb is None else rb.ctypes.data, row.ctypes.data, col.ctypes.data,
+                                                          dist.ctypes.data, size, C.byref(kept), C.byref(bad), C.byref(cand))
+            if rc == _lib.ERANGE:
+                e = LashError(rc, self._lib.lash_strerror(rc).decode() + " (pair %d)" % bad.value)
+                e.pair = bad.value                                   # (row - r0) * n_cols + col
+                raise e
+            self._ctx._check(rc)
+            if cap is not None or kept.value <= size:
+                break
+            size = kept.value
+        if stats is not None:
+            stats.update(n_kept=kept.value, n_candidates=cand.value)
+        n = min(kept.value, size)
+        return row[:n], col[:n], dist[:n]
+
+    def top_pairs(self, top, k, qry=None, triangle=None, max_dist=None, same_col=None, block_rows=None, **kw):
+        """`lash dist --top` over the whole set: walks row blocks of `block_rows` (default: all rows in one block) through
+        pair_block_top and a TopK, and returns the kept pairs (row, col, dist) in (row, col) order.  triangle (default: qry is None or
+        this set) prints the lower triangle, rows and columns being the same names; same_col: per row, as pair_block_top.  The other
+        keywords go to pair_block_top."""
+        q = qry or self
+        tri = (q is self) if triangle is None else bool(triangle)
+        acc = TopK(self.n if tri else q.n, top, tri, self._lib)
+        step = self.n if not block_rows else int(block_rows)
+        for r0 in range(0, self.n, max(step, 1)):
+            r1 = min(self.n, r0 + step)
+            nc = min(r1, q.n) if tri else q.n
+            cb, rb = acc.bounds(r0, r1, nc)
+            sc = None if same_col is None else np.asarray(same_col, np.uint32)[r0:r1]
+            row, col, dist = self.pair_block_top(r0, r1, top, k, qry=q, n_cols=nc, triangle=tri, max_dist=max_dist, same_col=sc, col_bound=cb,
+                                                 row_bound=rb if tri else None, **kw)
+            acc.add(row, col, dist)
+        out = acc.result()
+        acc.free()
+        return out
+
     def pair_block(self, r0, r1, qry=None, n_cols=None, triangle=False, estimator="fgra", out=None):
         """statistics of rows [r0, r1) against columns [0, n_cols) of `qry` (default: this set) as the dict lash_dist_rows takes.
         `out`: optional dict of preallocated (e.g. pinned) flat arrays 'c', 'n' (uint32), 'u' (float64) of >= (r1-r0)*n_cols."""
@@ -562,3 +622,63 @@ class SketchSet:
         if u is not None:
             st["sum_or_union"] = u
         return st
+
+
+# lash_top_key: a name's K-th (d, row, col) rank key, d = +inf for none
+TOP_KEY = np.dtype([("d", np.float64), ("row", np.uint32), ("col", np.uint32)])
+
+
+class TopK:
+    """lash_top: per name the `top` smallest (d, row, col) keys of the pairs added so far — the host half of `lash dist --top`, shared
+    with the command line.  n_names: the columns (rectangular) or the set (triangle: a pair counts for its row and its column)."""
+
+    def __init__(self, n_names, top, triangle=False, lib=None):
+        self._lib = lib or _lib.load()
+        self.n_names, self.top, self.triangle = int(n_names), int(top), bool(triangle)
+        h = C.c_void_p()
+        rc = self._lib.lash_top_create(self.n_names, self.top, 1 if triangle else 0, C.byref(h))
+        if rc != _lib.OK:
+            raise LashError(rc, self._lib.lash_strerror(rc).decode())
+        self._h = h
+
+    def _check(self, rc):
+        if rc != _lib.OK:
+            raise LashError(rc, self._lib.lash_strerror(rc).decode())
+
+    def add(self, row, col, dist):
+        row = np.ascontiguousarray(row, np.uint32)
+        col = np.ascontiguousarray(col, np.uint32)
+        dist = np.ascontiguousarray(dist, np.float64)
+        assert len(row) == len(col) == len(dist)
+        self._check(self._lib.lash_top_add(self._h, row.ctypes.data, col.ctypes.data, dist.ctypes.data, len(row)))
+
+    def bounds(self, r0, r1, n_cols):
+        """(col_bound [n_cols], row_bound [r1 - r0]) TOP_KEY arrays for pair_block_top"""
+        cb = np.zeros(int(n_cols), TOP_KEY)
+        rb = np.zeros(int(r1) - int(r0), TOP_KEY)
+        self._check(self._lib.lash_top_bounds(self._h, int(r0), int(r1), int(n_cols), cb.ctypes.data, rb.ctypes.data))
+        return cb, rb
+
+    def merge(self, other):
+        self._check(self._lib.lash_top_merge(self._h, other._h))
+
+    def result(self):
+        """the kept pairs (row, col, dist) in (row, col) order"""
+        n = C.c_uint64()
+        self._check(self._lib.lash_top_result(self._h, None, None, None, 0, C.byref(n)))
+        row, col = np.empty(n.value, np.uint32), np.empty(n.value, np.uint32)
+        dist = np.empty(n.value, np.float64)
+        if n.value:
+            self._check(self._lib.lash_top_result(self._h, row.ctypes.data, col.ctypes.data, dist.ctypes.data, n.value, C.byref(n)))
+        return row, col, dist
+
+    def free(self):
+        if getattr(self, "_h", None):
+            self._lib.lash_top_free(self._h)
+        self._h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
