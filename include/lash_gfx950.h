@@ -423,6 +423,34 @@ int      lash_top_merge(lash_top *dst, const lash_top *src);
 int      lash_top_result(lash_top *t, uint32_t *out_row, uint32_t *out_col, double *out_dist, uint64_t cap, uint64_t *n);
 void     lash_top_free(lash_top *t);
 
+/* pair_block_cluster: `lash dist --cluster D`, single-linkage clusters of a triangle run (rows and columns are the same names in the
+ * same order).  Two names are LINKED iff pair_block_within with the same arguments returns their pair: the exact d passes
+ * d <= max_dist, NaN never; the diagonal plays no part.  Clusters are the connected components of the links.  The block runs as
+ * pair_block_within with triangle = 1 (statistics, expected collisions), then a mark-and-join kernel (dist_cluster.hip): a pair whose
+ * names are already in one cluster is pruned without arithmetic, a pair that is surely linked joins the two clusters in a label array
+ * in device memory (a union-find, compare-and-swap on roots), a pair that is surely not linked is dropped, and only the pairs the
+ * device cannot decide (within the margin of max_dist, or host-only arithmetic) come back; each of those is evaluated here exactly
+ * and, when linked, joined in the same label array.  Blocks may run in any order and be spread over several accumulators (one per worker, each
+ * with the context of its device); the labels do not depend on it.  LASH_ERANGE and *bad_pair as pair_block_within (pairs the device
+ * cannot place are never pruned).  max_dist NaN, r1 or n_cols beyond the accumulator's n, an accumulator of another device: LASH_EINVAL.
+ * lash_cluster:
+ *   create   n names, each a cluster of its own; the label array lives on ctx's device
+ *   merge    folds another accumulator's clusters into dst (src's labels go through the host and are joined on dst's device, on
+ *            its default stream); src is unchanged
+ *   labels   out[i] = the smallest index of the cluster of i, for all n
+ * stats (may be NULL), per call: pairs = the block's printed off-diagonal pairs; pruned = already in one cluster, no distance
+ * computed; joined_on_device = successful joins (at most n - 1 over an accumulator's life); sent_to_host = the pairs that came
+ * back; clusters = the accumulator's number of clusters after the block. */
+typedef struct lash_cluster lash_cluster;
+typedef struct lash_cluster_stats { uint64_t pairs, pruned, joined_on_device, sent_to_host, clusters; } lash_cluster_stats;
+int      lash_cluster_create(lash_ctx *ctx, uint32_t n, lash_cluster **out);
+void     lash_cluster_free(lash_cluster *c);
+int      lash_sketch_set_pair_block_cluster(lash_ctx *ctx, const lash_sketch_set *ref, uint32_t r0, uint32_t r1, const lash_sketch_set *qry,
+                                            uint32_t n_cols, int k, int model, int fp32, int ull_estimator, const lash_hll_bias *tables,
+                                            double max_dist, lash_cluster *cluster, lash_cluster_stats *stats, uint64_t *bad_pair);
+int      lash_cluster_merge(lash_cluster *dst, const lash_cluster *src);
+int      lash_cluster_labels(const lash_cluster *c, uint32_t *out);
+
 /* HyperMinHash sets: hyperminhash's expected_collisions(n, m) for the pairs of a block in which BOTH sketches hold at most 2^19
  * distinct k-mers (the regime in which the crate walks 65 536 cells per pair; lash_hmh_pair_expected_collisions below):
  * out_ec[(r - r0) * n_cols + c] for exactly those pairs — the other entries are left untouched, lash_dist_rows derives theirs in

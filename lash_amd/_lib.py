@@ -35,6 +35,12 @@ class Timing(C.Structure):
                 ("direct_ms", C.c_float), ("defer_launches", C.c_uint32), ("sole_launches", C.c_uint32)]
 
 
+class ClusterStats(C.Structure):
+    """lash_cluster_stats: what one pair_block_cluster call did"""
+    _fields_ = [("pairs", C.c_uint64), ("pruned", C.c_uint64), ("joined_on_device", C.c_uint64), ("sent_to_host", C.c_uint64),
+                ("clusters", C.c_uint64)]
+
+
 _vp, _u64, _u32, _int = C.c_void_p, C.c_uint64, C.c_uint32, C.c_int
 _PP = C.POINTER(Params)
 _LP = C.POINTER(Layout)
@@ -114,6 +120,12 @@ PROTOTYPES = {
     "lash_top_merge": (_int, [_vp, _vp]),
     "lash_top_result": (_int, [_vp, _vp, _vp, _vp, _u64, C.POINTER(_u64)]),
     "lash_top_free": (None, [_vp]),
+    "lash_cluster_create": (_int, [_vp, _u32, C.POINTER(_vp)]),
+    "lash_cluster_free": (None, [_vp]),
+    "lash_sketch_set_pair_block_cluster": (_int, [_vp, _vp, _u32, _u32, _vp, _u32, _int, _int, _int, _int, _vp, C.c_double, _vp,
+                                                   C.POINTER(ClusterStats), C.POINTER(_u64)]),
+    "lash_cluster_merge": (_int, [_vp, _vp]),
+    "lash_cluster_labels": (_int, [_vp, _vp]),
     "lash_synth_genomes_device": (_int, [_vp, _u64, _u32, _u64, _vp]),
 }
 

@@ -158,6 +158,26 @@ WithinArgs within_args(const lash_sketch_set *ref, uint32_t r0, uint32_t r1, con
     return a;
 }
 
+int within_block(lash_ctx *ctx, const lash_sketch_set *ref, uint32_t r0, uint32_t r1, const lash_sketch_set *qry, uint32_t n_cols, int triangle, int k,
+                 int model, int fp32, int ull_estimator, WithinBlock &b)
+{
+    int rc;
+    const uint64_t np = (uint64_t)(r1 - r0) * n_cols;
+    if ((rc = reserve(ctx, ctx->st_img, np * 16 + 64))) return rc;
+    double *d_u = static_cast<double *>(ctx->st_img.ptr);
+    uint32_t *d_c = reinterpret_cast<uint32_t *>(d_u + np), *d_n = d_c + np;
+    if ((rc = lash_sketch_set_pair_block_device(ctx, ref, r0, r1, qry, n_cols, triangle, ull_estimator, d_c, d_n, d_u))) return rc;
+    EcBlock eb;
+    if (ref->algo == LASH_HMH && (rc = lash_set_ec_block(ctx, ref, r0, r1, qry, n_cols, eb))) return rc;
+    b.a = within_args(ref, r0, r1, qry, n_cols, triangle, k, model, fp32, d_c, d_n, d_u, eb);
+    const uint64_t nt = b.a.n_tiles;
+    if ((rc = reserve(ctx, ctx->wf_scratch, (nt + 1) * 8 + nt * WF_WORDS * 8 + nt * 4 + 64))) return rc;
+    b.d_off = static_cast<uint64_t *>(ctx->wf_scratch.ptr);
+    b.d_mask = b.d_off + nt + 1;
+    b.d_cnt = reinterpret_cast<uint32_t *>(b.d_mask + nt * WF_WORDS);
+    return LASH_OK;
+}
+
 int within_compact(lash_ctx *ctx, const WithinArgs &a, const uint64_t *d_mask, const uint32_t *d_cnt, uint64_t *d_off, std::vector<WithinPair> &cand)
 {
     int rc;
@@ -199,23 +219,13 @@ int lash_sketch_set_pair_block_within(lash_ctx *ctx, const lash_sketch_set *ref,
     (void)hipSetDevice(ctx->device);
     int rc;
     const int algo = ref->algo;
-    const uint64_t np = (uint64_t)nr * n_cols;
-    // the block's statistics: [sum_or_union f64 | c_or_zero u32 | n u32], as lash_sketch_set_pair_block
-    if ((rc = reserve(ctx, ctx->st_img, np * 16 + 64))) return rc;
-    double *d_u = static_cast<double *>(ctx->st_img.ptr);
-    uint32_t *d_c = reinterpret_cast<uint32_t *>(d_u + np), *d_n = d_c + np;
-    if ((rc = lash_sketch_set_pair_block_device(ctx, ref, r0, r1, qry, n_cols, triangle, ull_estimator, d_c, d_n, d_u))) return rc;
-    EcBlock eb;
-    if (algo == LASH_HMH && (rc = lash_set_ec_block(ctx, ref, r0, r1, qry, n_cols, eb))) return rc;
-
-    WithinArgs a = within_args(ref, r0, r1, qry, n_cols, triangle, k, model, fp32, d_c, d_n, d_u, eb);
+    WithinBlock b;
+    if ((rc = within_block(ctx, ref, r0, r1, qry, n_cols, triangle, k, model, fp32, ull_estimator, b))) return rc;
+    WithinArgs &a = b.a;
     a.limit = max_dist + (fp32 ? 0x1p-16 : 0x1p-40);                                 // the margin: see the top of this file
-
-    // scratch: [offsets u64 (n_tiles + 1) | mask u64 (n_tiles * WF_WORDS) | counts u32 (n_tiles)]
     const uint64_t nt = a.n_tiles;
-    if ((rc = reserve(ctx, ctx->wf_scratch, (nt + 1) * 8 + nt * WF_WORDS * 8 + nt * 4 + 64))) return rc;
-    uint64_t *d_off = static_cast<uint64_t *>(ctx->wf_scratch.ptr), *d_mask = d_off + nt + 1;
-    uint32_t *d_cnt = reinterpret_cast<uint32_t *>(d_mask + nt * WF_WORDS);
+    uint64_t *d_off = b.d_off, *d_mask = b.d_mask;
+    uint32_t *d_cnt = b.d_cnt;
     hipLaunchKernelGGL(within_mark_kernel, dim3(grid_for(nt)), dim3(256), 0, ctx->stream, a, d_mask, d_cnt);
     HIPCHK(ctx, hipGetLastError());
     std::vector<WithinPair> cand;

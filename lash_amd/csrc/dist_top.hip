@@ -375,13 +375,9 @@ int lash_sketch_set_pair_block_top(lash_ctx *ctx, const lash_sketch_set *ref, ui
     int rc;
     const int algo = ref->algo;
     const uint64_t np = (uint64_t)nr * n_cols;
-    if ((rc = reserve(ctx, ctx->st_img, np * 16 + 64))) return rc;                           // the statistics, as pair_block_within
-    double *d_u = static_cast<double *>(ctx->st_img.ptr);
-    uint32_t *d_c = reinterpret_cast<uint32_t *>(d_u + np), *d_n = d_c + np;
-    if ((rc = lash_sketch_set_pair_block_device(ctx, ref, r0, r1, qry, n_cols, triangle, ull_estimator, d_c, d_n, d_u))) return rc;
-    EcBlock eb;
-    if (algo == LASH_HMH && (rc = lash_set_ec_block(ctx, ref, r0, r1, qry, n_cols, eb))) return rc;
-    const WithinArgs a = within_args(ref, r0, r1, qry, n_cols, triangle, k, model, fp32, d_c, d_n, d_u, eb);
+    WithinBlock b;                                                                             // the statistics and scratch, as pair_block_within
+    if ((rc = within_block(ctx, ref, r0, r1, qry, n_cols, triangle, k, model, fp32, ull_estimator, b))) return rc;
+    const WithinArgs &a = b.a;
 
     // selection buffers: [hi u32 (np) | lo u32 (np) | tc, fc, col_bound (n_cols) | tr, fr, row_bound (nr) TopKey | same_col u32 (nr)]
     const uint64_t nk = 3 * (uint64_t)n_cols + 3 * (uint64_t)nr;
@@ -413,11 +409,9 @@ int lash_sketch_set_pair_block_top(lash_ctx *ctx, const lash_sketch_set *ref, ui
                        triangle && row_bound ? d_rb : nullptr, nr, n_cols, r0, triangle ? 1 : 0, d_fc, d_fr);
     HIPCHK(ctx, hipGetLastError());
 
-    // scratch: [offsets u64 (n_tiles + 1) | mask u64 (n_tiles * WF_WORDS) | counts u32 (n_tiles)], as pair_block_within
     const uint64_t nt = a.n_tiles;
-    if ((rc = reserve(ctx, ctx->wf_scratch, (nt + 1) * 8 + nt * WF_WORDS * 8 + nt * 4 + 64))) return rc;
-    uint64_t *d_off = static_cast<uint64_t *>(ctx->wf_scratch.ptr), *d_mask = d_off + nt + 1;
-    uint32_t *d_cnt = reinterpret_cast<uint32_t *>(d_mask + nt * WF_WORDS);
+    uint64_t *d_off = b.d_off, *d_mask = b.d_mask;
+    uint32_t *d_cnt = b.d_cnt;
     hipLaunchKernelGGL(top_mark_kernel, dim3((uint32_t)std::min<uint64_t>(nt, 1u << 20)), dim3(256), 0, ctx->stream, a, t, d_mask, d_cnt);
     HIPCHK(ctx, hipGetLastError());
     std::vector<WithinPair> cand;

@@ -22,6 +22,9 @@
 // --top K (not upstream): a block's pairs go through a selection on the device (lash_sketch_set_pair_block_top) and the survivors into
 // per-name lists on the host (lash_top_*, one per worker, merged at the end); N_K of a name is complete only after the last block, so the
 // kept rows are written once, at the end, in (row, col) order — the same rows in the same order as without the option, minus the others.
+// --cluster D (not upstream; same files only): single-linkage clusters, two names being linked iff --max-dist D prints their pair.  A
+// block's pairs are joined in a label array on the device (lash_sketch_set_pair_block_cluster, one lash_cluster per worker, merged at the
+// end); no pair text at all, the N lines "representative<TAB>member" are written once, at the end.
 #include "dist.hpp"
 
 #include <dirent.h>
@@ -128,6 +131,8 @@ std::string run_dist(const DistOptions &opt)
     if (!(err = slurp(rf["files"], txt)).empty() || !json_parse_string_array(txt, rnames)) return err.empty() ? "bad names JSON " + rf["files"] : err;
     if (!(err = slurp(qf["files"], txt)).empty() || !json_parse_string_array(txt, qnames)) return err.empty() ? "bad names JSON " + qf["files"] : err;
     const bool same_files = qf["files"] == rf["files"];                                               // main.rs:404
+    if (opt.has_cluster && !(same_files && rf["sketches"] == qf["sketches"]))
+        return "--cluster needs an all-vs-all run: -q and -r must name the same sketch files";
     // utils.rs:111-127: the maps' key order (a repeated name is one entry carrying its last sketch)
     std::vector<uint32_t> rorder, qorder;
     if (opt.file_order) {
@@ -238,7 +243,8 @@ std::string run_dist(const DistOptions &opt)
     const bool gpu_ec = small_ref && small_qry;
     FILE *out = fopen(opt.output_file.c_str(), "w");
     if (!out) return "cannot create " + opt.output_file;
-    if (!opt.matrix) fprintf(out, "Reference\tQuery\tDistance\n");                                   // main.rs:409-412
+    if (opt.has_cluster) fprintf(out, "Representative\tMember\n");
+    else if (!opt.matrix) fprintf(out, "Reference\tQuery\tDistance\n");                              // main.rs:409-412
     else for (uint32_t j = 0; j < nq; ++j) fprintf(out, "\t%s", col_name[j].c_str());                // main.rs:439-441
     // ---- blocks of reference rows: bounded pair tables (all-vs-all on 10^5 sketches is 5 * 10^9 printed pairs), about the
     //      same number of PRINTED pairs each — with same files row i prints i + 1 columns, so late blocks hold fewer rows ----
@@ -270,6 +276,11 @@ std::string run_dist(const DistOptions &opt)
         for (lash_top *&t : tops)
             if (lash_top_create(same_files ? nr : nq, opt.top, same_files ? 1 : 0, &t) != LASH_OK) return "cannot create the --top lists";
 
+    // --cluster: per worker, the clusters joined by the blocks it ran (created by the worker: the labels live on its device)
+    std::vector<lash_cluster *> clusters(devices.size(), nullptr);
+    struct ClustersGuard { std::vector<lash_cluster *> &c; ~ClustersGuard() { for (lash_cluster *p : c) lash_cluster_free(p); } } clusters_guard{clusters};
+    std::atomic<uint64_t> cl_pairs{0}, cl_pruned{0}, cl_joined{0}, cl_sent{0};   // (LASH_CLI_TIMING)
+
     auto worker = [&](size_t wi) {
         const int device = devices[wi];
         const DevSets *ds = nullptr;
@@ -277,6 +288,7 @@ std::string run_dist(const DistOptions &opt)
         lash_ctx *ctx = nullptr;
         int rc = lash_ctx_create(&ctx, device);                  // the worker's own stream and staging; the sets are shared, read-only
         if (rc == LASH_OK) rc = lash_ctx_set_layout(ctx, &opt.layout);
+        if (rc == LASH_OK && opt.has_cluster) rc = lash_cluster_create(ctx, nr, &clusters[wi]);
         std::string my_fail = rc == LASH_OK ? "" : std::string(lash_strerror(rc));
         // pair tables in page-locked memory (the copy back runs at the link rate): hmh C / N; hll zero + sum; ull the union estimate
         uint32_t *C = nullptr, *N = nullptr;
@@ -324,6 +336,16 @@ std::string run_dist(const DistOptions &opt)
                 if (rc == LASH_OK) rc = lash_top_add(tops[wi], w_row.data(), w_col.data(), w_dist.data(), kept);
                 if (rc == LASH_ERANGE) my_fail = "union of " + row_name[i0 + bad / n_cols] + " and " + col_name[bad % n_cols] + bias_msg;
                 else if (rc != LASH_OK) my_fail = std::string(lash_strerror(rc)) + " " + lash_ctx_last_error(ctx);
+            } else if (my_fail.empty() && !skip && opt.has_cluster) {
+                // pair statistics, expected collisions and the joins on the device; only the pairs it cannot decide come back, and
+                // the library links those in the accumulator's host side
+                uint64_t bad = 0;
+                lash_cluster_stats cs;
+                rc = lash_sketch_set_pair_block_cluster(ctx, ds->ref, i0, i1, ds->qry, n_cols, k, opt.model, opt.fp32 ? 1 : 0, ull_est, bias,
+                                                        opt.cluster_dist, clusters[wi], &cs, &bad);
+                if (rc == LASH_ERANGE) my_fail = "union of " + row_name[i0 + bad / n_cols] + " and " + col_name[bad % n_cols] + bias_msg;
+                else if (rc != LASH_OK) my_fail = std::string(lash_strerror(rc)) + " " + lash_ctx_last_error(ctx);
+                else { cl_pairs += cs.pairs; cl_pruned += cs.pruned; cl_joined += cs.joined_on_device; cl_sent += cs.sent_to_host; }
             } else if (my_fail.empty() && !skip && opt.has_max_dist) {
                 // pair statistics, expected collisions and the cutoff on the device; only the survivors come back
                 uint64_t kept = 0, bad = 0;
@@ -355,7 +377,7 @@ std::string run_dist(const DistOptions &opt)
                     if (rc != LASH_OK) my_fail = std::string(lash_strerror(rc)) + " " + lash_ctx_last_error(ctx);
                 }
             }
-            if (my_fail.empty() && !skip && !opt.has_max_dist && !opt.top) {
+            if (my_fail.empty() && !skip && !opt.has_max_dist && !opt.top && !opt.has_cluster) {
                 BlockTables bt;
                 bt.c_or_zero = C; bt.n_counts = N; bt.sum_or_union = U; bt.hmh_ec = have_ec ? EC : nullptr; bt.ld = n_cols;
                 my_fail = dist_block_rows(algo_id, prec, k, opt.model, opt.fp32, bias, i0, i1, same_files, nq, rcard.data(), qcard.data(), bt, row_name,
@@ -401,6 +423,31 @@ std::string run_dist(const DistOptions &opt)
             if (timing) fprintf(stderr, "[lash dist] --top: %llu candidates from the device, %llu rows kept\n",
                                 (unsigned long long)top_candidates.load(), (unsigned long long)n);
             mark("--top: the kept rows written");
+        }
+    }
+    if (opt.has_cluster && fail.empty()) {
+        // --cluster: the workers' clusters merged; every name under its cluster's first name, in row order
+        for (size_t w = 1; w < clusters.size() && fail.empty(); ++w)
+            if (!clusters[0] || !clusters[w] || lash_cluster_merge(clusters[0], clusters[w]) != LASH_OK) fail = "cannot merge the --cluster labels";
+        std::vector<uint32_t> label(nr);
+        if (fail.empty() && nr && (!clusters[0] || lash_cluster_labels(clusters[0], label.data()) != LASH_OK)) fail = "cannot read the --cluster labels";
+        if (fail.empty()) {
+            std::vector<uint32_t> by_rep(nr);
+            std::iota(by_rep.begin(), by_rep.end(), 0u);
+            std::stable_sort(by_rep.begin(), by_rep.end(), [&](uint32_t x, uint32_t y) { return label[x] < label[y]; });
+            std::string text;
+            uint64_t n_clusters = 0;
+            for (uint32_t i : by_rep) {
+                n_clusters += label[i] == i;
+                text.append(row_name[label[i]]).push_back('\t');
+                text.append(row_name[i]).push_back('\n');
+                if (text.size() >= (1u << 20)) { fwrite(text.data(), 1, text.size(), out); text.clear(); }
+            }
+            fwrite(text.data(), 1, text.size(), out);
+            if (timing) fprintf(stderr, "[lash dist] --cluster: %llu pairs looked at, %llu pruned as already joined, %llu joined on the device, "
+                                "%llu sent to the host, %llu clusters\n", (unsigned long long)cl_pairs.load(), (unsigned long long)cl_pruned.load(),
+                                (unsigned long long)cl_joined.load(), (unsigned long long)cl_sent.load(), (unsigned long long)n_clusters);
+            mark("--cluster: the clusters written");
         }
     }
     fclose(out);

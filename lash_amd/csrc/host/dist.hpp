@@ -20,6 +20,8 @@ struct DistOptions {
     bool has_max_dist = false; // --max-dist D: print only the rows whose distance d passes d <= D (list form only)
     double max_dist = 0.0;
     uint32_t top = 0;          // --top K (1..LASH_TOP_MAX): print only the rows in some name's K nearest (list form only); 0 = off
+    bool has_cluster = false;  // --cluster D: single-linkage clusters of a triangle run instead of pairs; names are linked iff --max-dist D prints them
+    double cluster_dist = 0.0;
     std::string hll_bias_file; // --hll-bias / $LASH_HLL_BIAS: HLL++ bias tables (lash_hll_bias_load); empty = that regime is refused
     lash_layout layout;        // --layout / $LASH_LAYOUT (include/lash_gfx950.h)
     DistOptions() { lash_layout_default(&layout); }

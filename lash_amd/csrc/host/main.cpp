@@ -5,7 +5,8 @@
 // Extras that do not exist upstream: --gpus N / --device D / --devices LIST (which GPUs to use, one worker each), --batch-mb M, --stream-mb M (files
 // larger than M MiB are streamed in chunks with on-device accumulation), --hmh-x-low; dist: --device D, --block-rows N,
 // --file-order (rows / columns in list-file order instead of the reference's seeded hash-map order), --max-dist D (print only
-// the pairs with distance <= D), --top K (only each name's K nearest) (reference rows per GPU call); both: --layout SPEC (or $LASH_LAYOUT): the crate-internal rules as data, see `lash_layout`
+// the pairs with distance <= D), --top K (only each name's K nearest), --cluster D (single-linkage clusters of an all-vs-all instead
+// of pairs) (reference rows per GPU call); both: --layout SPEC (or $LASH_LAYOUT): the crate-internal rules as data, see `lash_layout`
 // in include/lash_gfx950.h.
 #include <chrono>
 #include <cmath>
@@ -56,6 +57,10 @@ void usage()
             "      --max-dist <D> print only the pairs whose distance is <= D (same rows, same order; not with --dm)\n"
             "      --top <K>      print only each query's K nearest (triangle runs: a pair in either name's K nearest; the\n"
             "                     name itself counts, so use K+1 for K others), K 1-1024; same rows, same order; not with --dm\n"
+            "      --cluster <D>  all-vs-all only (-q and -r the same sketch files): single-linkage clusters instead of pairs; two\n"
+            "                     names are linked iff --max-dist D prints their pair.  Output: Representative<TAB>Member, one line\n"
+            "                     per name, the representative being the cluster's first name in row order; not with --dm,\n"
+            "                     --top or --max-dist\n"
             "      --hll-bias <file>  HLL++ bias tables (tools/ref_probe/extract_hll_bias.py) [default: $LASH_HLL_BIAS];\n"
             "                     without them hll estimates <= 5 * 2^p are refused\n");
 }
@@ -221,6 +226,17 @@ int cmd_dist(int argc, char **argv)
         }
         if (opt.matrix) { fprintf(stderr, "error: --top cannot be used with --dm (a square matrix cannot drop cells)\n"); return 2; }
         opt.top = (uint32_t)n;
+    }
+    if (a.kv.count("cluster")) {
+        const std::string &v = a.kv["cluster"];
+        char *e = nullptr;
+        const double d = v.empty() ? NAN : strtod(v.c_str(), &e);
+        if (!e || *e != 0 || !std::isfinite(d)) { fprintf(stderr, "error: invalid value '%s' for --cluster: a finite number is required\n", v.c_str()); return 2; }
+        if (opt.matrix) { fprintf(stderr, "error: --cluster cannot be used with --dm (clusters are not a matrix)\n"); return 2; }
+        if (opt.top) { fprintf(stderr, "error: --cluster cannot be used with --top (it prints clusters, not pairs)\n"); return 2; }
+        if (opt.has_max_dist) { fprintf(stderr, "error: --cluster cannot be used with --max-dist (--cluster D is its own cutoff)\n"); return 2; }
+        opt.has_cluster = true;
+        opt.cluster_dist = d;
     }
     err = layout_from_option(a.kv.count("layout") ? a.kv["layout"] : "", opt.layout);
     if (!err.empty()) { fprintf(stderr, "error: %s\n", err.c_str()); return 2; }

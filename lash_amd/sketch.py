@@ -596,6 +596,37 @@ class SketchSet:
         acc.free()
         return out
 
+    def pair_block_cluster(self, r0, r1, max_dist, k, clusters, n_cols=None, model=1, fp32=False, estimator="fgra", hll_bias=None, stats=None):
+        """`lash dist --cluster`: rows [r0, r1) x columns [0, n_cols) (default r1) of this set's lower triangle joined into `clusters` (a
+        Clusters of this set's size): two members are linked iff pair_block_within(..., triangle=True) returns their pair
+        (lash_sketch_set_pair_block_cluster).  Blocks may run in any order and over several Clusters objects (merge).  stats: optional
+        dict, gets pairs, pruned, joined_on_device, sent_to_host, clusters.  LashError.pair as pair_block_within.  cardinalities() must
+        have run."""
+        nc = min(int(r1), self.n) if n_cols is None else int(n_cols)
+        st, bad = _lib.ClusterStats(), C.c_uint64()
+        rc = self._lib.lash_sketch_set_pair_block_cluster(self._ctx._h, self._h, int(r0), int(r1), self._h, nc, int(k), int(model), 1 if fp32 else 0,
+                                                          ULL_ESTIMATORS[estimator], _bias_handle(hll_bias), float(max_dist), clusters._h,
+                                                          C.byref(st), C.byref(bad))
+        if rc == _lib.ERANGE:
+            e = LashError(rc, self._lib.lash_strerror(rc).decode() + " (pair %d)" % bad.value)
+            e.pair = bad.value                                       # (row - r0) * n_cols + col
+            raise e
+        self._ctx._check(rc)
+        if stats is not None:
+            stats.update({f: getattr(st, f) for f, _ in st._fields_})
+
+    def clusters(self, max_dist, k, block_rows=None, **kw):
+        """`lash dist --cluster` over the whole set: walks the triangle in row blocks of `block_rows` (default: one block) and returns,
+        as a numpy uint32 array, for every member the smallest index of its single-linkage cluster.  The other keywords go to
+        pair_block_cluster."""
+        acc = Clusters(self._ctx, self.n)
+        step = self.n if not block_rows else int(block_rows)
+        for r0 in range(0, self.n, max(step, 1)):
+            self.pair_block_cluster(r0, min(self.n, r0 + step), max_dist, k, acc, **kw)
+        out = acc.labels()
+        acc.free()
+        return out
+
     def pair_block(self, r0, r1, qry=None, n_cols=None, triangle=False, estimator="fgra", out=None):
         """statistics of rows [r0, r1) against columns [0, n_cols) of `qry` (default: this set) as the dict lash_dist_rows takes.
         `out`: optional dict of preallocated (e.g. pinned) flat arrays 'c', 'n' (uint32), 'u' (float64) of >= (r1-r0)*n_cols."""
@@ -675,6 +706,42 @@ class TopK:
     def free(self):
         if getattr(self, "_h", None):
             self._lib.lash_top_free(self._h)
+        self._h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+class Clusters:
+    """lash_cluster: the single-linkage clusters of n names joined so far — a label array on the context's GPU, where pair_block_cluster
+    joins both the links the device is sure of and the ones only the host could confirm; shared with the command line."""
+
+    def __init__(self, ctx, n):
+        self._ctx, self._lib, self.n = ctx, ctx._lib, int(n)
+        h = C.c_void_p()
+        ctx._check(self._lib.lash_cluster_create(ctx._h, self.n, C.byref(h)))
+        self._h = h
+
+    def _check(self, rc):
+        if rc != _lib.OK:
+            raise LashError(rc, self._lib.lash_strerror(rc).decode())
+
+    def merge(self, other):
+        """folds another accumulator's clusters in (one per worker / device); `other` is unchanged"""
+        self._check(self._lib.lash_cluster_merge(self._h, other._h))
+
+    def labels(self):
+        """numpy uint32 [n]: for every name the smallest index of its cluster"""
+        out = np.empty(self.n, np.uint32)
+        self._check(self._lib.lash_cluster_labels(self._h, out.ctypes.data))
+        return out
+
+    def free(self):
+        if getattr(self, "_h", None):
+            self._lib.lash_cluster_free(self._h)
         self._h = None
 
     def __del__(self):
