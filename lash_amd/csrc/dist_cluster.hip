@@ -10,12 +10,12 @@
 // joined with i so far (a root: label[x] == x).  It starts as the identity.
 //
 // Per block of rows [r0, r1) x columns [0, n_cols) of the lower triangle, after the pair kernels and the expected-collision GEMM:
-//   mark + join   the tiles of within_mark_kernel (dist_filter.hip).  For each printed off-diagonal pair: find both roots (reads only);
+//   mark + join   the tiles of mark_tiles (dist_filter.h).  For each printed off-diagonal pair: find both roots (reads only);
 //                 same root and the device can place the pair: PRUNED, no arithmetic (hmh / ull test the roots first; hll decides
-//                 first whether it can place the pair, which needs no distance).  Otherwise an interval [d_lo - margin, d_hi + margin]
-//                 that holds the host's d:
-//                   SURE    min(d_hi + margin, 1) <= D   -> join the two roots
-//                   OUT     d_lo - margin > D, or a NaN of hmh / ull   -> nothing
+//                 first whether it can place the pair, which needs no distance).  Otherwise the interval [d_lo, d_hi] of
+//                 pair_interval_dev (dist_filter.h), which holds the host's d:
+//                   SURE    d_hi <= D (PAIR_ONE: 1 <= D)   -> join the two roots
+//                   OUT     d_lo > D (PAIR_ONE: 1 > D), or a NaN of hmh / ull   -> nothing
 //                   UNSURE  everything else, every pair the device cannot place, a NaN of hll   -> mask bit: the pair goes back to
 //                           the host with its statistics (within_compact), which evaluates it exactly
 //   flatten       label[i] = root(i) for every index any call has touched so far, so that the next block's finds are one hop; it
@@ -24,20 +24,10 @@
 //                 flattened again.  Ordinary input has none.  lash_cluster_merge folds another accumulator in the same way: its
 //                 labels, copied through the host, are the links (i, label[i]).
 //
-// The interval.  Up to the final log / pow the device evaluates the host's expressions on the host's doubles (dist_filter.hip), so
-// the similarity is the host's bit for bit and d_lo = d_hi = the device's distance, which the libm of the two sides moves by less
-// than the margin (2^-40; 2^-16 under fp32: dist_filter.hip).  The one exception is HLL linear counting, whose union estimate calls
-// log (2 ulp between ocml and glibc): pair_similarity_dev gives a similarity from the union shrunk by 2^-44 (never below the host's:
-// d_lo) and one from the union grown by 2^-44 (never above: d_hi).  The distance is monotone in the similarity, so the host's d
-// lies in [d_lo - margin, d_hi + margin].  The host's d never exceeds 1 (min(.., 1); 1 - f^(1/k) with f >= 0), hence the cap.
-// Exact pairs: an upper similarity <= 0 means the host's is <= 0 too, and d = 1.0 on both sides, both models, f64 and f32 (as
-// dist_top.hip): SURE iff 1 <= D, else OUT, no margin.  NaN: hmh / ull similarities are bit-identical and NaN goes through log / pow
-// alike on both sides, so the host's d is NaN too and never links; under hll the pair is UNSURE.
-//
 // Soundness.
-//   A SURE pair is linked on the host: d <= d_hi + margin <= D (or d = 1 <= D exactly), and a host link is linked by definition.  So every
+//   A SURE pair is linked on the host: d <= d_hi <= D (or d = 1 <= D exactly), and a host link is linked by definition.  So every
 //     join joins two names that --max-dist D links: label components are always subsets of true components.
-//   An OUT pair is not linked: d >= d_lo - margin > D, or d = 1 > D, or d is NaN.  Dropping it loses nothing.
+//   An OUT pair is not linked: d >= d_lo > D, or d = 1 > D, or d is NaN.  Dropping it loses nothing.
 //   Pruning cannot change the components: a pruned pair has both names under one root, and labels only ever record true links, so the
 //     two names are already connected by true links; the pruned pair, linked or not, adds no connectivity.  The same holds for an
 //     UNSURE pair whose roots are equal.  Pairs the device cannot place are never pruned: the host must see each of them, because
@@ -75,7 +65,7 @@ namespace lash {
 struct ClusterArgs {
     uint32_t *label;
     unsigned long long *counts;
-    double margin, max_dist;
+    double max_dist;
     uint32_t r0;
 };
 
@@ -115,55 +105,31 @@ __device__ inline bool cluster_pair(const WithinArgs &a, const ClusterArgs &c, u
 {
     const bool same = row_root == find_root(c.label, q);
     if (same && a.algo != LASH_HLL) { ++pruned; return false; }
-    double sim, sim_low;
+    double sim, sim_low, d_lo, d_hi;
     if (!pair_similarity_dev(a, r, q, &sim, &sim_low)) return true;                     // the host's: never pruned
     if (same) { ++pruned; return false; }
-    if (!(sim <= 0.0)) {
-        const bool ull = a.algo == LASH_ULL;
-        const double d_lo = pairmath::distance_from_similarity(sim, ull, a.k, a.model, a.fp32 != 0);
-        const double d_hi = sim_low == sim ? d_lo : pairmath::distance_from_similarity(sim_low, ull, a.k, a.model, a.fp32 != 0);
-        if (d_lo != d_lo || d_hi != d_hi) return a.algo == LASH_HLL;                    // NaN
-        if (d_lo - c.margin > c.max_dist) return false;                                 // out
-        if (!(fmin(d_hi + c.margin, 1.0) <= c.max_dist)) return true;                   // unsure, roots differ
-    } else if (!(1.0 <= c.max_dist)) return false;                                      // exact: d = 1 on both sides
+    if (pair_interval_dev(a, sim, sim_low, &d_lo, &d_hi) == PAIR_NAN) return a.algo == LASH_HLL;
+    if (d_lo > c.max_dist) return false;                                                // out
+    if (!(d_hi <= c.max_dist)) return true;                                             // unsure, roots differ
     if (join_roots(c.label, c.r0 + r, q)) ++joined;                                     // sure
     return false;
 }
 
 }  // namespace
 
-// the mask layout of within_mark_kernel (dist_filter.hip), for its scan and write kernels
 __global__ void __launch_bounds__(256) cluster_mark_kernel(WithinArgs a, ClusterArgs c, uint64_t *__restrict__ mask, uint32_t *__restrict__ tile_count)
 {
-    __shared__ uint32_t wsum[4];
     __shared__ uint32_t s_pruned, s_joined;
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     if (threadIdx.x == 0) { s_pruned = 0; s_joined = 0; }
     __syncthreads();
     uint32_t pruned = 0, joined = 0;
-    for (uint64_t tile = blockIdx.x; tile < a.n_tiles; tile += gridDim.x) {
-        const uint32_t r = (uint32_t)(tile / a.tiles_x), c0 = (uint32_t)(tile % a.tiles_x) * WF_TILE, c_end = row_end(a, r);
-        if (c0 >= c_end) {                                                              // wholly above the diagonal
-            if (threadIdx.x == 0) tile_count[tile] = 0;
-            continue;
-        }
-        uint32_t cnt = 0;
-        for (uint32_t step = 0; step < 4; ++step) {
-            const uint32_t word = step * 4u + wave, q = c0 + word * 64u + lane;
-            // The row's root, read again for every 64 pairs: one address for the whole wave (a single request) that goes past the L1
-            // like every label read.  Reading it once per tile would save three requests of a tile's ~20, but a row is new when its
-            // block runs: the joins of this wave's earlier steps are what lets the later ones prune.
-            const uint32_t row_root = find_root(c.label, c.r0 + r);
-            const bool keep = q < c_end && q != c.r0 + r && cluster_pair(a, c, r, q, row_root, pruned, joined);
-            const uint64_t bits = __ballot(keep);
-            if (lane == 0) mask[tile * WF_WORDS + word] = bits;
-            cnt += (uint32_t)__popcll(bits);
-        }
-        if (lane == 0) wsum[wave] = cnt;
-        __syncthreads();
-        if (threadIdx.x == 0) tile_count[tile] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
-        __syncthreads();
-    }
+    mark_tiles(a, mask, tile_count, [&](uint32_t r, uint32_t q) {
+        // The row's root, read again for every 64 pairs: one address for the whole wave (a single request) that goes past the L1
+        // like every label read.  Reading it once per tile would save three requests of a tile's ~20, but a row is new when its
+        // block runs: the joins of this wave's earlier steps are what lets the later ones prune.
+        const uint32_t row_root = find_root(c.label, c.r0 + r);
+        return q != c.r0 + r && cluster_pair(a, c, r, q, row_root, pruned, joined);
+    });
     if (pruned) atomicAdd(&s_pruned, pruned);
     if (joined) atomicAdd(&s_joined, joined);
     __syncthreads();
@@ -289,27 +255,19 @@ int lash_sketch_set_pair_block_cluster(lash_ctx *ctx, const lash_sketch_set *ref
 {
     using namespace lash;
     if (stats) *stats = lash_cluster_stats{};
-    if (!ctx || !ref || !qry || !cluster || r0 > r1 || r1 > ref->n || n_cols > qry->n || k < 1 || k > 32 || (model != 0 && model != 1))
-        return LASH_EINVAL;
-    if (std::isnan(max_dist) || r1 > cluster->n || n_cols > cluster->n || cluster->device != ctx->device) return LASH_EINVAL;
-    if (ref->card.size() != ref->n || qry->card.size() != qry->n) return LASH_EINVAL;          // lash_sketch_set_cardinalities first
-    const uint32_t nr = r1 - r0;
-    if (nr == 0 || n_cols == 0) return LASH_OK;
-    (void)hipSetDevice(ctx->device);
+    if (!cluster || std::isnan(max_dist) || r1 > cluster->n || n_cols > cluster->n || !ctx || cluster->device != ctx->device) return LASH_EINVAL;
     int rc;
-    const int algo = ref->algo;
     WithinBlock b;
-    if ((rc = within_block(ctx, ref, r0, r1, qry, n_cols, 1, k, model, fp32, ull_estimator, b))) return rc;
+    if ((rc = within_block(ctx, ref, r0, r1, qry, n_cols, 1, k, model, fp32, ull_estimator, b)) || !b.a.n_tiles) return rc;
     const WithinArgs &a = b.a;
 
     ClusterArgs c{};
     c.label = cluster->d_label;
     c.counts = cluster->d_counts;
-    c.margin = fp32 ? 0x1p-16 : 0x1p-40;                                                       // dist_filter.hip
     c.max_dist = max_dist;
     c.r0 = r0;
     HIPCHK(ctx, hipMemsetAsync(cluster->d_counts, 0, 3 * sizeof(unsigned long long), ctx->stream));
-    hipLaunchKernelGGL(cluster_mark_kernel, dim3((uint32_t)std::min<uint64_t>(a.n_tiles, 1u << 20)), dim3(256), 0, ctx->stream, a, c, b.d_mask, b.d_cnt);
+    hipLaunchKernelGGL(cluster_mark_kernel, dim3(mark_grid(a.n_tiles)), dim3(256), 0, ctx->stream, a, c, b.d_mask, b.d_cnt);
     HIPCHK(ctx, hipGetLastError());
     cluster->touched = std::max({cluster->touched, r1, n_cols});                               // blocks may come in any order
     unsigned long long counts[2] = {0, 0};
@@ -319,19 +277,11 @@ int lash_sketch_set_pair_block_cluster(lash_ctx *ctx, const lash_sketch_set *ref
     std::vector<WithinPair> cand;
     if ((rc = within_compact(ctx, a, b.d_mask, b.d_cnt, b.d_off, cand))) return rc;
 
-    // exact: the host arithmetic of lash_dist_rows in row-major order (the first refused pair is the one --max-dist reports)
     std::vector<uint2> links;
-    for (const WithinPair &w : cand) {
-        const uint32_t row = r0 + w.row;
-        double ec, d;
-        const double *ecp = nullptr;
-        if (algo == LASH_HMH && !std::isnan(w.ec_x)) { ec = hmh_ec_from_cell_sum(w.ec_x); ecp = &ec; }
-        if (!dist_pair_host(algo, ref->p, k, model, fp32, ref->card[row], qry->card[w.col], w.c_or_zero, w.n, w.sum_or_union, tables, ecp, &d)) {
-            if (bad_pair) *bad_pair = (uint64_t)w.row * n_cols + w.col;
-            return LASH_ERANGE;
-        }
-        if (d <= max_dist) links.push_back(make_uint2(row, w.col));
-    }
+    rc = filter_evaluate(cand, ref, r0, qry, n_cols, k, model, fp32, tables, bad_pair, [&](uint32_t row, uint32_t col, double d, uint32_t) {
+        if (d <= max_dist) links.push_back(make_uint2(row, col));
+    });
+    if (rc) return rc;
     if (!links.empty()) HIPCHK(ctx, apply_links(cluster, ctx->stream, links, &roots));
     if (stats) {
         uint64_t pairs = 0;                                                                    // the printed off-diagonal pairs

@@ -1,7 +1,7 @@
 // dist_filter.h — what the pair filters of `lash dist` share: --max-dist (dist_filter.hip), --top (dist_top.hip) and --cluster
-// (dist_cluster.hip).  The block's
-// statistics as the filter kernels read them, the device distance of one pair (its error analysis is at the top of dist_filter.hip),
-// and the candidate layout with the scan / write kernels that compact a mask of candidates in (row, col) order.
+// (dist_cluster.hip).  The block's statistics as the filter kernels read them, the device similarity of one pair and the interval
+// it puts around the host's distance (with the error analysis), the tile loop of the three mark kernels with the mask layout the
+// scan / write kernels compact in (row, col) order, and the host's exact evaluation of what comes back.
 #pragma once
 #include "lash_ctx.h"
 #include "dist_pair.h"
@@ -38,11 +38,18 @@ __device__ __forceinline__ uint32_t row_end(const WithinArgs &a, uint32_t r)
     return e < (int64_t)a.n_cols ? (uint32_t)e : a.n_cols;
 }
 
+// the position in EcBlock::X of the cell sum of a small hmh pair: rs / cs = the row's / column's place in its set's small_idx, both >= 0
+__device__ __forceinline__ uint64_t small_cell(const WithinArgs &a, int32_t rs, int32_t cs)
+{
+    const uint32_t ri = (uint32_t)rs - a.rbase, q0 = (uint32_t)cs / a.q_step * a.q_step, nq = min(a.q_step, a.nqs - q0);
+    return (uint64_t)a.nrs * q0 + (uint64_t)ri * nq + ((uint32_t)cs - q0);
+}
+
 // The device's similarity *sim of pair (r, q).  false: the pair needs the host's arithmetic (the HLL++ bias-table regime, a
 // linear-counting estimate at the threshold, a small HyperMinHash pair without a cell sum) and nothing is set.  The similarity is
 // the host's bit for bit, except for HLL in linear counting, where the union is shrunk by 2^-44 so that *sim is never below the
-// host's (dist_filter.hip); *sim_low is then the same expression with the union grown by 2^-44, never above the host's, and
-// everywhere else equal to *sim (--cluster needs both sides, dist_cluster.hip).
+// host's; *sim_low is then the same expression with the union grown by 2^-44, never above the host's, and everywhere else equal
+// to *sim (pair_interval_dev below says why).
 __device__ inline bool pair_similarity_dev(const WithinArgs &a, uint32_t r, uint32_t q, double *sim_out, double *sim_low_out)
 {
     const uint64_t at = (uint64_t)r * a.n_cols + q;
@@ -74,8 +81,7 @@ __device__ inline bool pair_similarity_dev(const WithinArgs &a, uint32_t r, uint
         if (c != 0.0 && !pairmath::hmh_ec_closed_form(qc, rc, &ec)) {
             const int32_t rs = a.row_small[r], cs = a.col_small[q];
             if (rs < 0 || cs < 0 || a.nrs == 0) return false;                           // (only NaN cardinalities get here)
-            const uint32_t ri = (uint32_t)rs - a.rbase, q0 = (uint32_t)cs / a.q_step * a.q_step, nq = min(a.q_step, a.nqs - q0);
-            ec = pairmath::hmh_ec_from_cell_sum(a.X[(uint64_t)a.nrs * q0 + (uint64_t)ri * nq + ((uint32_t)cs - q0)]);
+            ec = pairmath::hmh_ec_from_cell_sum(a.X[small_cell(a, rs, cs)]);
         }
         sim = pairmath::hmh_similarity(c, n, ec);
     }
@@ -83,15 +89,78 @@ __device__ inline bool pair_similarity_dev(const WithinArgs &a, uint32_t r, uint
     return true;
 }
 
-// The device's similarity *sim (pair_similarity_dev's) and the distance *d it gives; false as pair_similarity_dev.
-__device__ inline bool pair_distance_dev(const WithinArgs &a, uint32_t r, uint32_t q, double *sim_out, double *d_out)
+// How far the host's distance d of a placed pair can be from the device's: the one margin of the three filters.
+//   f64:  -ln(f) / k with d <= 1 has |ln f| <= k <= 32: ulp(32) / k ~ 2^-47 per ulp; 1 - f^(1/k): ulp(1) = 2^-52.  ocml and glibc are
+//         a few ulp apart: < 2^-44.  margin 2^-40.
+//   fp32: the same in float (ocml's logf / powf: <= 2 ulp; glibc's correctly rounded or 1 ulp): ulp(1.0f) = 2^-23 per ulp of
+//         d ~ 1, so a few ulp each side: < 2^-19.  margin 2^-16 (1.5e-5).
+__host__ __device__ constexpr double filter_margin(bool fp32) { return fp32 ? 0x1p-16 : 0x1p-40; }
+
+// The interval [*d_lo, *d_hi] that holds the host's exact d (dist_pair_host, in f32 under fp32) of a pair pair_similarity_dev has
+// placed (its false is the fourth outcome: the pair is the host's alone, always sent back and never pruned, because it may be the
+// one a run is refused on, LASH_ERANGE).
+//   Identical similarity.  Up to the final log / pow the device evaluates the host's expressions (dist_pair.h: + - * / with
+//     contraction off) on the host's f64 inputs: cardinalities, C / N / zero / sum / union estimates and, for small HyperMinHash
+//     pairs, the same collision_gemm_kernel cell sums.  So sim == sim_low == the host's similarity bit for bit, and d_lo and d_hi
+//     are one distance -/+ filter_margin, which covers the two sides' libm call on the same frac.
+//   HLL linear counting, m ln(m / zero), is the exception: it calls log.  ocml's f64 log is within 1 ulp and glibc's within 1 ulp,
+//     so the union estimates differ by at most 2 ulp (2^-51 relative).  pair_similarity_dev gives sim from the union shrunk by
+//     2^-44 (128x that: never below the host's similarity) and sim_low from the union grown by 2^-44 (never above it), and refuses
+//     an estimate within 2^-40 of the linear-counting threshold (the host may fall on the other side) like the whole bias-table
+//     regime.  The distance decreases as the similarity grows, so the host's d lies in [d(sim) - margin, d(sim_low) + margin].
+//   Cap.  The host's d never exceeds 1 (min(.., 1); 1 - f^(1/k) with f >= 0): d_hi = min(.., 1).
+//   PAIR_ONE.  sim <= 0 means the host's similarity, never above sim, is <= 0 as well, and then d = 1.0 exactly on both sides, both
+//     models, f64 and f32: no margin.  *d_lo = *d_hi = 1.
+//   PAIR_NAN.  A NaN distance.  hmh / ull similarities are bit-identical and NaN goes through log / pow alike on both sides: the
+//     host's d is NaN too, which no filter keeps, ranks or links.  Under hll the host decides: the pair is sent back.
+enum { PAIR_INTERVAL, PAIR_ONE, PAIR_NAN };
+__device__ inline int pair_interval_dev(const WithinArgs &a, double sim, double sim_low, double *d_lo, double *d_hi)
 {
-    double sim, sim_low;
-    if (!pair_similarity_dev(a, r, q, &sim, &sim_low)) return false;
-    *sim_out = sim;
-    *d_out = pairmath::distance_from_similarity(sim, a.algo == LASH_ULL, a.k, a.model, a.fp32 != 0);
-    return true;
+    *d_lo = *d_hi = 1.0;
+    if (sim <= 0.0) return PAIR_ONE;
+    const bool ull = a.algo == LASH_ULL;
+    const double margin = filter_margin(a.fp32 != 0);
+    const double near = pairmath::distance_from_similarity(sim, ull, a.k, a.model, a.fp32 != 0);
+    const double far = sim_low == sim ? near : pairmath::distance_from_similarity(sim_low, ull, a.k, a.model, a.fp32 != 0);   // (hll only)
+    if (near != near || far != far) return PAIR_NAN;
+    *d_lo = near - margin;
+    *d_hi = fmin(far + margin, 1.0);
+    return PAIR_INTERVAL;
 }
+
+// The tile loop of the three mark kernels (256 threads; grid mark_grid(n_tiles), any smaller grid works).  A workgroup owns a tile of
+// WF_TILE consecutive columns of one block row, tiles in row-major order; each wave takes 64 pairs at a time (step s of wave w:
+// mask word s * 4 + w) and calls keep(r, q) for the printed ones, q < row_end(r), possibly with some lanes off.
+// The layout within_scan_kernel / within_write_kernel (dist_filter.hip) read, stated here and nowhere else:
+//   mask[tile * WF_WORDS + word]   bit l set iff pair (r, c0 + word * 64 + l) is a candidate, r = tile / tiles_x,
+//                                  c0 = tile % tiles_x * WF_TILE; every word of a tile that starts before its row's end is written
+//   tile_count[tile]               the tile's set bits; 0 for a tile wholly above the diagonal, whose mask words are NOT written
+template <class Keep>
+__device__ __forceinline__ void mark_tiles(const WithinArgs &a, uint64_t *__restrict__ mask, uint32_t *__restrict__ tile_count, Keep &&keep)
+{
+    __shared__ uint32_t wsum[4];
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    for (uint64_t tile = blockIdx.x; tile < a.n_tiles; tile += gridDim.x) {
+        const uint32_t r = (uint32_t)(tile / a.tiles_x), c0 = (uint32_t)(tile % a.tiles_x) * WF_TILE, c_end = row_end(a, r);
+        if (c0 >= c_end) {                                                              // wholly above the diagonal
+            if (threadIdx.x == 0) tile_count[tile] = 0;
+            continue;
+        }
+        uint32_t cnt = 0;
+        for (uint32_t step = 0; step < 4; ++step) {
+            const uint32_t word = step * 4u + wave, q = c0 + word * 64u + lane;
+            const uint64_t bits = __ballot(q < c_end && keep(r, q));
+            if (lane == 0) mask[tile * WF_WORDS + word] = bits;
+            cnt += (uint32_t)__popcll(bits);
+        }
+        if (lane == 0) wsum[wave] = cnt;
+        __syncthreads();
+        if (threadIdx.x == 0) tile_count[tile] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+        __syncthreads();
+    }
+}
+
+inline uint32_t mark_grid(uint64_t n_tiles) { return (uint32_t)std::min<uint64_t>(n_tiles, 1u << 20); }
 
 // the block's WithinArgs from its statistics in HBM (d_c / d_n / d_u as lash_sketch_set_pair_block_device wrote them)
 WithinArgs within_args(const lash_sketch_set *ref, uint32_t r0, uint32_t r1, const lash_sketch_set *qry, uint32_t n_cols, int triangle, int k,
@@ -100,7 +169,8 @@ WithinArgs within_args(const lash_sketch_set *ref, uint32_t r0, uint32_t r1, con
 // One block of a filtered `lash dist` run, ready for a mark kernel: the pair statistics [sum_or_union f64 | c_or_zero u32 | n u32] (as
 // lash_sketch_set_pair_block) and, for hmh, the small pairs' cell sums in HBM, the WithinArgs over them (a.limit is the caller's), and
 // the compaction scratch [offsets u64 (n_tiles + 1) | mask u64 (n_tiles * WF_WORDS) | counts u32 (n_tiles)].  Queued on the context's
-// stream; nr and n_cols are not 0.
+// stream.  within_block is what the three ABI entries do first: the argument checks they share (LASH_EINVAL), hipSetDevice, the pair
+// kernels and the expected-collision GEMM.  LASH_OK with b.a.n_tiles == 0: an empty block, the entry returns LASH_OK at once.
 struct WithinBlock {
     WithinArgs a;
     uint64_t *d_off, *d_mask;
@@ -112,5 +182,35 @@ int within_block(lash_ctx *ctx, const lash_sketch_set *ref, uint32_t r0, uint32_
 // compaction: mask words [n_tiles][WF_WORDS] of candidates and their per-tile counts -> exclusive offsets (d_off: n_tiles + 1) -> the
 // candidates with their statistics in (row, col) order, copied back into `cand` (synchronous; dist_filter.hip's scan and write kernels)
 int within_compact(lash_ctx *ctx, const WithinArgs &a, const uint64_t *d_mask, const uint32_t *d_cnt, uint64_t *d_off, std::vector<WithinPair> &cand);
+
+// exact: the candidates in order (row-major) through the host arithmetic of lash_dist_rows, each handed to each(set row, col, d, block
+// row).  LASH_ERANGE at the first pair that arithmetic refuses (the one an unfiltered run reports), with *bad_pair = its place in the
+// block; the pairs before it have been handed over.
+template <class Each>
+int filter_evaluate(const std::vector<WithinPair> &cand, const lash_sketch_set *ref, uint32_t r0, const lash_sketch_set *qry, uint32_t n_cols, int k,
+                    int model, int fp32, const lash_hll_bias *tables, uint64_t *bad_pair, Each each)
+{
+    const int algo = ref->algo;
+    for (const WithinPair &w : cand) {
+        const uint32_t row = r0 + w.row;
+        double ec, d;
+        const double *ecp = nullptr;
+        if (algo == LASH_HMH && !std::isnan(w.ec_x)) { ec = hmh_ec_from_cell_sum(w.ec_x); ecp = &ec; }
+        if (!dist_pair_host(algo, ref->p, k, model, fp32, ref->card[row], qry->card[w.col], w.c_or_zero, w.n, w.sum_or_union, tables, ecp, &d)) {
+            if (bad_pair) *bad_pair = (uint64_t)w.row * n_cols + w.col;
+            return LASH_ERANGE;
+        }
+        each(row, w.col, d, w.row);
+    }
+    return LASH_OK;
+}
+
+// the rows an entry keeps: the first `cap` are stored, all are counted
+struct KeptRows {
+    uint32_t *row, *col;
+    double *dist;
+    uint64_t cap, n;
+    void add(uint32_t r, uint32_t c, double d) { if (n < cap) { row[n] = r; col[n] = c; dist[n] = d; } ++n; }
+};
 
 }  // namespace lash

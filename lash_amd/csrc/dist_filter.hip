@@ -13,53 +13,20 @@
 // A candidate is written with its statistics (and, for small HyperMinHash pairs, the expected-collision cell sum), and the host
 // evaluates it exactly with the code lash_dist_rows runs: the kernel only has to be sure not to miss a pair.
 //
-// Why "d_dev <= D + margin" cannot miss one.  Up to the final log / pow, the device evaluates the same expressions as the host
-// (dist_pair.h: +, -, *, / with contraction off, the same f64 inputs — cardinalities, C / N / zero / sum / union estimates, and
-// for small HyperMinHash pairs the same collision_gemm_kernel cell sums), so the similarity is bit-identical — with one exception:
-// HLL++ linear counting, m ln(m / zero), calls log.  ocml's f64 log is within 1 ulp, glibc's within 1 ulp, so the two can differ
-// by 2 ulp (2^-51 relative); the kernel shrinks its union estimate by 2^-44 (128x that) before the inclusion-exclusion, which can
-// only raise the similarity, and treats an estimate within 2^-40 of the linear-counting threshold as a candidate outright (the host
-// might fall on the other side).  The HLL++ bias-table regime (raw estimate <= 5m) is host-only arithmetic: always a candidate.
-// What remains is the distance's own libm call on the same frac:
-//   f64:  -ln(f) / k with d <= 1 has |ln f| <= k <= 32: ulp(32) / k ~ 2^-47 per ulp; 1 - f^(1/k): ulp(1) = 2^-52.  A few ulp each
-//         side: < 2^-44.  margin 2^-40.
-//   fp32: the same in float (ocml's logf / powf: <= 2 ulp; glibc's correctly rounded or 1 ulp): ulp(1.0f) = 2^-23 per ulp of
-//         d ~ 1, so a few ulp each side: < 2^-19.  margin 2^-16 (1.5e-5).
-// NaN distances (ull, two empty sketches, model 0) are candidates too; the host drops them (NaN never passes).
+// Why "d_dev <= D + margin" cannot miss one: the host's d is never below the device's distance of pair_similarity_dev's similarity
+// minus filter_margin (dist_filter.h, above pair_interval_dev, whose lower end this is), and a pair the device cannot place is a
+// candidate outright.  NaN distances (ull, two empty sketches, model 0) are candidates too; the host drops them (NaN never passes).
 #include "dist_filter.h"
 
 namespace lash {
 
-__device__ bool within_candidate(const WithinArgs &a, uint32_t r, uint32_t q)
-{
-    double sim, d;
-    if (!pair_distance_dev(a, r, q, &sim, &d)) return true;
-    return !(d > a.limit);                                                              // (NaN: a candidate)
-}
-
 __global__ void __launch_bounds__(256) within_mark_kernel(WithinArgs a, uint64_t *__restrict__ mask, uint32_t *__restrict__ tile_count)
 {
-    __shared__ uint32_t wsum[4];
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    for (uint64_t tile = blockIdx.x; tile < a.n_tiles; tile += gridDim.x) {
-        const uint32_t r = (uint32_t)(tile / a.tiles_x), c0 = (uint32_t)(tile % a.tiles_x) * WF_TILE, c_end = row_end(a, r);
-        if (c0 >= c_end) {                                                              // wholly above the diagonal
-            if (threadIdx.x == 0) tile_count[tile] = 0;
-            continue;
-        }
-        uint32_t cnt = 0;
-        for (uint32_t step = 0; step < 4; ++step) {
-            const uint32_t word = step * 4u + wave, q = c0 + word * 64u + lane;
-            const bool keep = q < c_end && within_candidate(a, r, q);
-            const uint64_t bits = __ballot(keep);
-            if (lane == 0) mask[tile * WF_WORDS + word] = bits;
-            cnt += (uint32_t)__popcll(bits);
-        }
-        if (lane == 0) wsum[wave] = cnt;
-        __syncthreads();
-        if (threadIdx.x == 0) tile_count[tile] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
-        __syncthreads();
-    }
+    mark_tiles(a, mask, tile_count, [&](uint32_t r, uint32_t q) {
+        double sim, sim_low;
+        if (!pair_similarity_dev(a, r, q, &sim, &sim_low)) return true;
+        return !(pairmath::distance_from_similarity(sim, a.algo == LASH_ULL, a.k, a.model, a.fp32 != 0) > a.limit);   // (NaN: a candidate)
+    });
 }
 
 // offsets[t] = sum of counts[0 .. t), offsets[n] = the total.  One workgroup: thread i sums a contiguous run of tiles, the 1024
@@ -113,26 +80,13 @@ __global__ void __launch_bounds__(256) within_write_kernel(WithinArgs a, const u
             w.ec_x = __builtin_nan("");
             if (a.algo == LASH_HMH && a.nrs) {
                 const int32_t rs = a.row_small[r], cs = a.col_small[q];
-                if (rs >= 0 && cs >= 0) {
-                    const uint32_t ri = (uint32_t)rs - a.rbase, q0 = (uint32_t)cs / a.q_step * a.q_step, nq = min(a.q_step, a.nqs - q0);
-                    w.ec_x = a.X[(uint64_t)a.nrs * q0 + (uint64_t)ri * nq + ((uint32_t)cs - q0)];
-                }
+                if (rs >= 0 && cs >= 0) w.ec_x = a.X[small_cell(a, rs, cs)];
             }
             out[base + before[word] + below] = w;
         }
         __syncthreads();
     }
 }
-
-}  // namespace lash
-
-namespace {
-
-uint32_t grid_for(uint64_t n_tiles) { return (uint32_t)std::min<uint64_t>(n_tiles, 1u << 20); }
-
-}  // namespace
-
-namespace lash {
 
 WithinArgs within_args(const lash_sketch_set *ref, uint32_t r0, uint32_t r1, const lash_sketch_set *qry, uint32_t n_cols, int triangle, int k,
                        int model, int fp32, const uint32_t *d_c, const uint32_t *d_n, const double *d_u, const EcBlock &eb)
@@ -161,6 +115,11 @@ WithinArgs within_args(const lash_sketch_set *ref, uint32_t r0, uint32_t r1, con
 int within_block(lash_ctx *ctx, const lash_sketch_set *ref, uint32_t r0, uint32_t r1, const lash_sketch_set *qry, uint32_t n_cols, int triangle, int k,
                  int model, int fp32, int ull_estimator, WithinBlock &b)
 {
+    b = WithinBlock{};
+    if (!ctx || !ref || !qry || r0 > r1 || r1 > ref->n || n_cols > qry->n || k < 1 || k > 32 || (model != 0 && model != 1)) return LASH_EINVAL;
+    if (ref->card.size() != ref->n || qry->card.size() != qry->n) return LASH_EINVAL;          // lash_sketch_set_cardinalities first
+    if (r0 == r1 || n_cols == 0) return LASH_OK;
+    (void)hipSetDevice(ctx->device);
     int rc;
     const uint64_t np = (uint64_t)(r1 - r0) * n_cols;
     if ((rc = reserve(ctx, ctx->st_img, np * 16 + 64))) return rc;
@@ -191,7 +150,7 @@ int within_compact(lash_ctx *ctx, const WithinArgs &a, const uint64_t *d_mask, c
     if (n_cand) {
         if ((rc = reserve(ctx, ctx->wf_out, n_cand * sizeof(WithinPair)))) return rc;
         WithinPair *d_out = static_cast<WithinPair *>(ctx->wf_out.ptr);
-        hipLaunchKernelGGL(within_write_kernel, dim3(grid_for(nt)), dim3(256), 0, ctx->stream, a, d_mask, d_cnt, d_off, d_out);
+        hipLaunchKernelGGL(within_write_kernel, dim3(mark_grid(nt)), dim3(256), 0, ctx->stream, a, d_mask, d_cnt, d_off, d_out);
         HIPCHK(ctx, hipGetLastError());
         HIPCHK(ctx, hipMemcpyAsync(cand.data(), d_out, n_cand * sizeof(WithinPair), hipMemcpyDeviceToHost, ctx->stream));
         HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
@@ -208,49 +167,25 @@ int lash_sketch_set_pair_block_within(lash_ctx *ctx, const lash_sketch_set *ref,
                                       double max_dist, uint32_t *out_row, uint32_t *out_col, double *out_dist, uint64_t cap, uint64_t *n_kept,
                                       uint64_t *bad_pair, uint64_t *n_candidates)
 {
+    using namespace lash;
     if (n_kept) *n_kept = 0;
     if (n_candidates) *n_candidates = 0;
-    if (!ctx || !ref || !qry || !n_kept || r0 > r1 || r1 > ref->n || n_cols > qry->n || k < 1 || k > 32 || (model != 0 && model != 1))
-        return LASH_EINVAL;
-    if (std::isnan(max_dist) || (cap && (!out_row || !out_col || !out_dist))) return LASH_EINVAL;
-    if (ref->card.size() != ref->n || qry->card.size() != qry->n) return LASH_EINVAL;          // lash_sketch_set_cardinalities first
-    const uint32_t nr = r1 - r0;
-    if (nr == 0 || n_cols == 0) return LASH_OK;
-    (void)hipSetDevice(ctx->device);
+    if (!n_kept || std::isnan(max_dist) || (cap && (!out_row || !out_col || !out_dist))) return LASH_EINVAL;
     int rc;
-    const int algo = ref->algo;
     WithinBlock b;
-    if ((rc = within_block(ctx, ref, r0, r1, qry, n_cols, triangle, k, model, fp32, ull_estimator, b))) return rc;
-    WithinArgs &a = b.a;
-    a.limit = max_dist + (fp32 ? 0x1p-16 : 0x1p-40);                                 // the margin: see the top of this file
-    const uint64_t nt = a.n_tiles;
-    uint64_t *d_off = b.d_off, *d_mask = b.d_mask;
-    uint32_t *d_cnt = b.d_cnt;
-    hipLaunchKernelGGL(within_mark_kernel, dim3(grid_for(nt)), dim3(256), 0, ctx->stream, a, d_mask, d_cnt);
+    if ((rc = within_block(ctx, ref, r0, r1, qry, n_cols, triangle, k, model, fp32, ull_estimator, b)) || !b.a.n_tiles) return rc;
+    b.a.limit = max_dist + filter_margin(fp32 != 0);
+    hipLaunchKernelGGL(within_mark_kernel, dim3(mark_grid(b.a.n_tiles)), dim3(256), 0, ctx->stream, b.a, b.d_mask, b.d_cnt);
     HIPCHK(ctx, hipGetLastError());
     std::vector<WithinPair> cand;
-    if ((rc = within_compact(ctx, a, d_mask, d_cnt, d_off, cand))) return rc;
-    const uint64_t n_cand = cand.size();
-    if (n_candidates) *n_candidates = n_cand;
-
-    // exact: the host arithmetic of lash_dist_rows, pair by pair, in row-major order (so the first refused pair is the one it reports)
-    uint64_t kept = 0;
-    for (const WithinPair &w : cand) {
-        const uint32_t row = r0 + w.row;
-        double ec, d;
-        const double *ecp = nullptr;
-        if (algo == LASH_HMH && !std::isnan(w.ec_x)) { ec = hmh_ec_from_cell_sum(w.ec_x); ecp = &ec; }
-        if (!dist_pair_host(algo, ref->p, k, model, fp32, ref->card[row], qry->card[w.col], w.c_or_zero, w.n, w.sum_or_union, tables, ecp, &d)) {
-            if (bad_pair) *bad_pair = (uint64_t)w.row * n_cols + w.col;
-            *n_kept = kept;
-            return LASH_ERANGE;
-        }
-        if (!(d <= max_dist)) continue;
-        if (kept < cap) { out_row[kept] = row; out_col[kept] = w.col; out_dist[kept] = d; }
-        ++kept;
-    }
-    *n_kept = kept;
-    return LASH_OK;
+    if ((rc = within_compact(ctx, b.a, b.d_mask, b.d_cnt, b.d_off, cand))) return rc;
+    if (n_candidates) *n_candidates = cand.size();
+    KeptRows kept{out_row, out_col, out_dist, cap, 0};
+    rc = filter_evaluate(cand, ref, r0, qry, n_cols, k, model, fp32, tables, bad_pair, [&](uint32_t row, uint32_t col, double d, uint32_t) {
+        if (d <= max_dist) kept.add(row, col, d);
+    });
+    *n_kept = kept.n;
+    return rc;
 }
 
 }  // extern "C"

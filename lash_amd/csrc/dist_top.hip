@@ -8,17 +8,12 @@
 // of a triangle run.  NaN is never ranked.
 //
 // Passes over a block of rows [r0, r1) x columns [0, n_cols):
-//   key      per pair an interval [lo, hi] that holds the host's exact d, as two order-preserving 32-bit keys (hi rounded up, lo
-//            rounded down to float, so that the interval only widens).  The general case is d_dev -/+ the margin of dist_filter.hip
-//            (2^-40, 2^-16 under fp32; the same HLL linear-counting handling, pair_distance_dev), hi capped at 1 (the host's d never
-//            exceeds 1: min(.., 1) / 1 - pow(f, 1/k) with f >= 0).  EXACT pairs have lo = hi = d and an even hi key (general
-//            pairs: odd, key | 1, which only rounds up):
-//              similarity <= 0 -> d = 1.0, both models, f64 and f32.  The similarity is bit-identical on both sides except under HLL
-//                linear counting, where the device's is never below the host's (dist_filter.hip): host similarity <= 0 as well;
-//              the row's same-name column (same_col) -> d = 0 (printed 0).  Still sent to the host, which must see it for LASH_ERANGE.
-//            Pairs the device cannot place (the HLL++ bias-table regime, a linear-counting estimate at the threshold) take no part
-//            in the selection and are always candidates.  A NaN distance: never a candidate for hmh / ull, whose similarity is
-//            bit-identical on the host and whose NaN propagates the same way through log / pow; under HLL it is always a candidate.
+//   key      per pair the interval [lo, hi] of pair_interval_dev (dist_filter.h), which holds the host's exact d, as two
+//            order-preserving 32-bit keys (hi rounded up, lo rounded down to float, so that the interval only widens).  EXACT pairs
+//            have lo = hi = d and an even hi key (general pairs: odd, key | 1, which only rounds up): PAIR_ONE (d = 1.0), and the
+//            row's same-name column (same_col) -> d = 0 (printed 0), still sent to the host, which must see it for LASH_ERANGE.
+//            Pairs the device cannot place take no part in the selection and are always candidates.  PAIR_NAN: never a candidate
+//            for hmh / ull, always one under HLL.
 //   select   per column (and, in a triangle block, per row) the K-th smallest hi key Tk over the block: a radix select, four 8-bit
 //            digits, histograms in LDS.  If Tk is odd, T = (decode(Tk), +inf, +inf); if it is even (exact), T = (decode(Tk), the
 //            position of the rank-th pair with that key).  Fewer than K placed pairs: T = +inf.
@@ -89,7 +84,7 @@ struct TopArgs {
     const uint32_t *same_col;                     // [nr] or null
     uint32_t *hi, *lo;                            // [nr][n_cols]
     const TopKey *fc, *fr;                        // combined cutoffs: [n_cols], [nr] (triangle)
-    double margin, max_dist;                      // max_dist NaN: none
+    double max_dist;                              // NaN: none
     uint32_t r0;
 };
 
@@ -100,17 +95,19 @@ __global__ void __launch_bounds__(256) top_key_kernel(WithinArgs a, TopArgs t)
     for (uint32_t r = blockIdx.y; r < a.nr; r += gridDim.y) {
         const uint64_t at = (uint64_t)r * a.n_cols + q;
         uint32_t hi, lo;
-        double sim, d;
+        double sim, sim_low, d_lo, d_hi;
         if (q >= row_end(a, r)) { hi = KEY_NONE; lo = LO_NEVER; }                       // above the diagonal: not printed
         else if (t.same_col && t.same_col[r] == q) { hi = ord(0.0f); lo = LO_ALWAYS; }   // prints 0; the host still evaluates it
-        else if (!pair_distance_dev(a, r, q, &sim, &d)) { hi = KEY_NONE; lo = LO_ALWAYS; }
-        else if (sim <= 0.0) hi = lo = ord(1.0f);                                       // exact: d = 1 on both sides
-        else if (d != d) { hi = KEY_NONE; lo = a.algo == LASH_HLL ? LO_ALWAYS : LO_NEVER; }
-        else {
-            float h = float_up(fmin(d + t.margin, 1.0));
+        else if (!pair_similarity_dev(a, r, q, &sim, &sim_low)) { hi = KEY_NONE; lo = LO_ALWAYS; }
+        else switch (pair_interval_dev(a, sim, sim_low, &d_lo, &d_hi)) {
+        case PAIR_ONE: hi = lo = ord(1.0f); break;                                      // exact
+        case PAIR_NAN: hi = KEY_NONE; lo = a.algo == LASH_HLL ? LO_ALWAYS : LO_NEVER; break;
+        default: {
+            float h = float_up(d_hi);
             if (h == 0.0f) h = 0.0f;                                                    // -0 -> +0: no odd key decodes to 0
             hi = ord(h) | 1u;
-            lo = ord(float_down(d - t.margin));
+            lo = ord(float_down(d_lo));
+        }
         }
         t.hi[at] = hi;
         t.lo[at] = lo;
@@ -281,41 +278,17 @@ __device__ inline bool top_pass(uint32_t hi, uint32_t lo, uint32_t row, uint32_t
     return d < t.d || (d == t.d && (row < t.row || (row == t.row && col <= t.col)));
 }
 
-__device__ bool top_candidate(const WithinArgs &a, const TopArgs &t, uint32_t r, uint32_t q)
-{
-    const uint64_t at = (uint64_t)r * a.n_cols + q;
-    const uint32_t lo = t.lo[at];
-    if (lo == LO_ALWAYS) return true;
-    if (lo == LO_NEVER) return false;
-    const uint32_t hi = t.hi[at];
-    if (!(t.max_dist != t.max_dist) && !((double)unord((hi & 1u) ? lo : hi) <= t.max_dist)) return false;
-    return top_pass(hi, lo, t.r0 + r, q, t.fc[q]) || (a.tri >= 0 && top_pass(hi, lo, t.r0 + r, q, t.fr[r]));
-}
-
-// the mask layout of within_mark_kernel (dist_filter.hip), for its scan and write kernels
 __global__ void __launch_bounds__(256) top_mark_kernel(WithinArgs a, TopArgs t, uint64_t *__restrict__ mask, uint32_t *__restrict__ tile_count)
 {
-    __shared__ uint32_t wsum[4];
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    for (uint64_t tile = blockIdx.x; tile < a.n_tiles; tile += gridDim.x) {
-        const uint32_t r = (uint32_t)(tile / a.tiles_x), c0 = (uint32_t)(tile % a.tiles_x) * WF_TILE, c_end = row_end(a, r);
-        if (c0 >= c_end) {
-            if (threadIdx.x == 0) tile_count[tile] = 0;
-            continue;
-        }
-        uint32_t cnt = 0;
-        for (uint32_t step = 0; step < 4; ++step) {
-            const uint32_t word = step * 4u + wave, q = c0 + word * 64u + lane;
-            const bool keep = q < c_end && top_candidate(a, t, r, q);
-            const uint64_t bits = __ballot(keep);
-            if (lane == 0) mask[tile * WF_WORDS + word] = bits;
-            cnt += (uint32_t)__popcll(bits);
-        }
-        if (lane == 0) wsum[wave] = cnt;
-        __syncthreads();
-        if (threadIdx.x == 0) tile_count[tile] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
-        __syncthreads();
-    }
+    mark_tiles(a, mask, tile_count, [&](uint32_t r, uint32_t q) {
+        const uint64_t at = (uint64_t)r * a.n_cols + q;
+        const uint32_t lo = t.lo[at];
+        if (lo == LO_ALWAYS) return true;
+        if (lo == LO_NEVER) return false;
+        const uint32_t hi = t.hi[at];
+        if (!(t.max_dist != t.max_dist) && !((double)unord((hi & 1u) ? lo : hi) <= t.max_dist)) return false;
+        return top_pass(hi, lo, t.r0 + r, q, t.fc[q]) || (a.tri >= 0 && top_pass(hi, lo, t.r0 + r, q, t.fr[r]));
+    });
 }
 
 }  // namespace lash
@@ -365,19 +338,13 @@ int lash_sketch_set_pair_block_top(lash_ctx *ctx, const lash_sketch_set *ref, ui
     static_assert(sizeof(TopKey) == sizeof(lash_top_key), "lash_top_key layout");
     if (n_kept) *n_kept = 0;
     if (n_candidates) *n_candidates = 0;
-    if (!ctx || !ref || !qry || !n_kept || r0 > r1 || r1 > ref->n || n_cols > qry->n || k < 1 || k > 32 || (model != 0 && model != 1))
-        return LASH_EINVAL;
-    if (top_k < 1 || top_k > LASH_TOP_MAX || (cap && (!out_row || !out_col || !out_dist))) return LASH_EINVAL;
-    if (ref->card.size() != ref->n || qry->card.size() != qry->n) return LASH_EINVAL;          // lash_sketch_set_cardinalities first
-    const uint32_t nr = r1 - r0;
-    if (nr == 0 || n_cols == 0) return LASH_OK;
-    (void)hipSetDevice(ctx->device);
+    if (!n_kept || top_k < 1 || top_k > LASH_TOP_MAX || (cap && (!out_row || !out_col || !out_dist))) return LASH_EINVAL;
     int rc;
-    const int algo = ref->algo;
-    const uint64_t np = (uint64_t)nr * n_cols;
-    WithinBlock b;                                                                             // the statistics and scratch, as pair_block_within
-    if ((rc = within_block(ctx, ref, r0, r1, qry, n_cols, triangle, k, model, fp32, ull_estimator, b))) return rc;
+    WithinBlock b;
+    if ((rc = within_block(ctx, ref, r0, r1, qry, n_cols, triangle, k, model, fp32, ull_estimator, b)) || !b.a.n_tiles) return rc;
     const WithinArgs &a = b.a;
+    const uint32_t nr = r1 - r0;
+    const uint64_t np = (uint64_t)nr * n_cols;
 
     // selection buffers: [hi u32 (np) | lo u32 (np) | tc, fc, col_bound (n_cols) | tr, fr, row_bound (nr) TopKey | same_col u32 (nr)]
     const uint64_t nk = 3 * (uint64_t)n_cols + 3 * (uint64_t)nr;
@@ -392,7 +359,6 @@ int lash_sketch_set_pair_block_top(lash_ctx *ctx, const lash_sketch_set *ref, ui
     TopArgs t{};
     t.same_col = same_col ? d_same : nullptr;
     t.hi = d_hi; t.lo = d_lo; t.fc = d_fc; t.fr = d_fr;
-    t.margin = fp32 ? 0x1p-16 : 0x1p-40;                                                       // dist_filter.hip
     t.max_dist = max_dist;
     t.r0 = r0;
     const uint32_t gx = (n_cols + 255) / 256;
@@ -409,35 +375,20 @@ int lash_sketch_set_pair_block_top(lash_ctx *ctx, const lash_sketch_set *ref, ui
                        triangle && row_bound ? d_rb : nullptr, nr, n_cols, r0, triangle ? 1 : 0, d_fc, d_fr);
     HIPCHK(ctx, hipGetLastError());
 
-    const uint64_t nt = a.n_tiles;
-    uint64_t *d_off = b.d_off, *d_mask = b.d_mask;
-    uint32_t *d_cnt = b.d_cnt;
-    hipLaunchKernelGGL(top_mark_kernel, dim3((uint32_t)std::min<uint64_t>(nt, 1u << 20)), dim3(256), 0, ctx->stream, a, t, d_mask, d_cnt);
+    hipLaunchKernelGGL(top_mark_kernel, dim3(mark_grid(a.n_tiles)), dim3(256), 0, ctx->stream, a, t, b.d_mask, b.d_cnt);
     HIPCHK(ctx, hipGetLastError());
     std::vector<WithinPair> cand;
-    if ((rc = within_compact(ctx, a, d_mask, d_cnt, d_off, cand))) return rc;
+    if ((rc = within_compact(ctx, a, b.d_mask, b.d_cnt, b.d_off, cand))) return rc;
     if (n_candidates) *n_candidates = cand.size();
 
-    // exact: the host arithmetic of lash_dist_rows in row-major order (the first refused pair is the one it reports), then the
-    // same-name rule, NaN dropped, d <= max_dist
-    uint64_t kept = 0;
-    for (const WithinPair &w : cand) {
-        const uint32_t row = r0 + w.row;
-        double ec, d;
-        const double *ecp = nullptr;
-        if (algo == LASH_HMH && !std::isnan(w.ec_x)) { ec = hmh_ec_from_cell_sum(w.ec_x); ecp = &ec; }
-        if (!dist_pair_host(algo, ref->p, k, model, fp32, ref->card[row], qry->card[w.col], w.c_or_zero, w.n, w.sum_or_union, tables, ecp, &d)) {
-            if (bad_pair) *bad_pair = (uint64_t)w.row * n_cols + w.col;
-            *n_kept = kept;
-            return LASH_ERANGE;
-        }
-        if (same_col && same_col[w.row] == w.col) d = 0.0;
-        if (std::isnan(d) || (!std::isnan(max_dist) && !(d <= max_dist))) continue;
-        if (kept < cap) { out_row[kept] = row; out_col[kept] = w.col; out_dist[kept] = d; }
-        ++kept;
-    }
-    *n_kept = kept;
-    return LASH_OK;
+    // the same-name rule, NaN dropped, d <= max_dist
+    KeptRows kept{out_row, out_col, out_dist, cap, 0};
+    rc = filter_evaluate(cand, ref, r0, qry, n_cols, k, model, fp32, tables, bad_pair, [&](uint32_t row, uint32_t col, double d, uint32_t block_row) {
+        if (same_col && same_col[block_row] == col) d = 0.0;
+        if (!std::isnan(d) && (std::isnan(max_dist) || d <= max_dist)) kept.add(row, col, d);
+    });
+    *n_kept = kept.n;
+    return rc;
 }
 
 int lash_top_create(uint32_t n_names, uint32_t top_k, int triangle, lash_top **out)

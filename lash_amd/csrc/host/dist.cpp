@@ -32,7 +32,6 @@
 
 #include <algorithm>
 #include <atomic>
-#include <charconv>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -44,7 +43,6 @@
 #include <sstream>
 #include <numeric>
 #include <thread>
-#include <unordered_map>
 #include <vector>
 
 #include "../../../include/lash_gfx950.h"
@@ -95,16 +93,34 @@ std::string slurp(const std::string &path, std::string &out)
     return "";
 }
 
-}  // namespace
+const char *const BIAS_MSG = ": cardinality estimate <= 5 * 2^p needs the HLL++ bias tables of streaming_algorithms, which are "
+                             "not built in (pass --hll-bias <file from tools/ref_probe/extract_hll_bias.py>, or sketch with a smaller -p)";
 
-std::string run_dist(const DistOptions &opt)
+// LASH_CLI_TIMING: where the wall time of a run goes
+struct Timing {
+    const bool on = getenv("LASH_CLI_TIMING") != nullptr;
+    const std::chrono::steady_clock::time_point t_start = std::chrono::steady_clock::now();
+    void mark(const char *what) const { if (on) fprintf(stderr, "[lash dist] %7.3f s  %s\n", std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count(), what); }
+};
+
+// what a run reads from its two sketch-file sets, checked
+struct DistInput {
+    int k = 0, algo_id = 0, prec = 0, ull_est = LASH_ULL_FGRA;
+    bool same_files = false, same_sketches = false;                  // the same name file (main.rs:404); one sketch file, read once
+    std::vector<std::string> rnames, qnames;                         // the name files
+    std::vector<uint32_t> rorder, qorder;                            // the maps' key order: the rows / columns, as indices into the name files
+    std::vector<uint8_t> rimg_store, qimg_store;
+    uint32_t nr = 0, nq = 0;
+    std::vector<std::string> row_name, col_name, col_tab;
+    std::vector<uint32_t> row_id, col_id;                            // "q_name == r_name prints 0" (main.rs:452-453) as an integer compare per pair
+    std::vector<uint32_t> same_col;                                  // --max-dist / --top: the column carrying each row's name, or NO_COLUMN
+    const std::vector<uint8_t> &rimg() const { return rimg_store; }
+    const std::vector<uint8_t> &qimg() const { return same_sketches ? rimg_store : qimg_store; }
+    bool one_set() const { return same_sketches && same_files; }     // the same images in the same order: one set is both sides
+};
+
+std::string load_input(const DistOptions &opt, const Timing &timing, DistInput &in)
 {
-    // LASH_CLI_TIMING: where the wall time of a run goes
-    const bool timing = getenv("LASH_CLI_TIMING") != nullptr;
-    const auto t_start = std::chrono::steady_clock::now();
-    auto mark = [&](const char *what) {
-        if (timing) fprintf(stderr, "[lash dist] %7.3f s  %s\n", std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count(), what);
-    };
     std::map<std::string, std::string> rf, qf;
     std::string err = find_files(opt.ref_prefix, rf);
     if (err.empty()) err = find_files(opt.query_prefix, qf);
@@ -118,66 +134,362 @@ std::string run_dist(const DistOptions &opt)
     const std::string algo = rp["algorithm"];
     if ((algo == "ull" || algo == "hll") && rp["precision"] != qp["precision"])
         return algo + " was not sketched with same precision btwn genomes";
-    const int k = atoi(rp["k"].c_str());
+    in.k = atoi(rp["k"].c_str());
     if (opt.model != 0 && opt.model != 1) return "model needs to be 0 or 1";
     const bool hll = algo == "hll", ull = algo == "ull";
     if (!hll && !ull && algo != "hmh") return "Algorithm must be either hmh, ull, or hll";
-    int ull_est = LASH_ULL_FGRA;
     if (ull) {                                                                                        // utils.rs:213-217
-        if (opt.estimator == "ml") ull_est = LASH_ULL_ML;
+        if (opt.estimator == "ml") in.ull_est = LASH_ULL_ML;
         else if (opt.estimator != "fgra") return "estimator needs to be either fgra or ml";
     }
-    std::vector<std::string> rnames, qnames;
-    if (!(err = slurp(rf["files"], txt)).empty() || !json_parse_string_array(txt, rnames)) return err.empty() ? "bad names JSON " + rf["files"] : err;
-    if (!(err = slurp(qf["files"], txt)).empty() || !json_parse_string_array(txt, qnames)) return err.empty() ? "bad names JSON " + qf["files"] : err;
-    const bool same_files = qf["files"] == rf["files"];                                               // main.rs:404
-    if (opt.has_cluster && !(same_files && rf["sketches"] == qf["sketches"]))
+    if (!(err = slurp(rf["files"], txt)).empty() || !json_parse_string_array(txt, in.rnames)) return err.empty() ? "bad names JSON " + rf["files"] : err;
+    if (!(err = slurp(qf["files"], txt)).empty() || !json_parse_string_array(txt, in.qnames)) return err.empty() ? "bad names JSON " + qf["files"] : err;
+    in.same_files = qf["files"] == rf["files"];                                                       // main.rs:404
+    in.same_sketches = rf["sketches"] == qf["sketches"];                                              // all-vs-all: one file, read once
+    if (opt.has_cluster && !(in.same_files && in.same_sketches))
         return "--cluster needs an all-vs-all run: -q and -r must name the same sketch files";
     // utils.rs:111-127: the maps' key order (a repeated name is one entry carrying its last sketch)
-    std::vector<uint32_t> rorder, qorder;
     if (opt.file_order) {
-        rorder.resize(rnames.size()); std::iota(rorder.begin(), rorder.end(), 0u);
-        qorder.resize(qnames.size()); std::iota(qorder.begin(), qorder.end(), 0u);
+        in.rorder.resize(in.rnames.size()); std::iota(in.rorder.begin(), in.rorder.end(), 0u);
+        in.qorder.resize(in.qnames.size()); std::iota(in.qorder.begin(), in.qorder.end(), 0u);
     } else {
-        rorder = hashbrown_key_order(rnames);
-        qorder = same_files ? rorder : hashbrown_key_order(qnames);
+        in.rorder = hashbrown_key_order(in.rnames);
+        in.qorder = in.same_files ? in.rorder : hashbrown_key_order(in.qnames);
     }
 
-    std::vector<uint8_t> rimg_store, qimg_store;
-    if (!(err = zstd_decompress_file(rf["sketches"], rimg_store)).empty()) return err;
-    const bool same_sketches = rf["sketches"] == qf["sketches"];                   // all-vs-all: one file, read once
-    if (!same_sketches && !(err = zstd_decompress_file(qf["sketches"], qimg_store)).empty()) return err;
-    const std::vector<uint8_t> &rimg = rimg_store, &qimg = same_sketches ? rimg_store : qimg_store;
-    mark("sketch files read and inflated");
-    const int algo_id = hll ? LASH_HLL : ull ? LASH_ULL : LASH_HMH;
-    const int prec = (hll || ull) ? atoi(rp["precision"].c_str()) : 0;
-    if (hll && (prec < 4 || prec > 16)) return "bad precision in " + rf["params"];
-    if (ull && (prec < 3 || prec > 26)) return "bad precision in " + rf["params"];
-    const size_t ib = lash_layout_image_bytes(&opt.layout, algo_id, prec);
+    if (!(err = zstd_decompress_file(rf["sketches"], in.rimg_store)).empty()) return err;
+    if (!in.same_sketches && !(err = zstd_decompress_file(qf["sketches"], in.qimg_store)).empty()) return err;
+    timing.mark("sketch files read and inflated");
+    in.algo_id = hll ? LASH_HLL : ull ? LASH_ULL : LASH_HMH;
+    in.prec = (hll || ull) ? atoi(rp["precision"].c_str()) : 0;
+    if (hll && (in.prec < 4 || in.prec > 16)) return "bad precision in " + rf["params"];
+    if (ull && (in.prec < 3 || in.prec > 26)) return "bad precision in " + rf["params"];
+    const size_t ib = lash_layout_image_bytes(&opt.layout, in.algo_id, in.prec);
     if (!ib) return "bad layout";
-    if (rimg.size() < rnames.size() * ib) return "Error with reading from " + rf["sketches"];
-    if (qimg.size() < qnames.size() * ib) return "Error with reading from " + qf["sketches"];
+    if (in.rimg().size() < in.rnames.size() * ib) return "Error with reading from " + rf["sketches"];
+    if (in.qimg().size() < in.qnames.size() * ib) return "Error with reading from " + qf["sketches"];
     // rows / columns: the ENTRIES of the two maps in key order (a repeated name is one entry carrying its last sketch,
     // utils.rs:111-127) — everything below is indexed by position in rorder / qorder, never by name-file index
-    const uint32_t nr = (uint32_t)rorder.size(), nq = (uint32_t)qorder.size();
-    std::vector<std::string> row_name(nr), col_name(nq);
-    for (uint32_t i = 0; i < nr; ++i) row_name[i] = rnames[rorder[i]];
-    for (uint32_t j = 0; j < nq; ++j) col_name[j] = qnames[qorder[j]];
-    // "q_name == r_name prints 0" (main.rs:452-453) as an integer compare per pair
-    std::vector<uint32_t> row_id, col_id;
-    name_ids(row_name, col_name, row_id, col_id);
-    const std::vector<std::string> col_tab = opt.matrix ? std::vector<std::string>() : tabbed_names(col_name);
-    // --max-dist / --top: the column carrying each row's name (a name is one entry per side, so at most one), found once — those pairs print 0
-    std::vector<uint32_t> same_col;
+    const uint32_t nr = in.nr = (uint32_t)in.rorder.size(), nq = in.nq = (uint32_t)in.qorder.size();
+    in.row_name.resize(nr); in.col_name.resize(nq);
+    for (uint32_t i = 0; i < nr; ++i) in.row_name[i] = in.rnames[in.rorder[i]];
+    for (uint32_t j = 0; j < nq; ++j) in.col_name[j] = in.qnames[in.qorder[j]];
+    name_ids(in.row_name, in.col_name, in.row_id, in.col_id);
+    if (!opt.matrix) in.col_tab = tabbed_names(in.col_name);
+    // a name is one entry per side, so at most one column carries a row's name; found once — those pairs print 0
     if (opt.has_max_dist || opt.top) {
-        std::vector<uint32_t> col_of(row_name.size() + col_name.size(), NO_COLUMN);
-        for (uint32_t j = 0; j < nq; ++j) col_of[col_id[j]] = j;
-        same_col.resize(nr);
-        for (uint32_t i = 0; i < nr; ++i) same_col[i] = col_of[row_id[i]];
+        std::vector<uint32_t> col_of(in.row_name.size() + in.col_name.size(), NO_COLUMN);
+        for (uint32_t j = 0; j < nq; ++j) col_of[in.col_id[j]] = j;
+        in.same_col.resize(nr);
+        for (uint32_t i = 0; i < nr; ++i) in.same_col[i] = col_of[in.row_id[i]];
+    }
+    return "";
+}
+
+// The sketches go to every device ONCE (lash_sketch_set: images + what the pair kernels derive from them), in map order; per-sketch
+// cardinalities (utils.rs:101-103, 213-217, 314-315) come from register histograms made on the GPU.
+struct DevSets { int device = 0; lash_ctx *ctx = nullptr; lash_sketch_set *ref = nullptr, *qry = nullptr; };
+struct DeviceSets {
+    std::vector<DevSets> sets;
+    std::vector<double> rcard, qcard;                                // (one set: qcard is a copy of rcard)
+    ~DeviceSets()
+    {
+        for (DevSets &d : sets) {
+            if (d.qry && d.qry != d.ref) lash_sketch_set_free(d.ctx, d.qry);
+            if (d.ref) lash_sketch_set_free(d.ctx, d.ref);
+            if (d.ctx) lash_ctx_destroy(d.ctx);
+        }
+    }
+    const DevSets *on(int device) const { for (const DevSets &d : sets) if (d.device == device) return &d; return nullptr; }
+};
+
+std::string make_device_sets(const DistOptions &opt, const DistInput &in, const std::vector<int> &devices, const lash_hll_bias *bias, DeviceSets &dev)
+{
+    const bool one_set = in.one_set();
+    dev.rcard.resize(in.nr);
+    for (int dv : devices) {
+        if (dev.on(dv)) continue;
+        dev.sets.emplace_back();
+        DevSets &d = dev.sets.back();
+        d.device = dv;
+        int rc = lash_ctx_create(&d.ctx, dv);
+        if (rc == LASH_OK) rc = lash_ctx_set_layout(d.ctx, &opt.layout);
+        if (rc == LASH_OK)
+            rc = lash_sketch_set_create(d.ctx, in.algo_id, in.prec, in.rimg().data(), (uint32_t)in.rnames.size(), in.rorder.data(), in.nr, &d.ref);
+        if (rc == LASH_OK) {
+            if (one_set) d.qry = d.ref;
+            else rc = lash_sketch_set_create(d.ctx, in.algo_id, in.prec, in.qimg().data(), (uint32_t)in.qnames.size(), in.qorder.data(), in.nq, &d.qry);
+        }
+        // (every device computes its sets' cardinalities: the sets keep them for the expected-collision vectors)
+        uint32_t bad = 0;
+        if (rc == LASH_OK) {
+            rc = lash_sketch_set_cardinalities(d.ctx, d.ref, in.ull_est, bias, dev.rcard.data(), &bad);
+            if (rc == LASH_ERANGE) return in.row_name[bad] + BIAS_MSG;
+        }
+        if (rc == LASH_OK && !one_set) {
+            dev.qcard.resize(in.nq);
+            rc = lash_sketch_set_cardinalities(d.ctx, d.qry, in.ull_est, bias, dev.qcard.data(), &bad);
+            if (rc == LASH_ERANGE) return in.col_name[bad] + BIAS_MSG;
+        }
+        if (rc == LASH_OK) rc = lash_sketch_set_prepare(d.ctx, d.ref, d.qry);
+        if (rc != LASH_OK) return std::string(lash_strerror(rc)) + " " + lash_ctx_last_error(d.ctx);
+    }
+    if (one_set) dev.qcard = dev.rcard;
+    return "";
+}
+
+// Blocks of reference rows [begin[b], begin[b + 1]): bounded pair tables (all-vs-all on 10^5 sketches is 5 * 10^9 printed pairs), about
+// the same number of PRINTED pairs each — with same files row i prints i + 1 columns, so late blocks hold fewer rows.
+std::vector<uint32_t> plan_blocks(const DistOptions &opt, const DistInput &in)
+{
+    const uint32_t nr = in.nr, nq = in.nq;
+    std::vector<uint32_t> begin{0};
+    const uint64_t total = in.same_files ? (uint64_t)nr * (nr + 1) / 2 : (uint64_t)nr * nq;
+    const uint64_t want = opt.block_rows ? 0 : std::max<uint64_t>(std::min<uint64_t>(32ull << 20, total / 16 + 1), 4096);   // pairs per block, >= ~16 blocks
+    uint64_t acc = 0;
+    for (uint32_t i = 0; i < nr; ++i) {
+        acc += in.same_files ? i + 1 : nq;
+        const bool cut = opt.block_rows ? (i + 1 - begin.back()) >= opt.block_rows : acc >= want;
+        if (cut && i + 1 < nr) { begin.push_back(i + 1); acc = 0; }
+    }
+    if (nr) begin.push_back(nr);
+    return begin;
+}
+
+// what the workers of a run share
+struct Run {
+    const DistOptions &opt;
+    const DistInput &in;
+    const DeviceSets &dev;
+    const lash_hll_bias *bias;
+    const Timing &timing;
+    std::vector<int> devices;                                    // one worker each
+    std::vector<uint32_t> block_begin;
+    bool gpu_ec = false;
+    int fmt_threads = 1;
+    FILE *out = nullptr;
+    std::atomic<uint32_t> next_block{0};
+    std::mutex wmu;
+    std::condition_variable wcv;
+    uint32_t next_to_write = 0;
+    std::string fail;                                            // guarded by wmu
+    // --top: per worker, the lists of the K nearest of every name (the columns; in a triangle run the set) from the blocks it ran
+    std::vector<lash_top *> tops;
+    std::atomic<uint64_t> top_candidates{0};                     // (LASH_CLI_TIMING: what the device passed to the host)
+    // --cluster: per worker, the clusters joined by the blocks it ran (created by the worker: the labels live on its device)
+    std::vector<lash_cluster *> clusters;
+    std::atomic<uint64_t> cl_pairs{0}, cl_pruned{0}, cl_joined{0}, cl_sent{0};   // (LASH_CLI_TIMING)
+    ~Run() { for (lash_top *p : tops) lash_top_free(p); for (lash_cluster *p : clusters) lash_cluster_free(p); if (out) fclose(out); }
+};
+
+struct Block { uint32_t i0, i1, n_cols; };
+
+// one worker: its own context (stream and staging; the sets are shared, read-only) and the buffers it reuses from block to block
+struct Worker {
+    Run &run;
+    const DistOptions &opt;
+    const DistInput &in;
+    const size_t wi;
+    const DevSets *ds;
+    lash_ctx *ctx = nullptr;
+    // the unfiltered run's pair tables in page-locked memory (the copy back runs at the link rate): hmh C / N; hll zero + sum; ull the union estimate
+    uint32_t *C = nullptr, *N = nullptr;
+    double *U = nullptr, *EC = nullptr;
+    size_t cap = 0, ec_cap = 0;
+    RowText row_text;                                            // the block's text
+    std::vector<uint32_t> w_row, w_col;                          // --max-dist / --top: the block's survivors
+    std::vector<double> w_dist;
+    std::vector<lash_top_key> col_bound, row_bound;              // --top: this worker's K-th key per name, for the next block
+    Worker(Run &r, size_t i) : run(r), opt(r.opt), in(r.in), wi(i), ds(r.dev.on(r.devices[i])) {}
+    ~Worker() { lash_host_free_pinned(C); lash_host_free_pinned(N); lash_host_free_pinned(U); lash_host_free_pinned(EC); if (ctx) lash_ctx_destroy(ctx); }
+
+    // The failure text of a block whose library call returned rc; `bad`: the refused pair's place in the block (LASH_ERANGE).
+    std::string block_failure(const Block &b, int rc, uint64_t bad = 0) const
+    {
+        if (rc == LASH_OK) return "";
+        if (rc == LASH_ERANGE) return "union of " + in.row_name[b.i0 + bad / b.n_cols] + " and " + in.col_name[bad % b.n_cols] + BIAS_MSG;
+        return std::string(lash_strerror(rc)) + " " + lash_ctx_last_error(ctx);
     }
 
-    const char *bias_msg = ": cardinality estimate <= 5 * 2^p needs the HLL++ bias tables of streaming_algorithms, which are "
-                           "not built in (pass --hll-bias <file from tools/ref_probe/extract_hll_bias.py>, or sketch with a smaller -p)";
+    // --max-dist / --top: entry(cap) fills the survivor buffers and sets *kept to the full count; again with larger ones until all rows fit
+    template <class Entry>
+    int kept_rows(uint64_t *kept, Entry entry)
+    {
+        if (w_row.empty()) { w_row.resize(1u << 16); w_col.resize(1u << 16); w_dist.resize(1u << 16); }
+        for (;;) {
+            const int rc = entry(w_row.size());
+            if (rc != LASH_OK || *kept <= w_row.size()) return rc;
+            w_row.resize(*kept + *kept / 4); w_col.resize(w_row.size()); w_dist.resize(w_row.size());
+        }
+    }
+
+    // --top: pair statistics, expected collisions and the selection on the device; the survivors go to this worker's lists
+    std::string block_top(const Block &b)
+    {
+        lash_top *top = run.tops[wi];
+        uint64_t kept = 0, bad = 0, cand = 0;
+        col_bound.resize(b.n_cols);
+        row_bound.resize(b.i1 - b.i0);
+        lash_top_key *rb = in.same_files ? row_bound.data() : nullptr;
+        lash_top_bounds(top, b.i0, b.i1, b.n_cols, col_bound.data(), rb);
+        int rc = kept_rows(&kept, [&](uint64_t cap) {
+            return lash_sketch_set_pair_block_top(ctx, ds->ref, b.i0, b.i1, ds->qry, b.n_cols, in.same_files ? 1 : 0, in.k, opt.model, opt.fp32 ? 1 : 0,
+                                                  in.ull_est, run.bias, opt.top, opt.has_max_dist ? opt.max_dist : NAN, in.same_col.data() + b.i0,
+                                                  col_bound.data(), rb, w_row.data(), w_col.data(), w_dist.data(), cap, &kept, &bad, &cand);
+        });
+        run.top_candidates += cand;
+        if (rc == LASH_OK) rc = lash_top_add(top, w_row.data(), w_col.data(), w_dist.data(), kept);
+        return block_failure(b, rc, bad);
+    }
+
+    // --cluster: pair statistics, expected collisions and the joins on the device; the library links the pairs it could not decide
+    std::string block_cluster(const Block &b)
+    {
+        uint64_t bad = 0;
+        lash_cluster_stats cs;
+        const int rc = lash_sketch_set_pair_block_cluster(ctx, ds->ref, b.i0, b.i1, ds->qry, b.n_cols, in.k, opt.model, opt.fp32 ? 1 : 0, in.ull_est, run.bias,
+                                                          opt.cluster_dist, run.clusters[wi], &cs, &bad);
+        if (rc == LASH_OK) { run.cl_pairs += cs.pairs; run.cl_pruned += cs.pruned; run.cl_joined += cs.joined_on_device; run.cl_sent += cs.sent_to_host; }
+        return block_failure(b, rc, bad);
+    }
+
+    // --max-dist: pair statistics, expected collisions and the cutoff on the device; only the survivors come back
+    std::string block_within(const Block &b)
+    {
+        uint64_t kept = 0, bad = 0;
+        const int rc = kept_rows(&kept, [&](uint64_t cap) {
+            return lash_sketch_set_pair_block_within(ctx, ds->ref, b.i0, b.i1, ds->qry, b.n_cols, in.same_files ? 1 : 0, in.k, opt.model, opt.fp32 ? 1 : 0,
+                                                     in.ull_est, run.bias, opt.max_dist, w_row.data(), w_col.data(), w_dist.data(), cap, &kept,
+                                                     &bad, nullptr);
+        });
+        if (rc == LASH_OK)
+            format_block_within(b.i0, b.i1, in.same_files, in.nq, opt.max_dist, w_row.data(), w_col.data(), w_dist.data(), kept, in.same_col.data(),
+                                in.row_name, in.col_tab, row_text);
+        return block_failure(b, rc, bad);
+    }
+
+    // every pair: the pair tables come back and -t threads format them
+    std::string block_all(const Block &b)
+    {
+        const bool hll = in.algo_id == LASH_HLL, ull = in.algo_id == LASH_ULL;
+        const size_t np = (size_t)(b.i1 - b.i0) * b.n_cols;
+        if (np > cap) {
+            lash_host_free_pinned(C); lash_host_free_pinned(N); lash_host_free_pinned(U);
+            C = N = nullptr; U = nullptr;
+            cap = np + np / 8;
+            if (!ull) C = static_cast<uint32_t *>(lash_host_alloc_pinned(cap * 4));
+            if (!hll && !ull) N = static_cast<uint32_t *>(lash_host_alloc_pinned(cap * 4));
+            if (hll || ull) U = static_cast<double *>(lash_host_alloc_pinned(cap * 8));
+            if (!((ull || C) && (hll || ull || N) && (!(hll || ull) || U))) return "out of page-locked host memory";
+        }
+        int rc = lash_sketch_set_pair_block(ctx, ds->ref, b.i0, b.i1, ds->qry, b.n_cols, in.same_files ? 1 : 0, in.ull_est, C, N, U);
+        bool have_ec = false;
+        if (rc == LASH_OK && run.gpu_ec) {
+            // hyperminhash's expected_collisions below 2^19 distinct k-mers on both sides is a 65 536-cell sum — on the host
+            // 4 ms to 0.2 s per pair; the library does the block's small pairs as one matrix product on the GPU
+            if (np > ec_cap) { lash_host_free_pinned(EC); ec_cap = np + np / 8; EC = static_cast<double *>(lash_host_alloc_pinned(ec_cap * 8)); }
+            uint64_t n_small = 0;
+            rc = EC ? lash_sketch_set_hmh_expected_collisions(ctx, ds->ref, b.i0, b.i1, ds->qry, b.n_cols, EC, &n_small) : LASH_ENOMEM;
+            have_ec = n_small != 0;
+        }
+        if (rc != LASH_OK) return block_failure(b, rc);
+        BlockTables bt;
+        bt.c_or_zero = C; bt.n_counts = N; bt.sum_or_union = U; bt.hmh_ec = have_ec ? EC : nullptr; bt.ld = b.n_cols;
+        return dist_block_rows(in.algo_id, in.prec, in.k, opt.model, opt.fp32, run.bias, b.i0, b.i1, in.same_files, in.nq, run.dev.rcard.data(), run.dev.qcard.data(),
+                               bt, in.row_name, in.col_name, in.col_tab, in.row_id.data(), in.col_id.data(), opt.matrix, run.fmt_threads, row_text);
+    }
+
+    // Blocks in turn, each through its mode's step, written in block order whatever order the workers finish in.
+    void work()
+    {
+        int rc = lash_ctx_create(&ctx, run.devices[wi]);
+        if (rc == LASH_OK) rc = lash_ctx_set_layout(ctx, &opt.layout);
+        if (rc == LASH_OK && opt.has_cluster) rc = lash_cluster_create(ctx, in.nr, &run.clusters[wi]);
+        std::string my_fail = rc == LASH_OK ? "" : std::string(lash_strerror(rc));
+        const uint32_t n_blocks = (uint32_t)run.block_begin.size() - 1;
+        for (;;) {
+            const uint32_t blk = run.next_block.fetch_add(1);
+            if (blk >= n_blocks) break;
+            const uint32_t i0 = run.block_begin[blk], i1 = run.block_begin[blk + 1];
+            const Block b{i0, i1, in.same_files ? std::min(i1, in.nq) : in.nq};   // the triangle: no row of the block prints beyond its own column
+            bool skip;
+            { std::lock_guard<std::mutex> lk(run.wmu); skip = !run.fail.empty(); }
+            row_text.off.clear(); row_text.len.clear();
+            if (my_fail.empty() && !skip)
+                my_fail = opt.top ? block_top(b) : opt.has_cluster ? block_cluster(b) : opt.has_max_dist ? block_within(b) : block_all(b);
+            std::unique_lock<std::mutex> lk(run.wmu);
+            run.wcv.wait(lk, [&] { return run.next_to_write == blk; });
+            if (!my_fail.empty() && run.fail.empty()) run.fail = my_fail;
+            if (run.fail.empty())
+                for (size_t r = 0; r < row_text.rows(); ++r) fwrite(row_text.data(r), 1, row_text.size(r), run.out);
+            ++run.next_to_write;
+            lk.unlock();
+            run.wcv.notify_all();
+        }
+    }
+};
+
+// --top: the workers' lists merged, the kept pairs in (row, col) order through the --max-dist formatter (every pair passes; same-name
+// pairs are in the lists with d = 0 when they are among the K nearest)
+std::string finish_top(Run &run)
+{
+    const DistInput &in = run.in;
+    for (size_t w = 1; w < run.tops.size(); ++w)
+        if (lash_top_merge(run.tops[0], run.tops[w]) != LASH_OK) return "cannot merge the --top lists";
+    uint64_t n = 0;
+    std::vector<uint32_t> t_row, t_col;
+    std::vector<double> t_dist;
+    if (lash_top_result(run.tops[0], nullptr, nullptr, nullptr, 0, &n) == LASH_OK) {
+        t_row.resize(n); t_col.resize(n); t_dist.resize(n);
+        if (lash_top_result(run.tops[0], t_row.data(), t_col.data(), t_dist.data(), n, &n) != LASH_OK) return "cannot read the --top lists";
+    }
+    RowText text;
+    const std::vector<uint32_t> no_same(in.nr, NO_COLUMN);
+    format_block_within(0, in.nr, in.same_files, in.nq, HUGE_VAL, t_row.data(), t_col.data(), t_dist.data(), n, no_same.data(), in.row_name, in.col_tab, text);
+    for (size_t r = 0; r < text.rows(); ++r) fwrite(text.data(r), 1, text.size(r), run.out);
+    if (run.timing.on) fprintf(stderr, "[lash dist] --top: %llu candidates from the device, %llu rows kept\n",
+                               (unsigned long long)run.top_candidates.load(), (unsigned long long)n);
+    run.timing.mark("--top: the kept rows written");
+    return "";
+}
+
+// --cluster: the workers' clusters merged; every name under its cluster's first name, in row order
+std::string finish_cluster(Run &run)
+{
+    const DistInput &in = run.in;
+    const std::vector<lash_cluster *> &cl = run.clusters;
+    for (size_t w = 1; w < cl.size(); ++w)
+        if (!cl[0] || !cl[w] || lash_cluster_merge(cl[0], cl[w]) != LASH_OK) return "cannot merge the --cluster labels";
+    std::vector<uint32_t> label(in.nr);
+    if (in.nr && (!cl[0] || lash_cluster_labels(cl[0], label.data()) != LASH_OK)) return "cannot read the --cluster labels";
+    std::vector<uint32_t> by_rep(in.nr);
+    std::iota(by_rep.begin(), by_rep.end(), 0u);
+    std::stable_sort(by_rep.begin(), by_rep.end(), [&](uint32_t x, uint32_t y) { return label[x] < label[y]; });
+    std::string text;
+    uint64_t n_clusters = 0;
+    for (uint32_t i : by_rep) {
+        n_clusters += label[i] == i;
+        text.append(in.row_name[label[i]]).push_back('\t');
+        text.append(in.row_name[i]).push_back('\n');
+        if (text.size() >= (1u << 20)) { fwrite(text.data(), 1, text.size(), run.out); text.clear(); }
+    }
+    fwrite(text.data(), 1, text.size(), run.out);
+    if (run.timing.on) fprintf(stderr, "[lash dist] --cluster: %llu pairs looked at, %llu pruned as already joined, %llu joined on the device, "
+                               "%llu sent to the host, %llu clusters\n", (unsigned long long)run.cl_pairs.load(), (unsigned long long)run.cl_pruned.load(),
+                               (unsigned long long)run.cl_joined.load(), (unsigned long long)run.cl_sent.load(), (unsigned long long)n_clusters);
+    run.timing.mark("--cluster: the clusters written");
+    return "";
+}
+
+}  // namespace
+
+std::string run_dist(const DistOptions &opt)
+{
+    const Timing timing{};
+    DistInput in;
+    std::string err = load_input(opt, timing, in);
+    if (!err.empty()) return err;
+    const bool hll = in.algo_id == LASH_HLL, hmh = in.algo_id == LASH_HMH;
     lash_hll_bias *bias = nullptr;
     if (hll && !opt.hll_bias_file.empty()) {
         const int brc = lash_hll_bias_load(opt.hll_bias_file.c_str(), &bias);
@@ -185,274 +497,46 @@ std::string run_dist(const DistOptions &opt)
     }
     struct BiasGuard { lash_hll_bias *b; ~BiasGuard() { lash_hll_bias_free(b); } } bias_guard{bias};
 
-    // ---- the sketches go to every device ONCE (lash_sketch_set: images + what the pair kernels derive from them), in map order;
-    //      per-sketch cardinalities (utils.rs:101-103, 213-217, 314-315) come from register histograms made on the GPU ----
     // Without --devices, two workers share the GPU: while one formats and writes its block the other has the next block's
     // pair statistics computed (a block is GPU work, then -t threads of formatting, then an ordered write).
-    std::vector<int> devices = opt.devices.empty() ? std::vector<int>{opt.device, opt.device} : opt.devices;
-    struct DevSets { int device = 0; lash_ctx *ctx = nullptr; lash_sketch_set *ref = nullptr, *qry = nullptr; };
-    std::vector<DevSets> dev_sets;
-    auto free_sets = [&]() {
-        for (DevSets &d : dev_sets) {
-            if (d.qry && d.qry != d.ref) lash_sketch_set_free(d.ctx, d.qry);
-            if (d.ref) lash_sketch_set_free(d.ctx, d.ref);
-            if (d.ctx) lash_ctx_destroy(d.ctx);
-        }
-        dev_sets.clear();
-    };
-    struct SetsGuard { decltype(free_sets) &f; ~SetsGuard() { f(); } } sets_guard{free_sets};
-    const bool one_set = same_sketches && same_files;            // the same images in the same order: one set is both sides
-    std::vector<double> rcard(nr), qcard_store;
-    for (int dv : devices) {
-        bool seen = false;
-        for (const DevSets &d : dev_sets) seen = seen || d.device == dv;
-        if (seen) continue;
-        dev_sets.emplace_back();
-        DevSets &d = dev_sets.back();
-        d.device = dv;
-        int rc = lash_ctx_create(&d.ctx, dv);
-        if (rc == LASH_OK) rc = lash_ctx_set_layout(d.ctx, &opt.layout);
-        if (rc == LASH_OK) rc = lash_sketch_set_create(d.ctx, algo_id, prec, rimg.data(), (uint32_t)rnames.size(), rorder.data(), nr, &d.ref);
-        if (rc == LASH_OK) {
-            if (one_set) d.qry = d.ref;
-            else rc = lash_sketch_set_create(d.ctx, algo_id, prec, qimg.data(), (uint32_t)qnames.size(), qorder.data(), nq, &d.qry);
-        }
-        // (every device computes its sets' cardinalities: the sets keep them for the expected-collision vectors)
-        uint32_t bad = 0;
-        std::vector<double> qc(one_set ? 0 : nq);
-        if (rc == LASH_OK) {
-            rc = lash_sketch_set_cardinalities(d.ctx, d.ref, ull_est, bias, rcard.data(), &bad);
-            if (rc == LASH_ERANGE) return row_name[bad] + bias_msg;
-        }
-        if (rc == LASH_OK && !one_set) {
-            rc = lash_sketch_set_cardinalities(d.ctx, d.qry, ull_est, bias, qc.data(), &bad);
-            if (rc == LASH_ERANGE) return col_name[bad] + bias_msg;
-            qcard_store = qc;
-        }
-        if (rc == LASH_OK) rc = lash_sketch_set_prepare(d.ctx, d.ref, d.qry);
-        if (rc != LASH_OK) return std::string(lash_strerror(rc)) + " " + lash_ctx_last_error(d.ctx);
-    }
-    const std::vector<double> &qcard = one_set ? rcard : qcard_store;
-    mark("sketches resident on the device(s), cardinalities, pair-kernel operands");
+    DeviceSets dev;
+    Run run{opt, in, dev, bias, timing};
+    run.devices = opt.devices.empty() ? std::vector<int>{opt.device, opt.device} : opt.devices;
+    if (!(err = make_device_sets(opt, in, run.devices, bias, dev)).empty()) return err;
+    timing.mark("sketches resident on the device(s), cardinalities, pair-kernel operands");
     // hyperminhash's expected collisions need the GPU only when some pair has both sketches at or below 2^19 distinct k-mers
     bool small_ref = false, small_qry = false;
-    if (!hll && !ull) {
-        for (double c : rcard) small_ref = small_ref || !(c > 524288.0);
-        for (double c : qcard) small_qry = small_qry || !(c > 524288.0);
+    if (hmh) {
+        for (double c : dev.rcard) small_ref = small_ref || !(c > 524288.0);
+        for (double c : dev.qcard) small_qry = small_qry || !(c > 524288.0);
     }
-    const bool gpu_ec = small_ref && small_qry;
-    FILE *out = fopen(opt.output_file.c_str(), "w");
-    if (!out) return "cannot create " + opt.output_file;
-    if (opt.has_cluster) fprintf(out, "Representative\tMember\n");
-    else if (!opt.matrix) fprintf(out, "Reference\tQuery\tDistance\n");                              // main.rs:409-412
-    else for (uint32_t j = 0; j < nq; ++j) fprintf(out, "\t%s", col_name[j].c_str());                // main.rs:439-441
-    // ---- blocks of reference rows: bounded pair tables (all-vs-all on 10^5 sketches is 5 * 10^9 printed pairs), about the
-    //      same number of PRINTED pairs each — with same files row i prints i + 1 columns, so late blocks hold fewer rows ----
-    std::vector<uint32_t> block_begin{0};
-    {
-        const uint64_t total = same_files ? (uint64_t)nr * (nr + 1) / 2 : (uint64_t)nr * nq;
-        const uint64_t want = opt.block_rows ? 0 : std::max<uint64_t>(std::min<uint64_t>(32ull << 20, total / 16 + 1), 4096);   // pairs per block, >= ~16 blocks
-        uint64_t acc = 0;
-        for (uint32_t i = 0; i < nr; ++i) {
-            acc += same_files ? i + 1 : nq;
-            const bool cut = opt.block_rows ? (i + 1 - block_begin.back()) >= opt.block_rows : acc >= want;
-            if (cut && i + 1 < nr) { block_begin.push_back(i + 1); acc = 0; }
-        }
-        if (nr) block_begin.push_back(nr);
-    }
-    const uint32_t n_blocks = (uint32_t)block_begin.size() - 1;
-    if (devices.size() > n_blocks) devices.resize(std::max<uint32_t>(n_blocks, 1));
-    const int fmt_threads = std::max(1, opt.threads / (int)devices.size());
-    std::atomic<uint32_t> next_block{0};
-    std::mutex wmu;
-    std::condition_variable wcv;
-    uint32_t next_to_write = 0;
-    std::string fail;                                            // guarded by wmu
-    // --top: per worker, the lists of the K nearest of every name (the columns; in a triangle run the set) from the blocks it ran
-    std::vector<lash_top *> tops(devices.size(), nullptr);
-    std::atomic<uint64_t> top_candidates{0};                     // (LASH_CLI_TIMING: what the device passed to the host)
-    struct TopsGuard { std::vector<lash_top *> &t; ~TopsGuard() { for (lash_top *p : t) lash_top_free(p); } } tops_guard{tops};
+    run.gpu_ec = small_ref && small_qry;
+    run.out = fopen(opt.output_file.c_str(), "w");
+    if (!run.out) return "cannot create " + opt.output_file;
+    if (opt.has_cluster) fprintf(run.out, "Representative\tMember\n");
+    else if (!opt.matrix) fprintf(run.out, "Reference\tQuery\tDistance\n");                          // main.rs:409-412
+    else for (uint32_t j = 0; j < in.nq; ++j) fprintf(run.out, "\t%s", in.col_name[j].c_str());      // main.rs:439-441
+    run.block_begin = plan_blocks(opt, in);
+    const uint32_t n_blocks = (uint32_t)run.block_begin.size() - 1;
+    if (run.devices.size() > n_blocks) run.devices.resize(std::max<uint32_t>(n_blocks, 1));
+    run.fmt_threads = std::max(1, opt.threads / (int)run.devices.size());
+    run.tops.assign(run.devices.size(), nullptr);
+    run.clusters.assign(run.devices.size(), nullptr);
     if (opt.top)
-        for (lash_top *&t : tops)
-            if (lash_top_create(same_files ? nr : nq, opt.top, same_files ? 1 : 0, &t) != LASH_OK) return "cannot create the --top lists";
-
-    // --cluster: per worker, the clusters joined by the blocks it ran (created by the worker: the labels live on its device)
-    std::vector<lash_cluster *> clusters(devices.size(), nullptr);
-    struct ClustersGuard { std::vector<lash_cluster *> &c; ~ClustersGuard() { for (lash_cluster *p : c) lash_cluster_free(p); } } clusters_guard{clusters};
-    std::atomic<uint64_t> cl_pairs{0}, cl_pruned{0}, cl_joined{0}, cl_sent{0};   // (LASH_CLI_TIMING)
-
-    auto worker = [&](size_t wi) {
-        const int device = devices[wi];
-        const DevSets *ds = nullptr;
-        for (const DevSets &d : dev_sets) if (d.device == device) ds = &d;
-        lash_ctx *ctx = nullptr;
-        int rc = lash_ctx_create(&ctx, device);                  // the worker's own stream and staging; the sets are shared, read-only
-        if (rc == LASH_OK) rc = lash_ctx_set_layout(ctx, &opt.layout);
-        if (rc == LASH_OK && opt.has_cluster) rc = lash_cluster_create(ctx, nr, &clusters[wi]);
-        std::string my_fail = rc == LASH_OK ? "" : std::string(lash_strerror(rc));
-        // pair tables in page-locked memory (the copy back runs at the link rate): hmh C / N; hll zero + sum; ull the union estimate
-        uint32_t *C = nullptr, *N = nullptr;
-        double *U = nullptr, *EC = nullptr;
-        size_t cap = 0, ec_cap = 0;
-        RowText row_text;                                        // the block's text; its memory is reused from block to block
-        std::vector<uint32_t> w_row, w_col;                      // --max-dist: the block's survivors
-        std::vector<double> w_dist;
-        std::vector<lash_top_key> col_bound, row_bound;          // --top: this worker's K-th key per name, for the next block
-        auto grow = [&](size_t np) {
-            if (np <= cap) return true;
-            lash_host_free_pinned(C); lash_host_free_pinned(N); lash_host_free_pinned(U);
-            C = N = nullptr; U = nullptr;
-            cap = np + np / 8;
-            if (!ull) C = static_cast<uint32_t *>(lash_host_alloc_pinned(cap * 4));
-            if (!hll && !ull) N = static_cast<uint32_t *>(lash_host_alloc_pinned(cap * 4));
-            if (hll || ull) U = static_cast<double *>(lash_host_alloc_pinned(cap * 8));
-            return (ull || C) && (hll || ull || N) && (!(hll || ull) || U);
-        };
-        for (;;) {
-            const uint32_t blk = next_block.fetch_add(1);
-            if (blk >= n_blocks) break;
-            const uint32_t i0 = block_begin[blk], i1 = block_begin[blk + 1];
-            const uint32_t n_cols = same_files ? std::min(i1, nq) : nq;     // the triangle: no row of the block prints beyond its own column
-            bool skip;
-            { std::lock_guard<std::mutex> lk(wmu); skip = !fail.empty(); }
-            bool have_ec = false;
-            row_text.off.clear(); row_text.len.clear();
-            if (my_fail.empty() && !skip && opt.top) {
-                // pair statistics, expected collisions and the selection on the device; the survivors go to this worker's lists
-                uint64_t kept = 0, bad = 0, cand = 0;
-                if (w_row.empty()) { w_row.resize(1u << 16); w_col.resize(1u << 16); w_dist.resize(1u << 16); }
-                col_bound.resize(n_cols);
-                row_bound.resize(i1 - i0);
-                lash_top_bounds(tops[wi], i0, i1, n_cols, col_bound.data(), same_files ? row_bound.data() : nullptr);
-                for (;;) {
-                    rc = lash_sketch_set_pair_block_top(ctx, ds->ref, i0, i1, ds->qry, n_cols, same_files ? 1 : 0, k, opt.model, opt.fp32 ? 1 : 0, ull_est,
-                                                        bias, opt.top, opt.has_max_dist ? opt.max_dist : NAN, same_col.data() + i0, col_bound.data(),
-                                                        same_files ? row_bound.data() : nullptr, w_row.data(), w_col.data(), w_dist.data(), w_row.size(),
-                                                        &kept, &bad, &cand);
-                    if (rc != LASH_OK || kept <= w_row.size()) break;
-                    w_row.resize(kept + kept / 4); w_col.resize(w_row.size()); w_dist.resize(w_row.size());
-                }
-                top_candidates += cand;
-                if (rc == LASH_OK) rc = lash_top_add(tops[wi], w_row.data(), w_col.data(), w_dist.data(), kept);
-                if (rc == LASH_ERANGE) my_fail = "union of " + row_name[i0 + bad / n_cols] + " and " + col_name[bad % n_cols] + bias_msg;
-                else if (rc != LASH_OK) my_fail = std::string(lash_strerror(rc)) + " " + lash_ctx_last_error(ctx);
-            } else if (my_fail.empty() && !skip && opt.has_cluster) {
-                // pair statistics, expected collisions and the joins on the device; only the pairs it cannot decide come back, and
-                // the library links those in the accumulator's host side
-                uint64_t bad = 0;
-                lash_cluster_stats cs;
-                rc = lash_sketch_set_pair_block_cluster(ctx, ds->ref, i0, i1, ds->qry, n_cols, k, opt.model, opt.fp32 ? 1 : 0, ull_est, bias,
-                                                        opt.cluster_dist, clusters[wi], &cs, &bad);
-                if (rc == LASH_ERANGE) my_fail = "union of " + row_name[i0 + bad / n_cols] + " and " + col_name[bad % n_cols] + bias_msg;
-                else if (rc != LASH_OK) my_fail = std::string(lash_strerror(rc)) + " " + lash_ctx_last_error(ctx);
-                else { cl_pairs += cs.pairs; cl_pruned += cs.pruned; cl_joined += cs.joined_on_device; cl_sent += cs.sent_to_host; }
-            } else if (my_fail.empty() && !skip && opt.has_max_dist) {
-                // pair statistics, expected collisions and the cutoff on the device; only the survivors come back
-                uint64_t kept = 0, bad = 0;
-                if (w_row.empty()) { w_row.resize(1u << 16); w_col.resize(1u << 16); w_dist.resize(1u << 16); }
-                for (;;) {
-                    rc = lash_sketch_set_pair_block_within(ctx, ds->ref, i0, i1, ds->qry, n_cols, same_files ? 1 : 0, k, opt.model, opt.fp32 ? 1 : 0,
-                                                           ull_est, bias, opt.max_dist, w_row.data(), w_col.data(), w_dist.data(), w_row.size(),
-                                                           &kept, &bad, nullptr);
-                    if (rc != LASH_OK || kept <= w_row.size()) break;
-                    w_row.resize(kept + kept / 4); w_col.resize(w_row.size()); w_dist.resize(w_row.size());
-                }
-                if (rc == LASH_ERANGE) my_fail = "union of " + row_name[i0 + bad / n_cols] + " and " + col_name[bad % n_cols] + bias_msg;
-                else if (rc != LASH_OK) my_fail = std::string(lash_strerror(rc)) + " " + lash_ctx_last_error(ctx);
-                else format_block_within(i0, i1, same_files, nq, opt.max_dist, w_row.data(), w_col.data(), w_dist.data(), kept, same_col.data(),
-                                         row_name, col_tab, row_text);
-            } else if (my_fail.empty() && !skip) {
-                const size_t np = (size_t)(i1 - i0) * n_cols;
-                if (!grow(np)) my_fail = "out of page-locked host memory";
-                else {
-                    rc = lash_sketch_set_pair_block(ctx, ds->ref, i0, i1, ds->qry, n_cols, same_files ? 1 : 0, ull_est, C, N, U);
-                    if (rc == LASH_OK && gpu_ec) {
-                        // hyperminhash's expected_collisions below 2^19 distinct k-mers on both sides is a 65 536-cell sum — on the host
-                        // 4 ms to 0.2 s per pair; the library does the block's small pairs as one matrix product on the GPU
-                        if (np > ec_cap) { lash_host_free_pinned(EC); ec_cap = np + np / 8; EC = static_cast<double *>(lash_host_alloc_pinned(ec_cap * 8)); }
-                        uint64_t n_small = 0;
-                        rc = EC ? lash_sketch_set_hmh_expected_collisions(ctx, ds->ref, i0, i1, ds->qry, n_cols, EC, &n_small) : LASH_ENOMEM;
-                        have_ec = n_small != 0;
-                    }
-                    if (rc != LASH_OK) my_fail = std::string(lash_strerror(rc)) + " " + lash_ctx_last_error(ctx);
-                }
-            }
-            if (my_fail.empty() && !skip && !opt.has_max_dist && !opt.top && !opt.has_cluster) {
-                BlockTables bt;
-                bt.c_or_zero = C; bt.n_counts = N; bt.sum_or_union = U; bt.hmh_ec = have_ec ? EC : nullptr; bt.ld = n_cols;
-                my_fail = dist_block_rows(algo_id, prec, k, opt.model, opt.fp32, bias, i0, i1, same_files, nq, rcard.data(), qcard.data(), bt, row_name,
-                                          col_name, col_tab, row_id.data(), col_id.data(), opt.matrix, fmt_threads, row_text);
-                if (!my_fail.empty()) row_text.len.clear();
-            }
-            // in block order, whatever order the devices finish in
-            std::unique_lock<std::mutex> lk(wmu);
-            wcv.wait(lk, [&] { return next_to_write == blk; });
-            if (!my_fail.empty() && fail.empty()) fail = my_fail;
-            if (fail.empty())
-                for (size_t r = 0; r < row_text.rows(); ++r) fwrite(row_text.data(r), 1, row_text.size(r), out);
-            ++next_to_write;
-            lk.unlock();
-            wcv.notify_all();
-        }
-        lash_host_free_pinned(C); lash_host_free_pinned(N); lash_host_free_pinned(U); lash_host_free_pinned(EC);
-        if (ctx) lash_ctx_destroy(ctx);
-    };
+        for (lash_top *&t : run.tops)
+            if (lash_top_create(in.same_files ? in.nr : in.nq, opt.top, in.same_files ? 1 : 0, &t) != LASH_OK) return "cannot create the --top lists";
     {
         std::vector<std::thread> pool;
-        for (size_t d = 1; d < devices.size(); ++d) pool.emplace_back(worker, d);
-        worker(0);
+        for (size_t d = 1; d < run.devices.size(); ++d) pool.emplace_back([&run, d] { Worker(run, d).work(); });
+        Worker(run, 0).work();
         for (auto &t : pool) t.join();
     }
-    if (opt.top && fail.empty()) {
-        // --top: the workers' lists merged, the kept pairs in (row, col) order through the --max-dist formatter (every pair passes;
-        // same-name pairs are in the lists with d = 0 when they are among the K nearest)
-        for (size_t w = 1; w < tops.size() && fail.empty(); ++w)
-            if (lash_top_merge(tops[0], tops[w]) != LASH_OK) fail = "cannot merge the --top lists";
-        uint64_t n = 0;
-        std::vector<uint32_t> t_row, t_col;
-        std::vector<double> t_dist;
-        if (fail.empty() && lash_top_result(tops[0], nullptr, nullptr, nullptr, 0, &n) == LASH_OK) {
-            t_row.resize(n); t_col.resize(n); t_dist.resize(n);
-            if (lash_top_result(tops[0], t_row.data(), t_col.data(), t_dist.data(), n, &n) != LASH_OK) fail = "cannot read the --top lists";
-        }
-        if (fail.empty()) {
-            RowText text;
-            const std::vector<uint32_t> no_same(nr, NO_COLUMN);
-            format_block_within(0, nr, same_files, nq, HUGE_VAL, t_row.data(), t_col.data(), t_dist.data(), n, no_same.data(), row_name, col_tab, text);
-            for (size_t r = 0; r < text.rows(); ++r) fwrite(text.data(r), 1, text.size(r), out);
-            if (timing) fprintf(stderr, "[lash dist] --top: %llu candidates from the device, %llu rows kept\n",
-                                (unsigned long long)top_candidates.load(), (unsigned long long)n);
-            mark("--top: the kept rows written");
-        }
-    }
-    if (opt.has_cluster && fail.empty()) {
-        // --cluster: the workers' clusters merged; every name under its cluster's first name, in row order
-        for (size_t w = 1; w < clusters.size() && fail.empty(); ++w)
-            if (!clusters[0] || !clusters[w] || lash_cluster_merge(clusters[0], clusters[w]) != LASH_OK) fail = "cannot merge the --cluster labels";
-        std::vector<uint32_t> label(nr);
-        if (fail.empty() && nr && (!clusters[0] || lash_cluster_labels(clusters[0], label.data()) != LASH_OK)) fail = "cannot read the --cluster labels";
-        if (fail.empty()) {
-            std::vector<uint32_t> by_rep(nr);
-            std::iota(by_rep.begin(), by_rep.end(), 0u);
-            std::stable_sort(by_rep.begin(), by_rep.end(), [&](uint32_t x, uint32_t y) { return label[x] < label[y]; });
-            std::string text;
-            uint64_t n_clusters = 0;
-            for (uint32_t i : by_rep) {
-                n_clusters += label[i] == i;
-                text.append(row_name[label[i]]).push_back('\t');
-                text.append(row_name[i]).push_back('\n');
-                if (text.size() >= (1u << 20)) { fwrite(text.data(), 1, text.size(), out); text.clear(); }
-            }
-            fwrite(text.data(), 1, text.size(), out);
-            if (timing) fprintf(stderr, "[lash dist] --cluster: %llu pairs looked at, %llu pruned as already joined, %llu joined on the device, "
-                                "%llu sent to the host, %llu clusters\n", (unsigned long long)cl_pairs.load(), (unsigned long long)cl_pruned.load(),
-                                (unsigned long long)cl_joined.load(), (unsigned long long)cl_sent.load(), (unsigned long long)n_clusters);
-            mark("--cluster: the clusters written");
-        }
-    }
-    fclose(out);
-    mark("all rows written");
-    return fail;
+    if (run.fail.empty() && opt.top) run.fail = finish_top(run);
+    if (run.fail.empty() && opt.has_cluster) run.fail = finish_cluster(run);
+    fclose(run.out);
+    run.out = nullptr;
+    timing.mark("all rows written");
+    return run.fail;
 }
 
 }  // namespace lashhost

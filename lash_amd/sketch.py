@@ -505,6 +505,30 @@ class SketchSet:
         self._ctx._check(self._lib.lash_sketch_set_hmh_expected_collisions(self._ctx._h, self._h, int(r0), int(r1), q._h, nc, out.ctypes.data, C.byref(cnt)))
         return out if cnt.value else None
 
+    def _check_pair(self, rc, bad):
+        """rc of a filtered-block entry: LASH_ERANGE raises a LashError whose .pair is the refused pair, (row - r0) * n_cols + col."""
+        if rc == _lib.ERANGE:
+            e = LashError(rc, self._lib.lash_strerror(rc).decode() + " (pair %d)" % bad.value)
+            e.pair = bad.value
+            raise e
+        self._ctx._check(rc)
+
+    def _kept_rows(self, cap, stats, call):
+        """call((out_row, out_col, out_dist, cap, &n_kept, &bad_pair, &n_candidates)) -> rc until the buffers hold every kept row (cap: once)."""
+        size = (1 << 12) if cap is None else int(cap)
+        while True:
+            row, col = np.empty(size, np.uint32), np.empty(size, np.uint32)
+            dist = np.empty(size, np.float64)
+            kept, bad, cand = C.c_uint64(), C.c_uint64(), C.c_uint64()
+            self._check_pair(call((row.ctypes.data, col.ctypes.data, dist.ctypes.data, size, C.byref(kept), C.byref(bad), C.byref(cand))), bad)
+            if cap is not None or kept.value <= size:
+                break
+            size = kept.value
+        if stats is not None:
+            stats.update(n_kept=kept.value, n_candidates=cand.value)
+        n = min(kept.value, size)
+        return row[:n], col[:n], dist[:n]
+
     def pair_block_within(self, r0, r1, max_dist, k, qry=None, n_cols=None, triangle=False, model=1, fp32=False, estimator="fgra",
                           hll_bias=None, cap=None, stats=None):
         """`lash dist --max-dist`: the pairs of rows [r0, r1) x columns [0, n_cols) whose distance d (lash_dist_rows' number, before the
@@ -514,27 +538,9 @@ class SketchSet:
         cardinalities() must have run on both sets."""
         q = qry or self
         nc = q.n if n_cols is None else int(n_cols)
-        size = (1 << 12) if cap is None else int(cap)
-        while True:
-            row, col = np.empty(size, np.uint32), np.empty(size, np.uint32)
-            dist = np.empty(size, np.float64)
-            kept, bad, cand = C.c_uint64(), C.c_uint64(), C.c_uint64()
-            rc = self._lib.lash_sketch_set_pair_block_within(self._ctx._h, self._h, int(r0), int(r1), q._h, nc, 1 if triangle else 0, int(k), int(model),
-                                                             1 if fp32 else 0, ULL_ESTIMATORS[estimator], _bias_handle(hll_bias), float(max_dist),
-                                                             row.ctypes.data, col.ctypes.data, dist.ctypes.data, size, C.byref(kept), C.byref(bad),
-                                                             C.byref(cand))
-            if rc == _lib.ERANGE:
-                e = LashError(rc, self._lib.lash_strerror(rc).decode() + " (pair %d)" % bad.value)
-                e.pair = bad.value                                   # (row - r0) * n_cols + col
-                raise e
-            self._ctx._check(rc)
-            if cap is not None or kept.value <= size:
-                break
-            size = kept.value
-        if stats is not None:
-            stats.update(n_kept=kept.value, n_candidates=cand.value)
-        n = min(kept.value, size)
-        return row[:n], col[:n], dist[:n]
+        return self._kept_rows(cap, stats, lambda out: self._lib.lash_sketch_set_pair_block_within(
+            self._ctx._h, self._h, int(r0), int(r1), q._h, nc, 1 if triangle else 0, int(k), int(model), 1 if fp32 else 0,
+            ULL_ESTIMATORS[estimator], _bias_handle(hll_bias), float(max_dist), *out))
 
     def pair_block_top(self, r0, r1, top, k, qry=None, n_cols=None, triangle=False, max_dist=None, same_col=None, col_bound=None,
                        row_bound=None, model=1, fp32=False, estimator="fgra", hll_bias=None, cap=None, stats=None):
@@ -551,29 +557,10 @@ class SketchSet:
         assert sc is None or len(sc) >= int(r1) - int(r0)
         assert cb is None or len(cb) >= nc
         assert rb is None or len(rb) >= int(r1) - int(r0)
-        size = (1 << 12) if cap is None else int(cap)
-        while True:
-            row, col = np.empty(size, np.uint32), np.empty(size, np.uint32)
-            dist = np.empty(size, np.float64)
-            kept, bad, cand = C.c_uint64(), C.c_uint64(), C.c_uint64()
-            rc = self._lib.lash_sketch_set_pair_block_top(self._ctx._h, self._h, int(r0), int(r1), q._h, nc, 1 if triangle else 0, int(k), int(model),
-                                                          1 if fp32 else 0, ULL_ESTIMATORS[estimator], _bias_handle(hll_bias), int(top),
-                                                          float("nan") if max_dist is None else float(max_dist),
-                                                          None if sc is None else sc.ctypes.data, None if cb is None else cb.ctypes.data,
-                                                          None if rb is None else rb.ctypes.data, row.ctypes.data, col.ctypes.data,
-                                                          dist.ctypes.data, size, C.byref(kept), C.byref(bad), C.byref(cand))
-            if rc == _lib.ERANGE:
-                e = LashError(rc, self._lib.lash_strerror(rc).decode() + " (pair %d)" % bad.value)
-                e.pair = bad.value                                   # (row - r0) * n_cols + col
-                raise e
-            self._ctx._check(rc)
-            if cap is not None or kept.value <= size:
-                break
-            size = kept.value
-        if stats is not None:
-            stats.update(n_kept=kept.value, n_candidates=cand.value)
-        n = min(kept.value, size)
-        return row[:n], col[:n], dist[:n]
+        return self._kept_rows(cap, stats, lambda out: self._lib.lash_sketch_set_pair_block_top(
+            self._ctx._h, self._h, int(r0), int(r1), q._h, nc, 1 if triangle else 0, int(k), int(model), 1 if fp32 else 0,
+            ULL_ESTIMATORS[estimator], _bias_handle(hll_bias), int(top), float("nan") if max_dist is None else float(max_dist),
+            None if sc is None else sc.ctypes.data, None if cb is None else cb.ctypes.data, None if rb is None else rb.ctypes.data, *out))
 
     def top_pairs(self, top, k, qry=None, triangle=None, max_dist=None, same_col=None, block_rows=None, **kw):
         """`lash dist --top` over the whole set: walks row blocks of `block_rows` (default: all rows in one block) through
@@ -604,14 +591,9 @@ class SketchSet:
         have run."""
         nc = min(int(r1), self.n) if n_cols is None else int(n_cols)
         st, bad = _lib.ClusterStats(), C.c_uint64()
-        rc = self._lib.lash_sketch_set_pair_block_cluster(self._ctx._h, self._h, int(r0), int(r1), self._h, nc, int(k), int(model), 1 if fp32 else 0,
-                                                          ULL_ESTIMATORS[estimator], _bias_handle(hll_bias), float(max_dist), clusters._h,
-                                                          C.byref(st), C.byref(bad))
-        if rc == _lib.ERANGE:
-            e = LashError(rc, self._lib.lash_strerror(rc).decode() + " (pair %d)" % bad.value)
-            e.pair = bad.value                                       # (row - r0) * n_cols + col
-            raise e
-        self._ctx._check(rc)
+        self._check_pair(self._lib.lash_sketch_set_pair_block_cluster(self._ctx._h, self._h, int(r0), int(r1), self._h, nc, int(k), int(model),
+                                                                      1 if fp32 else 0, ULL_ESTIMATORS[estimator], _bias_handle(hll_bias),
+                                                                      float(max_dist), clusters._h, C.byref(st), C.byref(bad)), bad)
         if stats is not None:
             stats.update({f: getattr(st, f) for f, _ in st._fields_})
 
