@@ -214,6 +214,35 @@ int lash_sketch_files_raw_device(lash_ctx *ctx, const lash_params *prm, const ui
  * The first byte of a file must be '>' or '@' (parse_fastx_file fails otherwise, utils.rs:453): LASH_EINVAL from both. */
 uint32_t lash_ctx_format_errors(lash_ctx *ctx, uint32_t *file_index, uint32_t cap);
 
+/* One sketch per FASTA RECORD (`lash sketch --per-record`; Mash's -i): viral / plasmid databases, metagenome assemblies and contig sets come as
+ * one multi-FASTA with 10^4 - 10^6 records.  lash_fasta_index finds the records of a batch of raw, uncompressed FASTA files on the device
+ * (fasta_index.hip), in file order then byte order:
+ *   start[r]   byte offset of record r's '>' in the buffer, r in [0, n_records]; the extra entry is file_off[n_files], so record r is
+ *              bytes [start[r], start[r + 1]) (a file's last record ends where the next file begins)
+ *   id_len[r]  length of the record id: the header bytes after '>' up to the first space, TAB, CR, LF or the end of the file (may be 0)
+ *   file[r]    index of the file the record belongs to
+ * Rules (needletail's): a record starts at a file's first byte and at every '>' whose preceding byte in the same file is '\n'; a '>'
+ * anywhere else starts nothing; every record counts whatever its sequence.  An empty file holds no record.  file_off[0] must be 0.  A
+ * file whose first byte is not '>' (every FASTQ file): LASH_EINVAL.  _device: the bytes are in device memory, file_off stays on the
+ * host; both entries synchronize the context's stream once (the number of records sizes the result).  Each accessor is one copy to
+ * the host.  Free with lash_rec_index_free.  An index made by lash_fasta_index keeps its device copy of the bytes until it is freed.
+ * lash_sketch_records_raw sketches records [r0, r1) of an index made from the same raw / file_off: one image per record, exactly what
+ * lash_sketch_files_raw gives for the same records written one per file — it IS that call, with start[r0 .. r1] as its file offsets, so
+ * the HyperLogLog `sum` replay and lash_ctx_format_errors / lash_ctx_hll_inexact_sums work as there, with record indices relative to
+ * r0 where that entry has file indices.  A caller bounds the bytes of images in flight by the width of [r0, r1).  With an index made by
+ * lash_fasta_index from this same `raw` pointer (unchanged since) the bytes are not copied to the device again.  LASH_F_AMINO:
+ * LASH_EINVAL. */
+typedef struct lash_rec_index lash_rec_index;
+int      lash_fasta_index(lash_ctx *ctx, const uint8_t *raw, const uint64_t *file_off, uint32_t n_files, lash_rec_index **out);
+int      lash_fasta_index_device(lash_ctx *ctx, const uint8_t *d_raw, const uint64_t *file_off, uint32_t n_files, lash_rec_index **out);
+uint64_t lash_rec_index_n_records(const lash_rec_index *index);
+int      lash_rec_index_start(lash_ctx *ctx, const lash_rec_index *index, uint64_t *out);    /* n_records + 1 */
+int      lash_rec_index_id_len(lash_ctx *ctx, const lash_rec_index *index, uint32_t *out);   /* n_records */
+int      lash_rec_index_file(lash_ctx *ctx, const lash_rec_index *index, uint32_t *out);     /* n_records */
+void     lash_rec_index_free(lash_ctx *ctx, lash_rec_index *index);
+int      lash_sketch_records_raw(lash_ctx *ctx, const lash_params *prm, const uint8_t *raw, const uint64_t *file_off, uint32_t n_files,
+                                 const lash_rec_index *index, uint64_t r0, uint64_t r1, uint8_t *out_images);
+
 /* HyperLogLog images carry `sum` = sum_j 2^-m[j] (f64).  streaming_algorithms keeps it incrementally per k-mer (sum -= 2^-old;
  * sum += 2^-new); that is exactly the sum over the final registers as long as every register is <= 53 - p, and the HIP path
  * writes that sum.  A register above 53 - p (one k-mer in 2^(52-p): p = 14 -> 1 in 2.7e11) makes the incremental value depend

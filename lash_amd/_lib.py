@@ -74,6 +74,14 @@ PROTOTYPES = {
     "lash_sketch_files_raw": (_int, [_vp, _PP, _vp, _vp, _vp, _u32, _vp]),
     "lash_sketch_files_raw_device": (_int, [_vp, _PP, _vp, _vp, _vp, _u32, _vp]),
     "lash_ctx_format_errors": (_u32, [_vp, _vp, _u32]),
+    "lash_fasta_index": (_int, [_vp, _vp, _vp, _u32, C.POINTER(_vp)]),
+    "lash_fasta_index_device": (_int, [_vp, _vp, _vp, _u32, C.POINTER(_vp)]),
+    "lash_rec_index_n_records": (_u64, [_vp]),
+    "lash_rec_index_start": (_int, [_vp, _vp, _vp]),
+    "lash_rec_index_id_len": (_int, [_vp, _vp, _vp]),
+    "lash_rec_index_file": (_int, [_vp, _vp, _vp]),
+    "lash_rec_index_free": (None, [_vp, _vp]),
+    "lash_sketch_records_raw": (_int, [_vp, _PP, _vp, _vp, _u32, _vp, _u64, _u64, _vp]),
     "lash_hll_replay_sums_device": (_int, [_vp, _PP, _vp, _vp, _u64, _vp, _u32, _vp]),
     "lash_hll_replay_streamed_chunk": (_int, [_vp, _PP, _vp, _u64, _int, _vp, _vp, _vp, _vp]),
     "lash_ctx_hll_inexact_sums": (_u32, [_vp, _vp, _u32]),

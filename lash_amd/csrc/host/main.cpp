@@ -3,7 +3,8 @@
 //   lash sketch -f LIST [-o sketch] [-k 16] [-t N] [-a hmh|hll|ull] [-p 10] [-s 42]        (main.rs:30-96, 180-279)
 //   lash dist   -q PREFIX -r PREFIX [-o dist] [-t N] [-e fgra|ml] [-m 1|0] [--fp32] [--dm]   (main.rs:107-176, 280-617)
 // Extras that do not exist upstream: --gpus N / --device D / --devices LIST (which GPUs to use, one worker each), --batch-mb M, --stream-mb M (files
-// larger than M MiB are streamed in chunks with on-device accumulation), --hmh-x-low; dist: --device D, --block-rows N,
+// larger than M MiB are streamed in chunks with on-device accumulation), --hmh-x-low, --per-record (one sketch per FASTA record, the records
+// found on the GPU); dist: --device D, --block-rows N,
 // --file-order (rows / columns in list-file order instead of the reference's seeded hash-map order), --max-dist D (print only
 // the pairs with distance <= D), --top K (only each name's K nearest), --cluster D (single-linkage clusters of an all-vs-all instead
 // of pairs) (reference rows per GPU call); both: --layout SPEC (or $LASH_LAYOUT): the crate-internal rules as data, see `lash_layout`
@@ -49,6 +50,8 @@ void usage()
             "  -p, --precision <precision>  Specifiy precision, for ull and hll only. [default: 10]\n"
             "  -s, --seed <seed>            Random seed [default: 42]\n"
             "      --aa                     Amino acid sketching (k 1-12); the reference carries this flag commented out\n"
+            "      --per-record             One sketch per FASTA record instead of one per file (multi-FASTA collections; like Mash -i);\n"
+            "                               {output}_files.json then holds the record ids.  FASTA only, not with --aa\n"
             "      --gpus <n> | --device <d> | --devices <d,d,...>  GPUs to use, one worker each [default: device 0]\n"
             "dist options:\n"
             "  -q, --query <prefix>  -r, --reference <prefix>  -o, --output_file <name> [default: dist]\n"
@@ -108,7 +111,7 @@ int cmd_sketch(int argc, char **argv)
     std::string err;
     const std::map<std::string, std::string> alias = {{"f", "file"}, {"o", "output"}, {"k", "kmer"}, {"t", "threads"},
                                                       {"a", "algorithm"}, {"p", "precision"}, {"s", "seed"}};
-    if (!parse(argc, argv, 2, alias, {"hmh-x-low", "aa"}, a, err)) { fprintf(stderr, "error: %s\n", err.c_str()); return 2; }
+    if (!parse(argc, argv, 2, alias, {"hmh-x-low", "aa", "per-record"}, a, err)) { fprintf(stderr, "error: %s\n", err.c_str()); return 2; }
     if (!a.kv.count("file")) { fprintf(stderr, "error: the following required arguments were not provided:\n  --file <file>\n"); return 2; }
     SketchOptions opt;
     const std::string output = a.kv.count("output") ? a.kv["output"] : "sketch";
@@ -129,6 +132,8 @@ int cmd_sketch(int argc, char **argv)
     else { fprintf(stderr, "Algorithm must be either hmh, ull, or hll\n"); return 101; }      // main.rs:245 panic
     if (k < 1 || k > 32) { fprintf(stderr, "k-mer length must be 1-32\n"); return 101; }       // utils.rs:501 panic
     const bool amino = a.flags.count("aa") != 0;                                               // main.rs:97-104 (commented out there)
+    opt.per_record = a.flags.count("per-record") != 0;
+    if (opt.per_record && amino) { fprintf(stderr, "error: --per-record cannot be used with --aa (records are split for nucleotide FASTA only)\n"); return 2; }
     if (amino && k > 12) { fprintf(stderr, "k-mer length for amino acid must be 1\xe2\x80\x93" "12\n"); return 101; }   // utils.rs:554 panic
     opt.k = (int)k;
     opt.precision = (int)p;
@@ -161,8 +166,13 @@ int cmd_sketch(int argc, char **argv)
     if (!err.empty()) { fprintf(stderr, "Error: %s\n", err.c_str()); return 1; }
     err = write_parameters_json(output, alg, opt.k, opt.precision, opt.seed, amino);
     if (!err.empty()) { fprintf(stderr, "Error: %s\n", err.c_str()); return 1; }
-    fprintf(stderr, "sketched %llu files (%.3f GB of FASTA/FASTQ text) in %.2f s on %zu GPU(s), %llu batches\n",
-            (unsigned long long)st.files, st.bytes / 1e9, st.seconds, opt.devices.size(), (unsigned long long)st.batches);
+    if (opt.per_record)
+        fprintf(stderr, "sketched %llu records of %llu files (%.3f GB of FASTA text) in %.2f s on %zu GPU(s), %llu batches\n",
+                (unsigned long long)st.records, (unsigned long long)st.files, st.bytes / 1e9, st.seconds, opt.devices.size(),
+                (unsigned long long)st.batches);
+    else
+        fprintf(stderr, "sketched %llu files (%.3f GB of FASTA/FASTQ text) in %.2f s on %zu GPU(s), %llu batches\n",
+                (unsigned long long)st.files, st.bytes / 1e9, st.seconds, opt.devices.size(), (unsigned long long)st.batches);
     return 0;
 }
 

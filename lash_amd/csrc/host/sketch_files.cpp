@@ -102,7 +102,15 @@ struct Batch {
     std::vector<uint8_t> images;
     std::string err;
     std::mutex emu;
+    // --per-record: the images leave in parts (one per sub-call) that the writer takes while the batch is still being sketched, so
+    // that a batch of many small records never holds all its images at once (parts / parts_bytes: guarded by the queue mutex)
+    std::deque<std::vector<uint8_t>> parts;
+    size_t parts_bytes = 0;
+    std::vector<std::string> names;       // record ids, in order
 };
+
+// --per-record: bytes of images one sub-call may produce, and a batch may hold unwritten (8 192 HyperMinHash images)
+constexpr size_t kRecordImageCap = 256u << 20;
 
 // simple worker pool
 class Pool {
@@ -444,6 +452,53 @@ std::string sketch_files(const SketchOptions &opt, const std::vector<std::string
     // page-locked memory than ~512 MiB: pinning costs ~0.18 s per GB and is the slowest thing the host does here.
     const size_t in_flight_cap = std::max<size_t>(2 * devices.size() + 1,
                                                   (size_t)((512ull << 20) / std::max<uint64_t>(opt.batch_bytes, 1)));
+    // --per-record: index the batch on the device, then sketch its records in sub-calls of at most kRecordImageCap bytes of images; each
+    // sub-call's images go to the writer as one part.  A worker whose batch holds a cap's worth of unwritten images waits for the writer —
+    // unless the writer is waiting for a batch nobody has started yet (which may be the next one in this worker's own queue).
+    std::map<uint64_t, std::shared_ptr<Batch>> live;       // batches being sketched (guarded by qmu)
+    uint64_t writer_want = 0;                              // the batch the writer is at (guarded by qmu)
+    auto sketch_records = [&](lash_ctx *ctx, Batch &b) -> std::string {
+        const uint32_t nf = (uint32_t)(b.f1 - b.f0);
+        lash_rec_index *ix = nullptr;
+        int rc = lash_fasta_index(ctx, b.buf->p, b.file_off.data(), nf, &ix);
+        if (rc != LASH_OK) return std::string(lash_strerror(rc)) + " " + lash_ctx_last_error(ctx);
+        const uint64_t n = lash_rec_index_n_records(ix);
+        std::vector<uint64_t> start(n + 1);
+        std::vector<uint32_t> id_len(n);
+        if ((rc = lash_rec_index_start(ctx, ix, start.data())) == LASH_OK) rc = lash_rec_index_id_len(ctx, ix, id_len.data());
+        std::string e;
+        if (rc == LASH_OK) {
+            b.names.reserve(n);
+            for (uint64_t r = 0; r < n; ++r) b.names.emplace_back(reinterpret_cast<const char *>(b.buf->p) + start[r] + 1, id_len[r]);
+            const uint64_t step = std::max<uint64_t>(1, kRecordImageCap / std::max<size_t>(ib, 1));
+            for (uint64_t r0 = 0; r0 < n && rc == LASH_OK; r0 += step) {
+                const uint64_t r1 = std::min(n, r0 + step);
+                std::vector<uint8_t> part((size_t)(r1 - r0) * ib, 0);
+                rc = lash_sketch_records_raw(ctx, &prm, b.buf->p, b.file_off.data(), nf, ix, r0, r1, part.data());
+                if (rc != LASH_OK) break;
+                if (prm.algo == LASH_HLL) {
+                    // as the per-file path: a register above 53 - p that the library could not replay (none is expected: a call that
+                    // does not accumulate re-does such records exactly)
+                    std::vector<uint32_t> idx((size_t)(r1 - r0));
+                    const uint32_t nc = lash_ctx_hll_inexact_sums(ctx, idx.data(), (uint32_t)idx.size());
+                    for (uint32_t i = 0; i < nc && i < idx.size(); ++i)
+                        fprintf(stderr, "note: record '%s' of %s: a HyperLogLog register exceeds 53 - p; the header's sum field is the exact sum and may "
+                                        "differ from lash's incrementally rounded value in its last bits\n", b.names[r0 + idx[i]].c_str(), files[b.f0].c_str());
+                }
+                std::unique_lock<std::mutex> lk(qmu);
+                cv_done.wait(lk, [&] {
+                    return b.parts_bytes < kRecordImageCap ||
+                           (writer_want != b.index && !live.count(writer_want) && !finished.count(writer_want));
+                });
+                b.parts_bytes += part.size();
+                b.parts.push_back(std::move(part));
+                cv_done.notify_all();
+            }
+        }
+        if (rc != LASH_OK) e = std::string(lash_strerror(rc)) + " " + lash_ctx_last_error(ctx);
+        lash_rec_index_free(ctx, ix);
+        return e;
+    };
     auto gpu_worker = [&](int device) {
         lash_ctx *ctx = nullptr;
         int rc = lash_ctx_create(&ctx, device);
@@ -457,10 +512,15 @@ std::string sketch_files(const SketchOptions &opt, const std::vector<std::string
                 if (todo.empty()) break;
                 b = todo.front();
                 todo.pop_front();
+                if (opt.per_record) { live[b->index] = b; cv_done.notify_all(); }
             }
             if (b->err.empty()) {
                 if (rc != LASH_OK) b->err = lash_strerror(rc);
-                else {
+                else if (opt.per_record) {
+                    const auto g0 = std::chrono::steady_clock::now();
+                    b->err = sketch_records(ctx, *b);
+                    mark("GPU done, batch", b->index, std::chrono::duration<double>(std::chrono::steady_clock::now() - g0).count());
+                } else {
                     const uint32_t ng = (uint32_t)(b->f1 - b->f0);
                     b->images.assign((size_t)ng * ib, 0);
                     const auto g0 = std::chrono::steady_clock::now();
@@ -480,6 +540,7 @@ std::string sketch_files(const SketchOptions &opt, const std::vector<std::string
             }
             std::lock_guard<std::mutex> lk(qmu);
             if (b->buf) pool_bufs.push_back(std::move(b->buf));
+            live.erase(b->index);
             finished[b->index] = b;
             cv_done.notify_all();
         }
@@ -490,6 +551,8 @@ std::string sketch_files(const SketchOptions &opt, const std::vector<std::string
 
     // ---- writer: images in batch (== file) order into one zstd stream (utils.rs:567-574; frames: zstd_dl.hpp) ----
     std::string werr;
+    std::vector<std::string> record_names;                 // --per-record: the ids, in output order (the writer's)
+    uint64_t n_records = 0;
     uint64_t n_batches_total = 0;
     bool batches_known = false;
     std::thread writer([&]() {
@@ -500,16 +563,34 @@ std::string sketch_files(const SketchOptions &opt, const std::vector<std::string
             std::shared_ptr<Batch> b;
             {
                 std::unique_lock<std::mutex> lk(qmu);
-                cv_done.wait(lk, [&] { return finished.count(want) || (batches_known && want >= n_batches_total); });
-                if (!finished.count(want)) break;
-                b = finished[want];
+                cv_done.wait(lk, [&] { return finished.count(want) || live.count(want) || (batches_known && want >= n_batches_total); });
+                if (finished.count(want)) b = finished[want];
+                else if (live.count(want)) b = live[want];
+                else break;
+            }
+            for (;;) {                                      // --per-record: the batch's parts, as they come, until it is finished
+                std::vector<uint8_t> part;
+                {
+                    std::unique_lock<std::mutex> lk(qmu);
+                    cv_done.wait(lk, [&] { return !b->parts.empty() || finished.count(want); });
+                    if (b->parts.empty()) break;
+                    part = std::move(b->parts.front());
+                    b->parts.pop_front();
+                    b->parts_bytes -= part.size();
+                    cv_done.notify_all();
+                }
+                if (werr.empty()) werr = zw.write(part.data(), part.size());
+            }
+            {
+                std::lock_guard<std::mutex> lk(qmu);
                 finished.erase(want);
                 --in_flight;
+                writer_want = ++want;
                 cv_done.notify_all();
             }
             if (werr.empty() && !b->err.empty()) werr = b->err;
-            if (werr.empty()) werr = zw.write(b->images.data(), b->images.size());
-            ++want;
+            if (werr.empty() && !b->images.empty()) werr = zw.write(b->images.data(), b->images.size());
+            if (opt.per_record) { n_records += b->names.size(); record_names.insert(record_names.end(), b->names.begin(), b->names.end()); }
         }
         if (werr.empty()) werr = zw.finish();
     });
@@ -618,6 +699,7 @@ std::string sketch_files(const SketchOptions &opt, const std::vector<std::string
                         if (e.empty()) {
                             const int f = sniff_format(dst, s.size);
                             if (!f) e = "Invalid input file: neither FASTA ('>') nor FASTQ ('@'): " + files[i];
+                            else if (opt.per_record && f != LASH_FMT_FASTA) e = "--per-record takes FASTA input; this file starts with '@' (FASTQ): " + files[i];
                             b->fmt[i - b->f0] = (uint8_t)(f ? f : LASH_FMT_FASTA);
                             // (malformed FASTQ records: found on the device, the file is then re-done by the library with
                             // needletail's rule — utils.rs:457 — or, under layout fastq_err=skip, without the bad records)
@@ -644,6 +726,73 @@ std::string sketch_files(const SketchOptions &opt, const std::vector<std::string
                     cv_sized.wait_for(lk, std::chrono::milliseconds(50));
                     pump_inflates();
                 }
+            }
+            if (slots[i].big && opt.per_record) {
+                // a large multi-FASTA goes to the GPU workers as a sequence of batches, each a chunk of at most --stream-mb that ends
+                // before the last record start in it; a record is never split
+                finalize();
+                ByteStream bs;
+                bs.set_threads(opt.threads);
+                std::string rerr, e = bs.open(files[i]);
+                std::vector<uint8_t> tail;                  // what followed the previous chunk's cut
+                bool eof = false, first = true;
+                while (e.empty() && !eof) {
+                    auto b = std::make_shared<Batch>();
+                    b->f0 = i;
+                    b->f1 = i + 1;
+                    {
+                        // a chunk pins up to --stream-mb (1 GiB by default) where a batch pins --batch-mb, and pinning is the slowest thing
+                        // the host does (~0.18 s per GB): no more chunks in flight than keep every worker busy while one is being read,
+                        // and their buffers are recycled from chunk to chunk
+                        std::unique_lock<std::mutex> lk(qmu);
+                        cv_done.wait(lk, [&] { return in_flight < std::min(in_flight_cap, devices.size() + 1); });
+                        ++in_flight;
+                        if (!pool_bufs.empty()) { b->buf = std::move(pool_bufs.back()); pool_bufs.pop_back(); }
+                    }
+                    if (!b->buf) b->buf.reset(new PinnedBuf());
+                    // (the chunks are read here, one after another, on the planner's thread: a .gz inflates on the pool's threads inside
+                    // ByteStream, a plain file is one sequential read; the bytes after the cut are copied once more into the next chunk)
+                    size_t have = tail.size(), cut = 0;
+                    if (!b->buf->reserve(stream_bytes + 64)) e = "out of pinned host memory";
+                    else {
+                        uint8_t *p = b->buf->p;
+                        if (have) memcpy(p, tail.data(), have);
+                        while (have < stream_bytes) {
+                            const long r = bs.read(p + have, stream_bytes - have, rerr);
+                            if (r < 0) { e = rerr + " (" + files[i] + ")"; break; }
+                            if (r == 0) { eof = true; break; }
+                            have += (size_t)r;
+                            n_bytes += (uint64_t)r;
+                        }
+                        if (e.empty() && first) {
+                            if (have == 0) e = "Invalid input file: empty (" + files[i] + ")";
+                            else if (p[0] == '@') e = "--per-record takes FASTA input; this file starts with '@' (FASTQ): " + files[i];
+                            else if (p[0] != '>') e = "Invalid input file: neither FASTA ('>') nor FASTQ ('@'): " + files[i];
+                        }
+                        if (e.empty()) {
+                            cut = have;
+                            if (!eof)
+                                for (cut = have - 1; cut > 0 && !(p[cut] == '>' && p[cut - 1] == '\n'); --cut) {}
+                            if (cut == 0) {
+                                size_t id_end = 1;
+                                while (id_end < have && id_end < 200 && p[id_end] != ' ' && p[id_end] != '\t' && p[id_end] != '\r' && p[id_end] != '\n') ++id_end;
+                                e = "record '" + std::string(reinterpret_cast<const char *>(p) + 1, id_end - 1) + "' of " + files[i] + " does not fit in a chunk of " +
+                                    std::to_string(stream_bytes >> 20) + " MiB: --per-record never splits a record, raise --stream-mb";
+                            }
+                        }
+                        if (e.empty()) tail.assign(p + cut, p + have);
+                    }
+                    first = false;
+                    b->err = e;
+                    b->file_off = {0, (uint64_t)cut};
+                    b->fmt.assign(1, (uint8_t)LASH_FMT_FASTA);
+                    b->index = batch_index++;
+                    std::lock_guard<std::mutex> lk(qmu);
+                    todo.push_back(b);
+                    cv_todo.notify_one();
+                }
+                if (!e.empty()) err = e;
+                continue;
             }
             if (slots[i].big) {
                 // a large file is its own "batch": streamed here, in file order, into one accumulated image
@@ -692,18 +841,21 @@ std::string sketch_files(const SketchOptions &opt, const std::vector<std::string
     writer.join();
     mark("writer done", 0);
     if (err.empty()) err = werr;
-    if (!err.empty()) return err;
+    if (!err.empty()) {
+        if (opt.per_record) (void)remove((output_name + "_sketches.bin").c_str());   // a refused --per-record run leaves no output
+        return err;
+    }
 
     // ---- names (utils.rs:577-580) ----
     {
         std::ofstream out(output_name + "_files.json", std::ios::binary);
         if (!out) return "cannot create " + output_name + "_files.json";
-        out << json_pretty_string_array(files);
+        out << json_pretty_string_array(opt.per_record ? record_names : files);
         if (!out.good()) return "write failed";
     }
     if (stats) {
         stats->files = n_files;
-        stats->records = 0;
+        stats->records = n_records;
         stats->bytes = n_bytes;
         stats->batches = batch_index;
         stats->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count();

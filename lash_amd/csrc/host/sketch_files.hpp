@@ -27,6 +27,7 @@ struct SketchOptions {
     uint64_t stream_bytes = 1ull << 30;  // files larger than this (compressed: > 1/3 of it on disk) are streamed in chunks
                                          // of this size with on-device accumulation (BASELINE configs[4]); < 4 GiB
     uint32_t flags = 0;              // LASH_F_HMH_X_LOW, LASH_F_AMINO (--aa)
+    bool per_record = false;         // --per-record: one sketch per FASTA record instead of one per file (records found on the GPU)
     lash_layout layout;              // set by layout_from_option(); every context gets it
     SketchOptions() { lash_layout_default(&layout); }
 };

@@ -251,7 +251,7 @@ void lash_ctx_destroy(lash_ctx *ctx)
     release(ctx->sole_state);
     for (DevBuf *b : {&ctx->items, &ctx->item_begin, &ctx->item_kmers, &ctx->partials, &ctx->gregs, &ctx->counter, &ctx->st_seq, &ctx->st_rec,
                       &ctx->st_img, &ctx->hll_flags, &ctx->ec_ref, &ctx->ec_qry, &ctx->ec_x, &ctx->ec_card, &ctx->wf_scratch, &ctx->wf_out, &ctx->top_buf, &ctx->hll_bm_ref,
-                      &ctx->hll_bm_qry, &ctx->hll_lohi})
+                      &ctx->hll_bm_qry, &ctx->hll_lohi, &ctx->fa_off, &ctx->fa_scratch})
         release(*b);
     {
         lash_packed &sc = ctx->scratch;
@@ -674,6 +674,16 @@ void lash_fastq_neutralise_tail(uint8_t *tail, uint64_t n)
 int lash_sketch_files_raw(lash_ctx *ctx, const lash_params *prm, const uint8_t *raw, const uint64_t *file_off,
                           const uint8_t *file_fmt, uint32_t n_files, uint8_t *out_images)
 {
+    return files_raw_staged(ctx, prm, raw, nullptr, file_off, file_fmt, n_files, out_images);
+}
+
+}  // extern "C"
+
+// lash_sketch_files_raw; d_raw != NULL: the bytes of `raw` are already in device memory there (lash_sketch_records_raw: the record index
+// keeps the copy it was made from), so nothing is staged and file_off may start anywhere in the buffer
+int lashi::files_raw_staged(lash_ctx *ctx, const lash_params *prm, const uint8_t *raw, const uint8_t *d_raw, const uint64_t *file_off,
+                            const uint8_t *file_fmt, uint32_t n_files, uint8_t *out_images)
+{
     if (!ctx || !file_off || (n_files && (!out_images || !file_fmt))) return LASH_EINVAL;
     int rc = lash_params_check(prm);
     if (rc) return rc;
@@ -695,12 +705,12 @@ int lash_sketch_files_raw(lash_ctx *ctx, const lash_params *prm, const uint8_t *
         return lash_sketch_batch(ctx, prm, seq.empty() ? &dummy : seq.data(), rec_off.data(), rec_off.size() - 1, goff.data(), n_files, out_images);
     }
     const size_t ib = image_bytes(ctx->layout, prm->algo, prm->p), img_bytes = (size_t)n_files * ib;
-    if ((rc = reserve(ctx, ctx->st_seq, bytes + 64))) return rc;
+    if (!d_raw && (rc = reserve(ctx, ctx->st_seq, bytes + 64))) return rc;
     if ((rc = reserve(ctx, ctx->st_img, img_bytes + 64))) return rc;
-    if (bytes) HIPCHK(ctx, hipMemcpyAsync(ctx->st_seq.ptr, raw, bytes, hipMemcpyHostToDevice, ctx->stream));
+    if (!d_raw && bytes) HIPCHK(ctx, hipMemcpyAsync(ctx->st_seq.ptr, raw, bytes, hipMemcpyHostToDevice, ctx->stream));
     if ((prm->flags & LASH_F_ACCUMULATE) && img_bytes)
         HIPCHK(ctx, hipMemcpyAsync(ctx->st_img.ptr, out_images, img_bytes, hipMemcpyHostToDevice, ctx->stream));
-    rc = lash_sketch_files_raw_device(ctx, prm, static_cast<const uint8_t *>(ctx->st_seq.ptr), file_off, file_fmt, n_files,
+    rc = lash_sketch_files_raw_device(ctx, prm, d_raw ? d_raw : static_cast<const uint8_t *>(ctx->st_seq.ptr), file_off, file_fmt, n_files,
                                       static_cast<uint8_t *>(ctx->st_img.ptr));
     if (rc) return rc;
     // files whose FASTQ structure broke are re-done below from the caller's copy of the images (accumulate) or from scratch:
@@ -756,6 +766,8 @@ int lash_sketch_files_raw(lash_ctx *ctx, const lash_params *prm, const uint8_t *
             if (std::find(bad.begin(), bad.end(), g) == bad.end()) ctx->hll_left.push_back(g);
     return LASH_OK;
 }
+
+extern "C" {
 
 int lash_synth_genomes_device(lash_ctx *ctx, uint64_t first_genome, uint32_t n_genomes, uint64_t n_bases, uint8_t *d_out)
 {

@@ -159,6 +159,7 @@ struct lash_ctx {
                                          // counts | ticket]; record starts as bits at absolute byte positions
     bool last_sole_only = false;         // the last sketch call ran on that kernel alone (lash_timing::bases_last comes from its census)
     DevBuf st_seq, st_rec, st_img;       // staging for the synchronous host-buffer entries (files_raw, merge, pair statistics)
+    DevBuf fa_off, fa_scratch;           // lash_fasta_index[_device]: the file offsets; [masks | tile counts | tile bases] of fasta_index.hip
     // lash_sketch_batch[_async]: two staging slots and two copy streams, so that the H2D copy of batch n+1 and the D2H copy of
     // batch n-1 run while the kernels of batch n do (PCIe Gen5 moves 1 B/base: the host-buffer entry is link-bound)
     struct AsyncSlot { DevBuf seq, rec, img; hipEvent_t h2d = nullptr, kern = nullptr, d2h = nullptr; bool busy = false; };

@@ -1,0 +1,133 @@
+// lash_fasta_api.hip — the per-record entries of liblash_gfx950.so (include/lash_gfx950.h): lash_fasta_index[_device] and its accessors, the
+// device-side record index of raw multi-FASTA bytes (fasta_index.hip), and lash_sketch_records_raw, which hands a range of that index
+// to the raw-file route with records where it has files (`lash sketch --per-record`).
+#include "lash_ctx.h"
+#include "lash_internal.h"
+
+struct lash_rec_index {
+    int device = 0;
+    uint32_t n = 0, n_files = 0;
+    uint64_t total = 0;                          // bytes indexed == file_off[n_files]
+    DevBuf start, id_len, file;                  // [n + 1] u64, [n] u32, [n] u32
+    DevBuf raw;                                  // lash_fasta_index (host bytes): the device copy the index was made from, kept so that
+    const uint8_t *h_raw = nullptr;              // lash_sketch_records_raw on the same host buffer does not send the bytes again
+    mutable std::vector<uint64_t> h_start;       // host copy of start[], fetched by the first lash_sketch_records_raw
+};
+
+extern "C" {
+
+void lash_rec_index_free(lash_ctx *ctx, lash_rec_index *ix)
+{
+    if (!ix) return;
+    if (ctx) {
+        (void)hipSetDevice(ctx->device);
+        if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
+    }
+    for (DevBuf *b : {&ix->start, &ix->id_len, &ix->file, &ix->raw}) release(*b);
+    delete ix;
+}
+
+int lash_fasta_index_device(lash_ctx *ctx, const uint8_t *d_raw, const uint64_t *file_off, uint32_t n_files, lash_rec_index **out)
+{
+    if (!ctx || !out || !file_off || file_off[0] != 0) return LASH_EINVAL;
+    *out = nullptr;
+    for (uint32_t g = 0; g < n_files; ++g)
+        if (file_off[g + 1] < file_off[g]) return LASH_EINVAL;
+    const uint64_t total = file_off[n_files];
+    if (total && !d_raw) return LASH_EINVAL;
+    if (total >= (1ull << 33)) return LASH_ELIMIT;                 // record numbers are 32 bits wide
+    (void)hipSetDevice(ctx->device);
+    const uint32_t tb = fasta_index_tile_bytes(), n_tiles = (uint32_t)((total + tb - 1) / tb);
+    int rc;
+    if ((rc = reserve(ctx, ctx->fa_off, (size_t)(n_files + 1) * 8))) return rc;
+    if ((rc = reserve(ctx, ctx->fa_scratch, fasta_index_scratch_bytes(n_tiles)))) return rc;
+    if ((rc = upload(ctx, ctx->fa_off.ptr, file_off, (size_t)(n_files + 1) * 8))) return rc;
+    const uint64_t *d_off = static_cast<const uint64_t *>(ctx->fa_off.ptr);
+    uint8_t *scratch = static_cast<uint8_t *>(ctx->fa_scratch.ptr);
+    const uint32_t *d_two = nullptr;
+    HIPCHK(ctx, launch_fasta_mark(d_raw, total, d_off, n_files, n_tiles, scratch, &d_two, ctx->stream));
+    uint32_t two[2] = {0, 0};
+    HIPCHK(ctx, hipMemcpyAsync(two, d_two, 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    if (two[1]) { ctx->err = "lash_fasta_index: a file does not begin with '>' (FASTA only)"; return LASH_EINVAL; }
+    lash_rec_index *ix = new (std::nothrow) lash_rec_index();
+    if (!ix) return LASH_ENOMEM;
+    ix->device = ctx->device;
+    ix->n = two[0];
+    ix->n_files = n_files;
+    ix->total = total;
+    auto room = [&](DevBuf &b, size_t bytes) -> int {
+        HIPCHK(ctx, hipMalloc(&b.ptr, bytes));
+        b.cap = bytes;
+        return LASH_OK;
+    };
+    if ((rc = room(ix->start, ((size_t)ix->n + 1) * 8)) || (rc = room(ix->id_len, ((size_t)ix->n + 1) * 4)) ||
+        (rc = room(ix->file, ((size_t)ix->n + 1) * 4))) {
+        lash_rec_index_free(ctx, ix);
+        return rc;
+    }
+    const hipError_t e = launch_fasta_write(d_raw, total, d_off, n_files, n_tiles, scratch, ix->n, static_cast<uint64_t *>(ix->start.ptr),
+                                            static_cast<uint32_t *>(ix->file.ptr), static_cast<uint32_t *>(ix->id_len.ptr), ctx->stream);
+    if (e != hipSuccess) { lash_rec_index_free(ctx, ix); return fail(ctx, LASH_EHIP, "launch_fasta_write", e); }
+    *out = ix;
+    return LASH_OK;
+}
+
+int lash_fasta_index(lash_ctx *ctx, const uint8_t *raw, const uint64_t *file_off, uint32_t n_files, lash_rec_index **out)
+{
+    if (!ctx || !out || !file_off) return LASH_EINVAL;
+    *out = nullptr;
+    const uint64_t total = file_off[n_files];
+    if (total && !raw) return LASH_EINVAL;
+    (void)hipSetDevice(ctx->device);
+    DevBuf d{};                                                   // owned by the index from here on: one copy of the bytes per batch, not two
+    HIPCHK(ctx, hipMalloc(&d.ptr, total + 64));
+    d.cap = total + 64;
+    hipError_t e = total ? hipMemcpyAsync(d.ptr, raw, total, hipMemcpyHostToDevice, ctx->stream) : hipSuccess;
+    int rc = e == hipSuccess ? lash_fasta_index_device(ctx, static_cast<const uint8_t *>(d.ptr), file_off, n_files, out)
+                             : fail(ctx, LASH_EHIP, "hipMemcpyAsync", e);
+    if (rc) { (void)hipStreamSynchronize(ctx->stream); release(d); return rc; }
+    (*out)->raw = d;
+    (*out)->h_raw = raw;
+    return LASH_OK;
+}
+
+uint64_t lash_rec_index_n_records(const lash_rec_index *ix) { return ix ? ix->n : 0; }
+
+static int index_copy(lash_ctx *ctx, const lash_rec_index *ix, const DevBuf &b, void *dst, size_t bytes)
+{
+    if (!ctx || !ix || !dst || ctx->device != ix->device) return LASH_EINVAL;
+    (void)hipSetDevice(ctx->device);
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    if (bytes) HIPCHK(ctx, hipMemcpy(dst, b.ptr, bytes, hipMemcpyDeviceToHost));
+    return LASH_OK;
+}
+
+int lash_rec_index_start(lash_ctx *ctx, const lash_rec_index *ix, uint64_t *out) { return index_copy(ctx, ix, ix ? ix->start : DevBuf{}, out, ix ? ((size_t)ix->n + 1) * 8 : 0); }
+int lash_rec_index_id_len(lash_ctx *ctx, const lash_rec_index *ix, uint32_t *out) { return index_copy(ctx, ix, ix ? ix->id_len : DevBuf{}, out, ix ? (size_t)ix->n * 4 : 0); }
+int lash_rec_index_file(lash_ctx *ctx, const lash_rec_index *ix, uint32_t *out) { return index_copy(ctx, ix, ix ? ix->file : DevBuf{}, out, ix ? (size_t)ix->n * 4 : 0); }
+
+int lash_sketch_records_raw(lash_ctx *ctx, const lash_params *prm, const uint8_t *raw, const uint64_t *file_off, uint32_t n_files,
+                            const lash_rec_index *ix, uint64_t r0, uint64_t r1, uint8_t *out_images)
+{
+    if (!ctx || !ix || !file_off || r0 > r1 || r1 > ix->n || (r1 > r0 && (!raw || !out_images))) return LASH_EINVAL;
+    if (n_files != ix->n_files || file_off[n_files] != ix->total) return LASH_EINVAL;      // not the buffer the index was made from
+    int rc = lash_params_check(prm);
+    if (rc) return rc;
+    if (prm->flags & LASH_F_AMINO) return LASH_EINVAL;
+    if (ix->h_start.empty()) {
+        ix->h_start.resize((size_t)ix->n + 1);
+        if ((rc = lash_rec_index_start(ctx, ix, ix->h_start.data()))) { ix->h_start.clear(); return rc; }
+    }
+    // records [r0, r1) as the files of one raw call: a FASTA record is a well-formed FASTA file, and consecutive records are contiguous
+    // (a file ends where the next one's first record starts)
+    const uint32_t n = (uint32_t)(r1 - r0);
+    const std::vector<uint8_t> fmt(n, (uint8_t)LASH_FMT_FASTA);
+    if (ix->raw.ptr && ix->h_raw == raw && ix->device == ctx->device)      // the index holds these bytes on the device: offsets as they are
+        return files_raw_staged(ctx, prm, raw, static_cast<const uint8_t *>(ix->raw.ptr), ix->h_start.data() + r0, fmt.data(), n, out_images);
+    std::vector<uint64_t> off((size_t)n + 1);
+    for (uint32_t i = 0; i <= n; ++i) off[i] = ix->h_start[r0 + i] - ix->h_start[r0];
+    return lash_sketch_files_raw(ctx, prm, raw + ix->h_start[r0], off.data(), fmt.data(), n, out_images);
+}
+
+}  // extern "C"

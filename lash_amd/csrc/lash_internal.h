@@ -42,6 +42,8 @@ std::vector<uint32_t> hll_flagged(lash_ctx *ctx);
 // ---- lash_api.hip ---------------------------------------------------------------------------------------------------------------
 // needletail's record rules for uncompressed input as lash uses it (utils.rs:453-459), on the host: the exact path for the rare file the device
 // parse flags, and the streamed replay's
+int files_raw_staged(lash_ctx *ctx, const lash_params *prm, const uint8_t *raw, const uint8_t *d_raw, const uint64_t *file_off,
+                     const uint8_t *file_fmt, uint32_t n_files, uint8_t *out_images);
 size_t parse_fastx_strict(const uint8_t *d, size_t n, std::vector<uint8_t> *seq, std::vector<uint64_t> *rec_off, bool skip_bad = false,
                           std::vector<std::pair<size_t, size_t>> *bad = nullptr);
 

@@ -207,6 +207,16 @@ hipError_t launch_fastq_check(const uint8_t *d_raw, const FqFile *d_files, uint3
                               uint32_t *d_file_err, hipStream_t stream);
 size_t fastq_check_scratch_words(uint32_t n_files, uint32_t n_blocks);
 uint32_t fastq_check_block_bytes();
+// fasta_index.hip: the record index of raw multi-FASTA bytes (lash_fasta_index).  launch_fasta_mark queues the mark and scan kernels
+// and says where the record count and the "a file does not begin with '>'" flag will stand (two words, device); once the caller has
+// read the count and made room, launch_fasta_write queues the ordered write of start[n_records + 1] / file[] and the id_len[] walk.
+// d_file_off: n_files + 1 offsets, ascending from 0; d_scratch: fasta_index_scratch_bytes(n_tiles), n_tiles = tiles of `total` bytes.
+uint32_t fasta_index_tile_bytes();
+size_t fasta_index_scratch_bytes(uint32_t n_tiles);
+hipError_t launch_fasta_mark(const uint8_t *d_raw, uint64_t total, const uint64_t *d_file_off, uint32_t n_files, uint32_t n_tiles,
+                             uint8_t *d_scratch, const uint32_t **d_n_records_and_bad, hipStream_t stream);
+hipError_t launch_fasta_write(const uint8_t *d_raw, uint64_t total, const uint64_t *d_file_off, uint32_t n_files, uint32_t n_tiles,
+                              uint8_t *d_scratch, uint32_t n_records, uint64_t *d_start, uint32_t *d_file, uint32_t *d_id_len, hipStream_t stream);
 
 struct FinalizeArgs {
     const uint8_t  *partials;

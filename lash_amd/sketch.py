@@ -205,6 +205,34 @@ class Packed:
             pass
 
 
+class RecordIndex:
+    """Device-resident record index of raw multi-FASTA bytes (lash_rec_index*)."""
+
+    def __init__(self, ctx, handle):
+        self._ctx, self._h = ctx, handle
+        self.n_records = int(_lib.load().lash_rec_index_n_records(handle))
+
+    def arrays(self):
+        """(start[n + 1] u64, id_len[n] u32, file[n] u32), each one copy to the host"""
+        lib, n = _lib.load(), self.n_records
+        start, id_len, file = np.zeros(n + 1, np.uint64), np.zeros(n, np.uint32), np.zeros(n, np.uint32)
+        self._ctx._check(lib.lash_rec_index_start(self._ctx._h, self._h, start.ctypes.data))
+        self._ctx._check(lib.lash_rec_index_id_len(self._ctx._h, self._h, id_len.ctypes.data))
+        self._ctx._check(lib.lash_rec_index_file(self._ctx._h, self._h, file.ctypes.data))
+        return start, id_len, file
+
+    def free(self):
+        if self._h:
+            _lib.load().lash_rec_index_free(self._ctx._h, self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
 class Context:
     """One lash_ctx: a GPU, a stream and the HBM workspace.  Not thread-safe (like the C object)."""
 
@@ -317,6 +345,49 @@ class Context:
         self._check(self._lib.lash_sketch_files_raw(self._h, C.byref(prm), raw.ctypes.data if raw.size else None,
                                                     off.ctypes.data, fmt.ctypes.data if fmt.size else None,
                                                     len(files_bytes), out.ctypes.data if out.size else None))
+        return out
+
+    def fasta_index(self, raw, file_off, device=False, keep=False):
+        """lash_fasta_index: the records of raw multi-FASTA bytes, found on the GPU.  raw: uint8 array (or bytes) of the files back to
+        back — device=True: a device pointer / torch tensor; file_off: n_files + 1 byte offsets.  Returns (start[n + 1] u64,
+        id_len[n] u32, file[n] u32); keep=True returns a RecordIndex (for sketch_records_raw) instead."""
+        off = np.ascontiguousarray(file_off, dtype=np.uint64)
+        if not device:
+            raw = np.frombuffer(raw, dtype=np.uint8) if isinstance(raw, (bytes, bytearray)) else np.ascontiguousarray(raw, dtype=np.uint8)
+            assert raw.size >= int(off[-1])
+        h = C.c_void_p()
+        fn = self._lib.lash_fasta_index_device if device else self._lib.lash_fasta_index
+        rc = fn(self._h, _ptr(raw) if int(off[-1]) else None, off.ctypes.data, len(off) - 1, C.byref(h))
+        if rc == _lib.EINVAL:
+            raise LashError(rc, self._lib.lash_ctx_last_error(self._h).decode() or self._lib.lash_strerror(rc).decode())
+        self._check(rc)
+        ix = RecordIndex(self, h)
+        if keep:
+            return ix
+        try:
+            return ix.arrays()
+        finally:
+            ix.free()
+
+    def sketch_records_raw(self, algo, k, p, seed, raw, file_off, index=None, r0=0, r1=None, flags=0):
+        """lash_sketch_records_raw: one image per FASTA record of raw (host bytes), records [r0, r1) of `index` (a RecordIndex made
+        from the same raw / file_off; None: made here).  Returns images[r1 - r0, image_bytes]."""
+        prm = self._params(algo, k, p, seed, flags)
+        self._check(self._lib.lash_params_check(C.byref(prm)))
+        raw = np.frombuffer(raw, dtype=np.uint8) if isinstance(raw, (bytes, bytearray)) else np.ascontiguousarray(raw, dtype=np.uint8)
+        off = np.ascontiguousarray(file_off, dtype=np.uint64)
+        own = index is None
+        if own:
+            index = self.fasta_index(raw, off, keep=True)
+        try:
+            if r1 is None:
+                r1 = index.n_records
+            out = np.zeros((max(int(r1) - int(r0), 0), self.image_bytes(prm.algo, prm.p)), dtype=np.uint8)
+            self._check(self._lib.lash_sketch_records_raw(self._h, C.byref(prm), raw.ctypes.data if raw.size else None, off.ctypes.data,
+                                                          len(off) - 1, index._h, int(r0), int(r1), out.ctypes.data if out.size else None))
+        finally:
+            if own:
+                index.free()
         return out
 
     def format_errors(self):
