@@ -782,3 +782,70 @@ void lash_or_synth_genome(uint64_t genome, uint64_t n_bases, uint8_t *out_ascii)
         for (uint64_t j = 0; j < lim; j++) out_ascii[i + j] = (uint8_t)acgt[(w >> (2 * j)) & 3];
     }
 }
+
+/* ------------------------------------------------------------------------------------------
+ * Search for HyperMinHash inputs of high rank (tests/golden/make_hmh_rare_ranks.py).  xxh3_128 of 4 bytes
+ * cannot be inverted, but its domain is 2^32 values: hash all of them with the function above and keep
+ * those whose x half has at least min_lzm1 leading zeros below the bucket bits (hmh_add_hash's lz - 1).
+ * Every thread scans one contiguous range and keeps its own list; the lists are joined in range order,
+ * so the output is ascending in w whatever the number of threads.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct {
+    uint64_t seed, w0, w1; int x_is_low; unsigned min_lzm1;
+    uint32_t *w, *reg; uint64_t n, room; int err;
+} search_job;
+
+static void *search_worker(void *arg)
+{
+    search_job *j = (search_job *)arg;
+    for (uint64_t w = j->w0; w < j->w1; w++) {
+        uint64_t lo, hi;
+        lash_or_xxh3_128_4b((uint32_t)w, j->seed, &lo, &hi);
+        const uint64_t x = j->x_is_low ? lo : hi, y = j->x_is_low ? hi : lo;
+        const unsigned lzm1 = (unsigned)__builtin_clzll((x << HMH_P) ^ 0x3FFFULL);
+        if (lzm1 < j->min_lzm1) continue;
+        if (j->n == j->room) {
+            const uint64_t room = j->room ? 2 * j->room : 1024;
+            uint32_t *nw = (uint32_t *)realloc(j->w, room * 4), *nr = (uint32_t *)realloc(j->reg, room * 4);
+            if (nw) j->w = nw;
+            if (nr) j->reg = nr;
+            if (!nw || !nr) { j->err = -1; return NULL; }
+            j->room = room;
+        }
+        j->w[j->n] = (uint32_t)w;
+        j->reg[j->n++] = (uint32_t)(x >> (64 - HMH_P)) << 16 | (lzm1 + 1) << HMH_R | (uint32_t)(y & ((1u << HMH_R) - 1));
+    }
+    return NULL;
+}
+
+int64_t lash_or_hmh_rank_search(uint64_t seed, int x_is_low, int min_lzm1, uint32_t *out_w, uint32_t *out_reg, uint64_t cap, int threads)
+{
+    if (min_lzm1 < 0 || min_lzm1 > 50) return -1;
+    if (threads < 1) threads = 1;
+    if (threads > 256) threads = 256;
+    pthread_t th[256];
+    search_job *jobs = (search_job *)calloc((size_t)threads, sizeof(search_job));
+    if (!jobs) return -1;
+    const uint64_t span = ((1ULL << 32) + (uint64_t)threads - 1) / (uint64_t)threads;
+    for (int t = 0; t < threads; t++) {
+        uint64_t w0 = span * (uint64_t)t, w1 = w0 + span;
+        if (w0 > (1ULL << 32)) w0 = 1ULL << 32;
+        if (w1 > (1ULL << 32)) w1 = 1ULL << 32;
+        jobs[t].seed = seed; jobs[t].w0 = w0; jobs[t].w1 = w1; jobs[t].x_is_low = x_is_low; jobs[t].min_lzm1 = (unsigned)min_lzm1;
+        if (threads == 1) search_worker(&jobs[t]);
+        else pthread_create(&th[t], NULL, search_worker, &jobs[t]);
+    }
+    int64_t total = 0;
+    for (int t = 0; t < threads; t++) {
+        if (threads > 1) pthread_join(th[t], NULL);
+        if (jobs[t].err) total = -1;
+        for (uint64_t i = 0; i < jobs[t].n && total >= 0; i++, total++) {
+            if ((uint64_t)total >= cap) continue;
+            if (out_w) out_w[total] = jobs[t].w[i];
+            if (out_reg) out_reg[total] = jobs[t].reg[i];
+        }
+        free(jobs[t].w); free(jobs[t].reg);
+    }
+    free(jobs);
+    return total;
+}

@@ -119,6 +119,13 @@ int      lash_or_merge_images_layout(const lash_or_layout *lay, int algo, int p,
 int      lash_or_sketch_file_buffers(const lash_or_params *prm, const uint8_t *const *bufs, const uint64_t *lens,
                                      uint32_t n_files, uint8_t *images, int threads);
 
+/* Every 32-bit input w of the HyperMinHash rule (xxh3_128 of w's 4 bytes under `seed`; x = the high half, or the low one if
+ * x_is_low) whose rank lz - 1 = clz64((x << 14) ^ 0x3FFF) is at least min_lzm1, ascending in w: all 2^32 inputs are hashed, over
+ * `threads` threads (the result does not depend on their number).  out_w[i] = w and out_reg[i] = bucket << 16 | lz << 10 | sig for the
+ * first `cap` of them (either may be NULL); returns how many there are, or -1.  For tests/golden/make_hmh_rare_ranks.py: random
+ * genomes never hold the ranks that the kernels' rarest paths are written for. */
+int64_t  lash_or_hmh_rank_search(uint64_t seed, int x_is_low, int min_lzm1, uint32_t *out_w, uint32_t *out_reg, uint64_t cap, int threads);
+
 /* Synthetic genome generator of SURVEY.md §8(d): base i of genome g. */
 void     lash_or_synth_genome(uint64_t genome, uint64_t n_bases, uint8_t *out_ascii);
 

@@ -101,6 +101,8 @@ def _load():
     lib.lash_or_sketch_file_buffers.argtypes = [C.POINTER(Params), C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_int]
     lib.lash_or_synth_genome.restype = None
     lib.lash_or_synth_genome.argtypes = [C.c_uint64, C.c_uint64, C.c_void_p]
+    lib.lash_or_hmh_rank_search.restype = C.c_int64
+    lib.lash_or_hmh_rank_search.argtypes = [C.c_uint64, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int]
     return lib
 
 
@@ -201,3 +203,31 @@ def synth_genome(g: int, n: int) -> np.ndarray:
     out = np.empty(n, dtype=np.uint8)
     lib.lash_or_synth_genome(g, n, out.ctypes.data)
     return out
+
+
+def hmh_rank_search(seed, x_is_low, min_lzm1, threads=16):
+    """Every 32-bit input whose HyperMinHash rank lz - 1 under `seed` is at least min_lzm1 (all 2^32 are hashed: seconds), ascending:
+    (w, bucket << 16 | lz << 10 | sig) as two uint32 arrays.  Used by tests/golden/make_hmh_rare_ranks.py only."""
+    cap = (1 << 33 - min_lzm1) + 4096 if min_lzm1 < 32 else 4096                  # expected 2^(32 - min_lzm1), twice that and some
+    w, reg = np.empty(cap, np.uint32), np.empty(cap, np.uint32)
+    n = int(lib.lash_or_hmh_rank_search(seed & (2**64 - 1), int(bool(x_is_low)), int(min_lzm1), w.ctypes.data, reg.ctypes.data, cap, threads))
+    if n < 0 or n > cap:
+        raise ValueError("hmh_rank_search: %d results for room of %d" % (n, cap))
+    return w[:n].copy(), reg[:n].copy()
+
+
+def hmh_rank(w, seed, x_is_low=False):
+    """(bucket, lz - 1, signature) of the 32-bit HyperMinHash input w: what hmh_add_hash makes of the oracle's xxh3_128."""
+    lo, hi = xxh3_128_4b(w, seed)
+    x, y = (lo, hi) if x_is_low else (hi, lo)
+    return x >> 50, 64 - (((x << 14) & (2**64 - 1)) ^ 0x3FFF).bit_length(), y & 0x3FF
+
+
+def hmh_rare_ranks():
+    """tests/golden/hmh_rare_ranks.json (made by make_hmh_rare_ranks.py): its groups, `w` as a list of ints"""
+    import json
+    with open(os.path.join(_ROOT, "tests", "golden", "hmh_rare_ranks.json")) as f:
+        groups = json.load(f)["groups"]
+    for g in groups:
+        g["w"] = [int(t, 16) for t in g["w"].split()]
+    return groups
