@@ -79,33 +79,37 @@ LASH_HD double small_range_z(double c0, double c4, double c8, double c10, double
     return x2 * x2;
 }
 
-// saturated registers (largest representable update value 65 - p; r = 252 + low bits), as published in hash4j
-// [restated from memory of the published code; unreachable for inputs below ~2^50 distinct elements]
+// saturated registers (largest representable update value K = 65 - p; r = 252 + low bits: bit 1 = K-1 seen, bit 0 = K-2
+// seen).  Every ideal update value >= K lands on K, so K has the rate of K-1.  With q_j = e^(-lambda 2^-(K+j)) ("K+j not
+// seen", q_j = q_(j-1)^(1/2)) and y = q_(-1) = e^(-lambda 2^-(K-1)), a register is not saturated with probability y and holds
+// 252..255 with probabilities (1-y) * {y y^2, y (1-y^2), (1-y) y^2, (1-y)(1-y^2)}: the likelihood equation of these five
+// classes, times y (1 - y^2), is  alpha y^2 + beta y - gamma = 0.  Returns z = q_0 = sqrt(y).
+// Pinned by tests/test_ull_reference.py: sketches sampled from the Poisson model with 2 % to 50 % of their registers
+// saturated give unbiased FGRA and ML estimates, and FGRA equals the series of tests/ullref.py summed in 60 digits.
 LASH_HD double large_range_z(double w0, double w1, double w2, double w3, double m)
 {
     const double alpha = m + 3.0 * (w0 + w1 + w2 + w3), beta = w0 + w1 + 2.0 * (w2 + w3), gamma = m + 2.0 * w0 + w2 - w3;
     return sqrt((sqrt(beta * beta + 4.0 * alpha * gamma) - beta) / (2.0 * alpha));
 }
-LASH_HD double phi(double z, double z_square)
+// The ideal (uncapped) register of a saturated one has largest value K + j with probability (1 - q_j) q_j / (1 - q_0^2)
+//   = q_j / ((1 + q_0)(1 + q_1) ... (1 + q_j))          (1 - q_0 = (1 - q_j)(1 + q_1) ... (1 + q_j)),
+// weight 2^(-tau (K + j)).  j = 0 and j = 1 still see observed bits and are written out in fgra(); from j = 2 on both bits
+// are unknown, eta averages to psi(q_(j-1)), and
+//   phi(q_1) = (1 + q_1) * sum_(j >= 2) 2^(-tau j) psi(q_(j-1)) q_j / ((1 + q_1) ... (1 + q_j));
+// the terms fall like 2^-(1 + tau) each.  fgra() divides by (1 + q_1)(1 + q_0) and multiplies by 2^(-tau K).
+LASH_HD double phi(double q1)
 {
     const double pow2_mtau = pow(2.0, -TAU);
-    if (z <= 0.0) return 0.0;
-    if (z >= 1.0) return ETA_0 / (pow(2.0, TAU) * (2.0 * pow(2.0, TAU) - 1.0));
-    double prev = z_square, pz = z, next = sqrt(pz);
-    double pr = ETA_X * (pow(4.0, -TAU) / (2.0 - pow2_mtau)) / (1.0 + next);
-    double ps = psi(pz) / 1.0;
-    (void)prev;
-    double s = next * (ps + ps) * pr;
+    if (q1 <= 0.0) return 0.0;
+    if (q1 >= 1.0) return ETA_0 / (pow(2.0, TAU) * (2.0 * pow(2.0, TAU) - 1.0));
+    double cur = q1, w = pow2_mtau * pow2_mtau, s = 0.0;
     for (;;) {
-        prev = pz;
-        pz = next;
-        const double old = s;
-        next = sqrt(pz);
-        const double nps = psi(pz);
-        pr *= pow2_mtau / (1.0 + next);
-        s += next * ((nps + nps) - (pz + next) * ps) * pr;
+        const double next = sqrt(cur), old = s;
+        w /= 1.0 + next;
+        s += w * next * psi(cur);
         if (!(s > old)) return s;
-        ps = nps;
+        cur = next;
+        w *= pow2_mtau;
     }
 }
 
@@ -142,7 +146,7 @@ LASH_HD double fgra(const Hist &hist, int p)
         if (w0 > 0.0 || w1 > 0.0 || w2 > 0.0 || w3 > 0.0) {
             const double z = large_range_z(w0, w1, w2, w3, m), root_z = sqrt(z);
             const double q = pow(2.0, -TAU);
-            double s = phi(root_z, z) * (w0 + w1 + w2 + w3);
+            double s = phi(root_z) * (w0 + w1 + w2 + w3);
             s += z * (1.0 + root_z) * (w0 * ETA_0 + w1 * ETA_1 + w2 * ETA_2 + w3 * ETA_3);
             s += root_z * ((w0 + w1) * (z * q * (ETA_0 - ETA_2) + q * ETA_2) + (w2 + w3) * (z * q * (ETA_1 - ETA_3) + q * ETA_3));
             sum += s * pow(q, (double)(65 - p)) / ((1.0 + root_z) * (1.0 + z));

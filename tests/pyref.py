@@ -333,11 +333,31 @@ def _ull_expected_eta(q1, q2):
     return q1 * q2 * e[0] + q1 * (1 - q2) * e[1] + (1 - q1) * q2 * e[2] + (1 - q1) * (1 - q2) * e[3]
 
 
+def _ull_saturated_eta(t, b1, b2):
+    """E[eta_bits 2^(-tau j)] of a saturated register's ideal (uncapped) state at t = e^(-lambda 2^-K): the largest ideal value is
+    K + j with probability proportional to (1 - q_j) q_j, q_j = t^(2^-j); its bits are the observed ones for j = 0, an unknown
+    bit for K and the observed bit of K-1 for j = 1, both unknown from j = 2 on"""
+    if t <= 0.0:
+        return 0.0
+    q = lambda j: t ** (2.0 ** -j)
+    wj = lambda j: -math.expm1(math.log(t) * 2.0 ** -j) * q(j)
+    num = wj(0) * ULL_ETA[(b1 << 1) | b2] + 2.0 ** -ULL_TAU * wj(1) * (t * ULL_ETA[b1] + (1 - t) * ULL_ETA[2 | b1])
+    den = wj(0) + wj(1)
+    for j in range(2, 80):
+        num += 2.0 ** (-ULL_TAU * j) * wj(j) * _ull_expected_eta(q(j - 1), q(j - 2))
+        den += wj(j)
+    return num / den
+
+
 def ull_fgra(regs, p):
     m = 1 << p
     K = 65 - p
-    if any(_ull_state(r, p) and _ull_state(r, p)[0] >= K for r in regs):
-        raise NotImplementedError("saturated registers: not reachable in tests")
+    w = [sum(1 for r in regs if r == 252 + low) for low in range(4)]
+    t = None
+    if any(w):
+        # saturated (u = K): y = e^(-lambda 2^-(K-1)) from the likelihood of the classes {not saturated, 252, 253, 254, 255}
+        al, be, ga = m + 3 * sum(w), w[0] + w[1] + 2 * (w[2] + w[3]), m + 2 * w[0] + w[2] - w[3]
+        t = math.sqrt((math.sqrt(be * be + 4 * al * ga) - be) / (2 * al))            # e^(-lambda 2^-K)
     c0 = sum(1 for r in regs if r == 0)
     c4 = sum(1 for r in regs if r == 4 * p - 4)
     c8 = sum(1 for r in regs if r == 4 * p)
@@ -365,13 +385,18 @@ def ull_fgra(regs, p):
             total += s
             continue
         u, b1, b2 = st
-        w = 2.0 ** (-ULL_TAU * u)
+        if u >= K:
+            total += 2.0 ** (-ULL_TAU * K) * _ull_saturated_eta(t, b1, b2)
+            continue
+        wt = 2.0 ** (-ULL_TAU * u)
         if u >= 3:
-            total += w * ULL_ETA[(b1 << 1) | b2]
+            total += wt * ULL_ETA[(b1 << 1) | b2]
         elif u == 2:                                            # bit for u-2 = virtual value 0: unseen with probability z
-            total += w * (z * ULL_ETA[b1 << 1] + (1 - z) * ULL_ETA[(b1 << 1) | 1])
+            total += wt * (z * ULL_ETA[b1 << 1] + (1 - z) * ULL_ETA[(b1 << 1) | 1])
         else:                                                   # u == 1: both lower bits virtual (values 0 and -1)
-            total += w * _ull_expected_eta(z, z * z)
+            total += wt * _ull_expected_eta(z, z * z)
+    if total == 0.0:
+        return math.inf                                         # every register 255
     factor = m ** (1 + 1 / ULL_TAU) / (1 + ULL_V * (1 + ULL_TAU) / (2 * m))
     return factor * total ** (-1 / ULL_TAU)
 

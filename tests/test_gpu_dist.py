@@ -268,14 +268,16 @@ def test_ull_pair_union_estimates_match_host_estimators(p):
     empty = imgs[:1].copy()
     empty[0, 8:] = 0
     ref = np.concatenate([imgs, empty])
-    for est, tol in (("fgra", 1e-9), ("ml", 2e-4)):
+    # both sides round differently: FGRA (m + 1024) 2^-52, ML twice the solver's stopping step (tests/test_gpu_ull_pairs.py
+    # compares the same kernels with a reference that does not share ull_estimators.h)
+    for est, tol in (("fgra", ((1 << p) + 1024) * 2.0 ** -52), ("ml", 2 * 0.001 * 0.7608621002725182 / (1 << p) ** 0.5)):
         got = ctx.ull_pair_union_estimates(p, ref, imgs, estimator=est)
         assert got.shape == (len(ref), len(imgs))
         for i in range(len(ref)):
             for j in range(len(imgs)):
                 merged = O.merge_images(O.ULL, p, ref[i], imgs[j])
                 want = lash_amd.ull_estimate(merged[8:], p, est)
-                assert got[i, j] == pytest.approx(want, rel=tol, abs=1e-9), (p, est, i, j)
+                assert got[i, j] == pytest.approx(want, rel=tol, abs=0.0), (p, est, i, j)
         # a sketch merged with itself is itself
         for j in range(len(imgs)):
             assert got[j, j] == pytest.approx(lash_amd.ull_estimate(imgs[j][8:], p, est), rel=tol)
