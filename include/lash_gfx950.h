@@ -480,6 +480,36 @@ int      lash_sketch_set_pair_block_cluster(lash_ctx *ctx, const lash_sketch_set
 int      lash_cluster_merge(lash_cluster *dst, const lash_cluster *src);
 int      lash_cluster_labels(const lash_cluster *c, uint32_t *out);
 
+/* pair_block_derep: `lash dist --derep D`, greedy representatives of a triangle run (rows and columns are the same names in the same
+ * order, which is the priority order).  Two names are WITHIN max_dist iff pair_block_within with the same arguments returns their
+ * pair: the exact d passes d <= max_dist, NaN never; the diagonal plays no part.  Name i is a representative iff no representative
+ * j < i is within max_dist of it, and otherwise a member of the FIRST such j in row order (not the nearest; not transitive).  The block
+ * runs as pair_block_within with triangle = 1 (statistics, expected collisions), then a mark kernel and a trim kernel
+ * (dist_derep.hip): a column of an earlier block that is not a representative is pruned before any arithmetic, a pair that is surely
+ * farther than max_dist is dropped, the first column of an earlier block that is surely within it is recorded per row and every pair
+ * beyond it is cleared, and what is left comes back: that hit, the pairs before it the device cannot decide (within the margin of
+ * max_dist, or host-only arithmetic), and for a row without such a hit its in-block candidates too.  They are walked here row by row,
+ * in column order, with the exact arithmetic, each row stopping at its first representative within max_dist.  LASH_ERANGE with
+ * *bad_pair (as pair_block_within) iff that walk meets a pair the arithmetic refuses before the row stops; pairs beyond a row's
+ * stop do not matter.  Blocks depend on each other: they must arrive in row order, contiguous from 0, on one accumulator.
+ * LASH_EINVAL: max_dist NaN, r0 not the number of rows decided so far, r1 or n_cols beyond the accumulator's n, n_cols < r1, an
+ * accumulator of another device.
+ * lash_derep:
+ *   create   n names, all undecided; rep[] lives on ctx's device with a mirror on the host
+ *   result   out[i] = i for a representative, else the representative i is a member of, for all n; LASH_EINVAL before every name
+ *            is decided
+ * stats (may be NULL), per call: pairs = the block's printed off-diagonal pairs; pruned_not_rep = columns skipped without a distance;
+ * pruned_after_hit = mask bits the trim cleared; sent_to_host = the pairs that came back; evaluated = those the walk computed;
+ * representatives = the accumulator's count after the block. */
+typedef struct lash_derep lash_derep;
+typedef struct lash_derep_stats { uint64_t pairs, pruned_not_rep, pruned_after_hit, sent_to_host, evaluated, representatives; } lash_derep_stats;
+int      lash_derep_create(lash_ctx *ctx, uint32_t n, lash_derep **out);
+void     lash_derep_free(lash_derep *d);
+int      lash_sketch_set_pair_block_derep(lash_ctx *ctx, const lash_sketch_set *ref, uint32_t r0, uint32_t r1, const lash_sketch_set *qry,
+                                          uint32_t n_cols, int k, int model, int fp32, int ull_estimator, const lash_hll_bias *tables,
+                                          double max_dist, lash_derep *acc, lash_derep_stats *stats, uint64_t *bad_pair);
+int      lash_derep_result(const lash_derep *d, uint32_t *out);
+
 /* HyperMinHash sets: hyperminhash's expected_collisions(n, m) for the pairs of a block in which BOTH sketches hold at most 2^19
  * distinct k-mers (the regime in which the crate walks 65 536 cells per pair; lash_hmh_pair_expected_collisions below):
  * out_ec[(r - r0) * n_cols + c] for exactly those pairs — the other entries are left untouched, lash_dist_rows derives theirs in

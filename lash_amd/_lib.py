@@ -41,6 +41,12 @@ class ClusterStats(C.Structure):
                 ("clusters", C.c_uint64)]
 
 
+class DerepStats(C.Structure):
+    """lash_derep_stats: what one pair_block_derep call did"""
+    _fields_ = [("pairs", C.c_uint64), ("pruned_not_rep", C.c_uint64), ("pruned_after_hit", C.c_uint64), ("sent_to_host", C.c_uint64),
+                ("evaluated", C.c_uint64), ("representatives", C.c_uint64)]
+
+
 _vp, _u64, _u32, _int = C.c_void_p, C.c_uint64, C.c_uint32, C.c_int
 _PP = C.POINTER(Params)
 _LP = C.POINTER(Layout)
@@ -134,6 +140,11 @@ PROTOTYPES = {
                                                    C.POINTER(ClusterStats), C.POINTER(_u64)]),
     "lash_cluster_merge": (_int, [_vp, _vp]),
     "lash_cluster_labels": (_int, [_vp, _vp]),
+    "lash_derep_create": (_int, [_vp, _u32, C.POINTER(_vp)]),
+    "lash_derep_free": (None, [_vp]),
+    "lash_sketch_set_pair_block_derep": (_int, [_vp, _vp, _u32, _u32, _vp, _u32, _int, _int, _int, _int, _vp, C.c_double, _vp,
+                                                 C.POINTER(DerepStats), C.POINTER(_u64)]),
+    "lash_derep_result": (_int, [_vp, _vp]),
     "lash_synth_genomes_device": (_int, [_vp, _u64, _u32, _u64, _vp]),
 }
 

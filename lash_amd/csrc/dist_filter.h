@@ -1,6 +1,6 @@
-// dist_filter.h — what the pair filters of `lash dist` share: --max-dist (dist_filter.hip), --top (dist_top.hip) and --cluster
-// (dist_cluster.hip).  The block's statistics as the filter kernels read them, the device similarity of one pair and the interval
-// it puts around the host's distance (with the error analysis), the tile loop of the three mark kernels with the mask layout the
+// dist_filter.h — what the pair filters of `lash dist` share: --max-dist (dist_filter.hip), --top (dist_top.hip), --cluster
+// (dist_cluster.hip) and --derep (dist_derep.hip).  The block's statistics as the filter kernels read them, the device similarity of one pair and the interval
+// it puts around the host's distance (with the error analysis), the tile loop of the mark kernels with the mask layout the
 // scan / write kernels compact in (row, col) order, and the host's exact evaluation of what comes back.
 #pragma once
 #include "lash_ctx.h"
@@ -183,24 +183,32 @@ int within_block(lash_ctx *ctx, const lash_sketch_set *ref, uint32_t r0, uint32_
 // candidates with their statistics in (row, col) order, copied back into `cand` (synchronous; dist_filter.hip's scan and write kernels)
 int within_compact(lash_ctx *ctx, const WithinArgs &a, const uint64_t *d_mask, const uint32_t *d_cnt, uint64_t *d_off, std::vector<WithinPair> &cand);
 
-// exact: the candidates in order (row-major) through the host arithmetic of lash_dist_rows, each handed to each(set row, col, d, block
-// row).  LASH_ERANGE at the first pair that arithmetic refuses (the one an unfiltered run reports), with *bad_pair = its place in the
-// block; the pairs before it have been handed over.
+// exact: one candidate of the block whose first row is r0 through the host arithmetic of lash_dist_rows.  false: that arithmetic
+// refuses the pair (the HLL++ bias-table regime without tables) and *d is not set.
+inline bool filter_pair_host(const WithinPair &w, const lash_sketch_set *ref, uint32_t r0, const lash_sketch_set *qry, int k, int model, int fp32,
+                             const lash_hll_bias *tables, double *d)
+{
+    const int algo = ref->algo;
+    double ec;
+    const double *ecp = nullptr;
+    if (algo == LASH_HMH && !std::isnan(w.ec_x)) { ec = hmh_ec_from_cell_sum(w.ec_x); ecp = &ec; }
+    return dist_pair_host(algo, ref->p, k, model, fp32, ref->card[r0 + w.row], qry->card[w.col], w.c_or_zero, w.n, w.sum_or_union, tables, ecp, d);
+}
+
+// exact: the candidates in order (row-major) through filter_pair_host, each handed to each(set row, col, d, block row).  LASH_ERANGE
+// at the first pair that arithmetic refuses (the one an unfiltered run reports), with *bad_pair = its place in the block; the pairs
+// before it have been handed over.
 template <class Each>
 int filter_evaluate(const std::vector<WithinPair> &cand, const lash_sketch_set *ref, uint32_t r0, const lash_sketch_set *qry, uint32_t n_cols, int k,
                     int model, int fp32, const lash_hll_bias *tables, uint64_t *bad_pair, Each each)
 {
-    const int algo = ref->algo;
     for (const WithinPair &w : cand) {
-        const uint32_t row = r0 + w.row;
-        double ec, d;
-        const double *ecp = nullptr;
-        if (algo == LASH_HMH && !std::isnan(w.ec_x)) { ec = hmh_ec_from_cell_sum(w.ec_x); ecp = &ec; }
-        if (!dist_pair_host(algo, ref->p, k, model, fp32, ref->card[row], qry->card[w.col], w.c_or_zero, w.n, w.sum_or_union, tables, ecp, &d)) {
+        double d;
+        if (!filter_pair_host(w, ref, r0, qry, k, model, fp32, tables, &d)) {
             if (bad_pair) *bad_pair = (uint64_t)w.row * n_cols + w.col;
             return LASH_ERANGE;
         }
-        each(row, w.col, d, w.row);
+        each(r0 + w.row, w.col, d, w.row);
     }
     return LASH_OK;
 }

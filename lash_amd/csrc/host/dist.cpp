@@ -25,6 +25,9 @@
 // --cluster D (not upstream; same files only): single-linkage clusters, two names being linked iff --max-dist D prints their pair.  A
 // block's pairs are joined in a label array on the device (lash_sketch_set_pair_block_cluster, one lash_cluster per worker, merged at the
 // end); no pair text at all, the N lines "representative<TAB>member" are written once, at the end.
+// --derep D (not upstream; same files only): greedy representatives in row order, "within D" meaning that --max-dist D prints the pair.
+// A row is decided from the representatives among the rows before it (lash_sketch_set_pair_block_derep, one lash_derep), so the blocks
+// run in row order on one worker; the N lines are written once, at the end.
 #include "dist.hpp"
 
 #include <dirent.h>
@@ -148,6 +151,8 @@ std::string load_input(const DistOptions &opt, const Timing &timing, DistInput &
     in.same_sketches = rf["sketches"] == qf["sketches"];                                              // all-vs-all: one file, read once
     if (opt.has_cluster && !(in.same_files && in.same_sketches))
         return "--cluster needs an all-vs-all run: -q and -r must name the same sketch files";
+    if (opt.has_derep && !(in.same_files && in.same_sketches))
+        return "--derep needs an all-vs-all run: -q and -r must name the same sketch files";
     // utils.rs:111-127: the maps' key order (a repeated name is one entry carrying its last sketch)
     if (opt.file_order) {
         in.rorder.resize(in.rnames.size()); std::iota(in.rorder.begin(), in.rorder.end(), 0u);
@@ -279,7 +284,10 @@ struct Run {
     // --cluster: per worker, the clusters joined by the blocks it ran (created by the worker: the labels live on its device)
     std::vector<lash_cluster *> clusters;
     std::atomic<uint64_t> cl_pairs{0}, cl_pruned{0}, cl_joined{0}, cl_sent{0};   // (LASH_CLI_TIMING)
-    ~Run() { for (lash_top *p : tops) lash_top_free(p); for (lash_cluster *p : clusters) lash_cluster_free(p); if (out) fclose(out); }
+    // --derep: the one worker's accumulator (created by it: rep[] lives on its device)
+    lash_derep *derep = nullptr;
+    lash_derep_stats dr{};                                       // (LASH_CLI_TIMING: summed over the blocks; representatives: the last block's)
+    ~Run() { for (lash_top *p : tops) lash_top_free(p); for (lash_cluster *p : clusters) lash_cluster_free(p); lash_derep_free(derep); if (out) fclose(out); }
 };
 
 struct Block { uint32_t i0, i1, n_cols; };
@@ -353,6 +361,21 @@ struct Worker {
         return block_failure(b, rc, bad);
     }
 
+    // --derep: pair statistics, expected collisions, mark and trim on the device; the library walks what comes back.  One worker, so
+    // the blocks arrive in row order
+    std::string block_derep(const Block &b)
+    {
+        uint64_t bad = 0;
+        lash_derep_stats st;
+        const int rc = lash_sketch_set_pair_block_derep(ctx, ds->ref, b.i0, b.i1, ds->qry, b.n_cols, in.k, opt.model, opt.fp32 ? 1 : 0, in.ull_est, run.bias,
+                                                        opt.derep_dist, run.derep, &st, &bad);
+        if (rc == LASH_OK) {
+            run.dr.pairs += st.pairs; run.dr.pruned_not_rep += st.pruned_not_rep; run.dr.pruned_after_hit += st.pruned_after_hit;
+            run.dr.sent_to_host += st.sent_to_host; run.dr.evaluated += st.evaluated; run.dr.representatives = st.representatives;
+        }
+        return block_failure(b, rc, bad);
+    }
+
     // --max-dist: pair statistics, expected collisions and the cutoff on the device; only the survivors come back
     std::string block_within(const Block &b)
     {
@@ -405,6 +428,7 @@ struct Worker {
         int rc = lash_ctx_create(&ctx, run.devices[wi]);
         if (rc == LASH_OK) rc = lash_ctx_set_layout(ctx, &opt.layout);
         if (rc == LASH_OK && opt.has_cluster) rc = lash_cluster_create(ctx, in.nr, &run.clusters[wi]);
+        if (rc == LASH_OK && opt.has_derep) rc = lash_derep_create(ctx, in.nr, &run.derep);
         std::string my_fail = rc == LASH_OK ? "" : std::string(lash_strerror(rc));
         const uint32_t n_blocks = (uint32_t)run.block_begin.size() - 1;
         for (;;) {
@@ -416,7 +440,8 @@ struct Worker {
             { std::lock_guard<std::mutex> lk(run.wmu); skip = !run.fail.empty(); }
             row_text.off.clear(); row_text.len.clear();
             if (my_fail.empty() && !skip)
-                my_fail = opt.top ? block_top(b) : opt.has_cluster ? block_cluster(b) : opt.has_max_dist ? block_within(b) : block_all(b);
+                my_fail = opt.top ? block_top(b) : opt.has_cluster ? block_cluster(b) : opt.has_derep ? block_derep(b)
+                          : opt.has_max_dist ? block_within(b) : block_all(b);
             std::unique_lock<std::mutex> lk(run.wmu);
             run.wcv.wait(lk, [&] { return run.next_to_write == blk; });
             if (!my_fail.empty() && run.fail.empty()) run.fail = my_fail;
@@ -481,6 +506,31 @@ std::string finish_cluster(Run &run)
     return "";
 }
 
+// --derep: every name under its representative, in row order of the representative, then of the member (a representative is below
+// every member of its own, so it comes first)
+std::string finish_derep(Run &run)
+{
+    const DistInput &in = run.in;
+    std::vector<uint32_t> rep(in.nr);
+    if (in.nr && (!run.derep || lash_derep_result(run.derep, rep.data()) != LASH_OK)) return "cannot read the --derep representatives";
+    std::vector<uint32_t> by_rep(in.nr);
+    std::iota(by_rep.begin(), by_rep.end(), 0u);
+    std::stable_sort(by_rep.begin(), by_rep.end(), [&](uint32_t x, uint32_t y) { return rep[x] < rep[y]; });
+    std::string text;
+    for (uint32_t i : by_rep) {
+        text.append(in.row_name[rep[i]]).push_back('\t');
+        text.append(in.row_name[i]).push_back('\n');
+        if (text.size() >= (1u << 20)) { fwrite(text.data(), 1, text.size(), run.out); text.clear(); }
+    }
+    fwrite(text.data(), 1, text.size(), run.out);
+    if (run.timing.on) fprintf(stderr, "[lash dist] --derep: %llu pairs looked at, %llu pruned as not a representative, %llu pruned after a sure hit, "
+                               "%llu sent to the host, %llu evaluated, %llu representatives\n", (unsigned long long)run.dr.pairs,
+                               (unsigned long long)run.dr.pruned_not_rep, (unsigned long long)run.dr.pruned_after_hit,
+                               (unsigned long long)run.dr.sent_to_host, (unsigned long long)run.dr.evaluated, (unsigned long long)run.dr.representatives);
+    run.timing.mark("--derep: the representatives written");
+    return "";
+}
+
 }  // namespace
 
 std::string run_dist(const DistOptions &opt)
@@ -502,6 +552,10 @@ std::string run_dist(const DistOptions &opt)
     DeviceSets dev;
     Run run{opt, in, dev, bias, timing};
     run.devices = opt.devices.empty() ? std::vector<int>{opt.device, opt.device} : opt.devices;
+    if (opt.has_derep) {                                                                              // blocks depend on each other in row order
+        if (opt.devices.size() > 1) return "--derep runs its blocks in row order on one worker: --devices must name one device";
+        run.devices.resize(1);
+    }
     if (!(err = make_device_sets(opt, in, run.devices, bias, dev)).empty()) return err;
     timing.mark("sketches resident on the device(s), cardinalities, pair-kernel operands");
     // hyperminhash's expected collisions need the GPU only when some pair has both sketches at or below 2^19 distinct k-mers
@@ -513,7 +567,7 @@ std::string run_dist(const DistOptions &opt)
     run.gpu_ec = small_ref && small_qry;
     run.out = fopen(opt.output_file.c_str(), "w");
     if (!run.out) return "cannot create " + opt.output_file;
-    if (opt.has_cluster) fprintf(run.out, "Representative\tMember\n");
+    if (opt.has_cluster || opt.has_derep) fprintf(run.out, "Representative\tMember\n");
     else if (!opt.matrix) fprintf(run.out, "Reference\tQuery\tDistance\n");                          // main.rs:409-412
     else for (uint32_t j = 0; j < in.nq; ++j) fprintf(run.out, "\t%s", in.col_name[j].c_str());      // main.rs:439-441
     run.block_begin = plan_blocks(opt, in);
@@ -533,6 +587,7 @@ std::string run_dist(const DistOptions &opt)
     }
     if (run.fail.empty() && opt.top) run.fail = finish_top(run);
     if (run.fail.empty() && opt.has_cluster) run.fail = finish_cluster(run);
+    if (run.fail.empty() && opt.has_derep) run.fail = finish_derep(run);
     fclose(run.out);
     run.out = nullptr;
     timing.mark("all rows written");

@@ -22,6 +22,8 @@ struct DistOptions {
     uint32_t top = 0;          // --top K (1..LASH_TOP_MAX): print only the rows in some name's K nearest (list form only); 0 = off
     bool has_cluster = false;  // --cluster D: single-linkage clusters of a triangle run instead of pairs; names are linked iff --max-dist D prints them
     double cluster_dist = 0.0;
+    bool has_derep = false;    // --derep D: greedy representatives of a triangle run in row order; "within D" iff --max-dist D prints the pair
+    double derep_dist = 0.0;
     std::string hll_bias_file; // --hll-bias / $LASH_HLL_BIAS: HLL++ bias tables (lash_hll_bias_load); empty = that regime is refused
     lash_layout layout;        // --layout / $LASH_LAYOUT (include/lash_gfx950.h)
     DistOptions() { lash_layout_default(&layout); }

@@ -7,7 +7,7 @@
 // found on the GPU); dist: --device D, --block-rows N,
 // --file-order (rows / columns in list-file order instead of the reference's seeded hash-map order), --max-dist D (print only
 // the pairs with distance <= D), --top K (only each name's K nearest), --cluster D (single-linkage clusters of an all-vs-all instead
-// of pairs) (reference rows per GPU call); both: --layout SPEC (or $LASH_LAYOUT): the crate-internal rules as data, see `lash_layout`
+// of pairs), --derep D (greedy representatives of an all-vs-all in row order) (reference rows per GPU call); both: --layout SPEC (or $LASH_LAYOUT): the crate-internal rules as data, see `lash_layout`
 // in include/lash_gfx950.h.
 #include <chrono>
 #include <cmath>
@@ -64,6 +64,11 @@ void usage()
             "                     names are linked iff --max-dist D prints their pair.  Output: Representative<TAB>Member, one line\n"
             "                     per name, the representative being the cluster's first name in row order; not with --dm,\n"
             "                     --top or --max-dist\n"
+            "      --derep <D>    all-vs-all only: greedy dereplication instead of pairs.  Names are walked in row order; a name is a\n"
+            "                     Representative iff no earlier representative is within D of it (--max-dist D prints their pair),\n"
+            "                     else a member of the first such representative.  Row order is the priority: pass --file-order to\n"
+            "                     set it with the list file.  Output: Representative<TAB>Member, one line per name; not with --dm,\n"
+            "                     --top, --max-dist, --cluster or more than one entry in --devices\n"
             "      --hll-bias <file>  HLL++ bias tables (tools/ref_probe/extract_hll_bias.py) [default: $LASH_HLL_BIAS];\n"
             "                     without them hll estimates <= 5 * 2^p are refused\n");
 }
@@ -247,6 +252,23 @@ int cmd_dist(int argc, char **argv)
         if (opt.has_max_dist) { fprintf(stderr, "error: --cluster cannot be used with --max-dist (--cluster D is its own cutoff)\n"); return 2; }
         opt.has_cluster = true;
         opt.cluster_dist = d;
+    }
+    if (a.kv.count("derep")) {
+        const std::string &v = a.kv["derep"];
+        char *e = nullptr;
+        const double d = v.empty() ? NAN : strtod(v.c_str(), &e);
+        if (!e || *e != 0 || !std::isfinite(d)) { fprintf(stderr, "error: invalid value '%s' for --derep: a finite number is required\n", v.c_str()); return 2; }
+        if (opt.matrix) { fprintf(stderr, "error: --derep cannot be used with --dm (representatives are not a matrix)\n"); return 2; }
+        if (opt.top) { fprintf(stderr, "error: --derep cannot be used with --top (it prints representatives, not pairs)\n"); return 2; }
+        if (opt.has_max_dist) { fprintf(stderr, "error: --derep cannot be used with --max-dist (--derep D is its own cutoff)\n"); return 2; }
+        if (opt.has_cluster) { fprintf(stderr, "error: --derep cannot be used with --cluster (greedy representatives or single-linkage clusters, not both)\n"); return 2; }
+        if (opt.devices.size() > 1) {
+            fprintf(stderr, "error: --derep cannot be used with more than one entry in --devices: a block of rows is decided from the "
+                            "representatives of the blocks before it, so the blocks run in row order on one worker\n");
+            return 2;
+        }
+        opt.has_derep = true;
+        opt.derep_dist = d;
     }
     err = layout_from_option(a.kv.count("layout") ? a.kv["layout"] : "", opt.layout);
     if (!err.empty()) { fprintf(stderr, "error: %s\n", err.c_str()); return 2; }

@@ -680,6 +680,32 @@ class SketchSet:
         acc.free()
         return out
 
+    def pair_block_derep(self, r0, r1, max_dist, k, acc, n_cols=None, model=1, fp32=False, estimator="fgra", hll_bias=None, stats=None):
+        """`lash dist --derep`: rows [r0, r1) x columns [0, n_cols) (default r1) of this set's lower triangle decided in `acc` (a Derep of
+        this set's size): a row is a representative iff no representative before it is within max_dist (pair_block_within(...,
+        triangle=True) returns their pair), else a member of the first such one (lash_sketch_set_pair_block_derep).  Blocks must come in
+        row order, contiguous from 0 (LashError EINVAL otherwise).  stats: optional dict, gets pairs, pruned_not_rep, pruned_after_hit,
+        sent_to_host, evaluated, representatives.  LashError.pair as pair_block_within.  cardinalities() must have run."""
+        nc = min(int(r1), self.n) if n_cols is None else int(n_cols)
+        st, bad = _lib.DerepStats(), C.c_uint64()
+        self._check_pair(self._lib.lash_sketch_set_pair_block_derep(self._ctx._h, self._h, int(r0), int(r1), self._h, nc, int(k), int(model),
+                                                                    1 if fp32 else 0, ULL_ESTIMATORS[estimator], _bias_handle(hll_bias),
+                                                                    float(max_dist), acc._h, C.byref(st), C.byref(bad)), bad)
+        if stats is not None:
+            stats.update({f: getattr(st, f) for f, _ in st._fields_})
+
+    def derep(self, max_dist, k, block_rows=None, **kw):
+        """`lash dist --derep` over the whole set: walks the triangle in row blocks of `block_rows` (default: one block), in row order,
+        and returns the numpy uint32 array rep: rep[i] == i for a representative, else the representative i is a member of.  The other
+        keywords go to pair_block_derep."""
+        acc = Derep(self._ctx, self.n)
+        step = self.n if not block_rows else int(block_rows)
+        for r0 in range(0, self.n, max(step, 1)):
+            self.pair_block_derep(r0, min(self.n, r0 + step), max_dist, k, acc, **kw)
+        out = acc.result()
+        acc.free()
+        return out
+
     def pair_block(self, r0, r1, qry=None, n_cols=None, triangle=False, estimator="fgra", out=None):
         """statistics of rows [r0, r1) against columns [0, n_cols) of `qry` (default: this set) as the dict lash_dist_rows takes.
         `out`: optional dict of preallocated (e.g. pinned) flat arrays 'c', 'n' (uint32), 'u' (float64) of >= (r1-r0)*n_cols."""
@@ -795,6 +821,38 @@ class Clusters:
     def free(self):
         if getattr(self, "_h", None):
             self._lib.lash_cluster_free(self._h)
+        self._h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+class Derep:
+    """lash_derep: the greedy representatives of n names decided so far, in row order — rep[] on the context's GPU (where
+    pair_block_derep prunes the columns that are not representatives) with a mirror on the host; shared with the command line."""
+
+    def __init__(self, ctx, n):
+        self._ctx, self._lib, self.n = ctx, ctx._lib, int(n)
+        h = C.c_void_p()
+        ctx._check(self._lib.lash_derep_create(ctx._h, self.n, C.byref(h)))
+        self._h = h
+
+    def _check(self, rc):
+        if rc != _lib.OK:
+            raise LashError(rc, self._lib.lash_strerror(rc).decode())
+
+    def result(self):
+        """numpy uint32 [n]: rep[i] == i for a representative, else the representative of i; LashError EINVAL before all are decided"""
+        out = np.empty(self.n, np.uint32)
+        self._check(self._lib.lash_derep_result(self._h, out.ctypes.data))
+        return out
+
+    def free(self):
+        if getattr(self, "_h", None):
+            self._lib.lash_derep_free(self._h)
         self._h = None
 
     def __del__(self):
