@@ -1,12 +1,14 @@
 """hyperminhash's expected_collisions(n, m) on the GPU (lash_hmh_pair_expected_collisions): the 65 536-cell sum that the
 crate — and the host fallback — walk with four pow() per cell and pair, here one cell-probability vector per sketch and an
 f64 MFMA matrix product per block.  Checked against the pure-Python restatement of the crate's loop (tests/pyref.py) and
-against the library's own host path through lash_dist_rows."""
+against the library's own host path through lash_dist_rows; the 1000 x 1000 block cell by cell against the long-double table of
+tests/ecref.py within ecref.tol (tests/test_gpu_hmh_ec_tiles.py has the derivation, and every tile, edge and chunk)."""
 import time
 
 import numpy as np
 import pytest
 
+import ecref as E
 import pyref as R
 
 pytestmark = pytest.mark.gpu
@@ -52,12 +54,18 @@ def test_distances_with_and_without_the_gpu_term_agree_and_the_gpu_is_the_fast_o
         fast = lash_amd.dist_rows("hmh", 0, 16, 1, rc, qc, c_or_zero=c, n_counts=n, hmh_ec=ec)
         assert np.all(slow < 1.0) and np.max(np.abs(slow - fast)) <= 1e-12
         # 1 000 x 1 000 small sketches: the whole block in well under a second on the GPU (the host needs > 4 ms per pair)
-        big_r, big_q = rng.uniform(1e3, 5e5, 1000), rng.uniform(1e3, 5e5, 1000)
+        # (cardinalities from the pool of tests/ecref.py, so that every cell has its long-double reference)
+        table = E.pool_table()
+        big_ri, big_qi = rng.integers(0, len(table.cards), 1000), rng.integers(0, len(table.cards), 1000)
+        big_r, big_q = table.cards[big_ri], table.cards[big_qi]
         ctx.hmh_pair_expected_collisions(big_r[:8], big_q[:8])              # warm-up (module load)
         t0 = time.perf_counter()
         full = ctx.hmh_pair_expected_collisions(big_r, big_q)
         t_gpu = time.perf_counter() - t0
         assert np.all(np.isfinite(full)) and np.all(full > 0)
+        want, tol, small = E.expected(table, big_ri, big_qi, big_r, big_q)
+        assert small.all()
+        print("1000 x 1000 against the reference: worst %.2f ulp(ec)" % E.worst_in_ulp(full, want, tol, small))
         per_pair_host = t_host / (nr * nq)
         assert t_gpu < 5.0 and t_gpu / 1e6 < per_pair_host / 1000, (t_gpu, per_pair_host)
         print("host %.2f ms per pair; GPU %.3f s for 10^6 pairs" % (per_pair_host * 1e3, t_gpu))

@@ -105,6 +105,45 @@ def test_set_cardinalities_equal_the_per_image_entries(algo, p):
             s.free()
 
 
+def test_hmh_set_cardinalities_with_leading_zero_counts_above_39():
+    """hmh_cardinality_from_hist reports a register with lz > 39 as inexact (its 2^-lz no longer adds exactly into the histogram's
+    sum) and lash_sketch_set_cardinalities then sums that member in register order on the host, as the crate does.  Hashes do not
+    reach such ranks (tests/test_gpu_rare_hashes.py stays below), so the images are made up: lz = 40, 45, 52, 63 alone and many per
+    image, in the first and the last bucket, on empty and on filled images, among ordinary members of one set.  For 10 of the 51 the histogram's sum is not the
+    register-order sum in f64, so the fallback decides the result."""
+    import lash_amd
+    import pyref as R
+    rng = np.random.default_rng(40)
+    filled = ((rng.geometric(0.5, 16384).clip(1, 30) + 4) << 10 | rng.integers(0, 1024, 16384)).astype(np.uint16)
+    sparse = np.where(rng.random(16384) < 0.02, filled, 0).astype(np.uint16)
+    imgs = [filled.copy(), sparse.copy(), np.zeros(16384, np.uint16)]
+    rare = []
+    for lz in (40, 45, 52, 63):
+        for base in (np.zeros(16384, np.uint16), sparse, filled):
+            for where in ([0], [16383], [0, 16383], list(range(0, 16384, 37))):
+                im = base.copy()
+                im[where] = (lz << 10) | 0x155
+                rare.append(im)
+    mixed = filled.copy()
+    mixed[5::4] = np.array([40, 45, 52, 63], np.uint16)[np.arange(len(mixed[5::4])) % 4] << 10
+    rare += [mixed, np.full(16384, 63 << 10 | 1023, np.uint16), np.full(16384, 40 << 10, np.uint16)]
+    order = []
+    for i in range(len(rare)):                                          # ordinary members between the rare ones, the first and last rare
+        order += [3 + i, i % 3]
+    order = np.array(order[:-1], np.uint32)
+    imgs = np.stack(imgs + rare).view(np.uint8).reshape(-1, 32768)
+    assert all((im.view(np.uint16) >> 10).max() >= 40 for im in imgs[3:]) and all((im.view(np.uint16) >> 10).max() < 40 for im in imgs[:3])
+    with lash_amd.Context(0) as ctx:
+        s = ctx.sketch_set("hmh", 0, imgs, order)
+        got = s.cardinalities()
+        s.free()
+    host = np.array([lash_amd.sketch_cardinality("hmh", 0, imgs[i]) for i in order])
+    want = np.array([R.hmh_cardinality(imgs[i].tobytes()) for i in order])
+    assert np.array_equal(got, host), np.flatnonzero(got != host)
+    assert np.array_equal(got, want), np.flatnonzero(got != want)
+    assert len(set(got)) > 15
+
+
 @pytest.mark.parametrize("algo,p,est", [("hmh", 0, "fgra"), ("hll", 12, "fgra"), ("hll", 8, "fgra"), ("ull", 11, "fgra"), ("ull", 11, "ml")])
 def test_row_blocks_triangle_and_order_equal_the_whole_matrix_entries(algo, p, est):
     import lash_amd
