@@ -342,12 +342,25 @@ double lash_ull_estimate(const uint8_t *registers, int p, int estimator);
  * appendix; the crate carries them as constants).  The numbers are neither in /root/reference nor derivable, so they are NOT
  * in this library: lash_hll_bias_load reads them from a text file ('#' comments; "p <p> <n>" then n lines "<raw> <bias>", any
  * subset of p = 4..18) that tools/ref_probe/extract_hll_bias.py writes from the crate's source.  With `tables` NULL (or no
- * table for p) that regime returns LASH_ERANGE instead of a different estimate. */
+ * table for p) that regime returns LASH_ERANGE instead of a different estimate.
+ * The tables are measurements, so they can also be MADE: lash_hll_bias_simulate repeats the Monte-Carlo of the HLL++ paper on
+ * the GPU (hll_bias_sim.hip, DESIGN.md "Simulated HLL++ bias tables") and its arrays go to lash_hll_bias_from_arrays.  Those
+ * numbers are regenerated, not the crate's: estimates are unbiased with them, but not digit for digit what the reference prints. */
 typedef struct lash_hll_bias lash_hll_bias;
 int  lash_hll_bias_load(const char *path, lash_hll_bias **out);               /* LASH_EINVAL: cannot open; LASH_EFORMAT: malformed */
 int  lash_hll_bias_from_arrays(lash_hll_bias **inout, int p, const double *raw, const double *bias, uint32_t n);  /* *inout NULL: created */
 int  lash_hll_bias_has(const lash_hll_bias *tables, int p);
 void lash_hll_bias_free(lash_hll_bias *tables);
+/* One precision's table by simulation (the only entry of this group that needs the GPU).  n_trials random sets (0 = 2048, at most
+ * 2^20) are grown to 5 * 2^p distinct elements each; at the n_points checkpoints n_j = j * 5 * 2^p / (n_points - 1) (0 =
+ * lash_hll_bias_default_points(p) = min(200, 5 * 2^p + 1); 6 <= n_points <= 5 * 2^p + 1) the raw estimate alpha m^2 / sum of every set is
+ * taken: out_raw[j] = its mean over the sets (exact sum, exact quotient, rounded once to the nearest double), out_bias[j] = out_raw[j] - n_j, out_n[j] = n_j (out_n may be NULL).  The
+ * arrays hold n_points entries (the default count when 0 was passed).  Hash, register rule and summation orders are fixed: the same
+ * (p, n_points, n_trials, seed) gives the same bits on every run and device.  Synchronous.  LASH_EINVAL: p outside 4..18, n_points or
+ * n_trials out of range, NULL ctx / out_raw / out_bias. */
+int      lash_hll_bias_simulate(lash_ctx *ctx, int p, uint32_t n_points, uint32_t n_trials, uint64_t seed, uint64_t *out_n, double *out_raw,
+                                double *out_bias);
+uint32_t lash_hll_bias_default_points(int p);                                  /* 0 for p outside 4..18 */
 /* Per-sketch cardinalities from the register bytes (no header): hyperminhash's LogLog-beta (`cardinality()`, utils.rs:170-173),
  * streaming_algorithms' `len()` (utils.rs:315), lash_ull_estimate above. */
 double lash_hmh_cardinality(const uint8_t *registers, int big_endian);

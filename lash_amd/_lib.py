@@ -112,6 +112,8 @@ PROTOTYPES = {
     "lash_hll_bias_from_arrays": (_int, [C.POINTER(_vp), _int, _vp, _vp, _u32]),
     "lash_hll_bias_has": (_int, [_vp, _int]),
     "lash_hll_bias_free": (None, [_vp]),
+    "lash_hll_bias_simulate": (_int, [_vp, _int, _u32, _u32, _u64, _vp, _vp, _vp]),
+    "lash_hll_bias_default_points": (_u32, [_int]),
     "lash_hll_cardinality": (_int, [_vp, _int, _vp, C.POINTER(C.c_double)]),
     "lash_dist_rows": (_int, [_int, _int, _int, _int, _int, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_u64)]),
     "lash_hmh_pair_expected_collisions": (_int, [_vp, _vp, _u32, _vp, _u32, _vp]),

@@ -274,11 +274,18 @@ def main(argv=None):
     ap.add_argument("--max-dist", type=_finite, default=None, help="print only the pairs whose distance is <= D (not with --dm)")
     ap.add_argument("--backend", default=None, help="nccl (one GPU per rank, default) or gloo (ranks may share a GPU; images gathered on the host)")
     ap.add_argument("--device", type=int, default=None, help="GPU of this rank (default LOCAL_RANK; with --backend gloo several ranks may name the same one)")
-    ap.add_argument("--hll-bias", default=os.environ.get("LASH_HLL_BIAS"), help="HLL++ bias tables (tools/ref_probe/extract_hll_bias.py); without them "
+    ap.add_argument("--hll-bias", default=None, help="HLL++ bias tables (lash hll-bias, or tools/ref_probe/extract_hll_bias.py) [default: $LASH_HLL_BIAS]; without them "
                     "hll estimates <= 5 * 2^p are refused")
+    ap.add_argument("--hll-bias-sim", action="store_true", help="hll only: simulate the bias table of -p on the GPU at start-up "
+                    "(Context.hll_bias_simulate, defaults) and use it: regenerated measurements, not the reference crate's numbers.  Every rank "
+                    "simulates the same bits.  Not with --hll-bias; $LASH_HLL_BIAS is ignored")
     args = ap.parse_args(argv)
     if args.max_dist is not None and args.dm:
         ap.error("--max-dist cannot be used with --dm (a square matrix cannot drop cells)")
+    if args.hll_bias_sim and args.hll_bias is not None:
+        ap.error("--hll-bias-sim cannot be used with --hll-bias (simulate the tables or read them from a file, not both)")
+    if not args.hll_bias_sim and args.hll_bias is None:
+        args.hll_bias = os.environ.get("LASH_HLL_BIAS")
     import torch
     import torch.distributed as dist
     rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
@@ -304,8 +311,14 @@ def main(argv=None):
     local_images = torch.from_numpy(imgs)
     if backend == "nccl":
         local_images = local_images.cuda(device)
+    hll_bias = HllBias(args.hll_bias) if args.hll_bias else None
+    if args.hll_bias_sim and algo == "hll":
+        hll_bias = HllBias.simulated(ctx, p)
+        if rank == 0:
+            print("[lash_amd.allpairs] --hll-bias-sim: HLL++ bias table simulated on the GPU (regenerated measurements, not "
+                  "streaming_algorithms' tables), p %d: %d points, 2048 trials, seed 42" % (p, _lib.load().lash_hll_bias_default_points(p)), file=sys.stderr)
     parts = all_vs_all_stream(algo, p, args.kmer, local_images, [b - a for a, b in blocks], names, args.output_file, ctx=ctx, model=args.model,
-                              fp32=args.fp32, estimator=args.estimator, matrix=args.dm, hll_bias=HllBias(args.hll_bias) if args.hll_bias else None,
+                              fp32=args.fp32, estimator=args.estimator, matrix=args.dm, hll_bias=hll_bias,
                               threads=args.threads or None, max_dist=args.max_dist)
     del parts
     dist.barrier()

@@ -9,7 +9,9 @@
 //   hll  union zero / sum per pair (lash_hll_pair_union_stats) + streaming_algorithms' HLL++ `len()`: linear counting below
 //        the published per-precision threshold, else alpha*m^2/sum.  Its third regime (estimate <= 5m: subtract a
 //        k-nearest-neighbour bias read from the HLL++ empirical tables) needs data that is not in this image; a sketch
-//        or union that falls there is refused with a message instead of being estimated differently;
+//        or union that falls there is refused with a message instead of being estimated differently, unless the tables come
+//        from --hll-bias FILE or are simulated on the GPU at start-up (--hll-bias-sim: lash_hll_bias_simulate, regenerated
+//        measurements, not the crate's numbers);
 //   ull  union estimate per pair on the GPU (lash_ull_pair_union_estimates: merged-register histogram + FGRA or ML,
 //        ull_estimators.h), per-sketch estimates with lash_ull_estimate; similarity by inclusion-exclusion (utils.rs:272).
 // Order: the reference keeps its sketches in hashbrown maps seeded with XXH3(93) and takes the column order, the
@@ -97,7 +99,25 @@ std::string slurp(const std::string &path, std::string &out)
 }
 
 const char *const BIAS_MSG = ": cardinality estimate <= 5 * 2^p needs the HLL++ bias tables of streaming_algorithms, which are "
-                             "not built in (pass --hll-bias <file from tools/ref_probe/extract_hll_bias.py>, or sketch with a smaller -p)";
+                             "not built in (pass --hll-bias-sim to simulate them, --hll-bias <file from lash hll-bias or tools/ref_probe/extract_hll_bias.py>, or sketch with a smaller -p)";
+
+// One precision's simulated table on an open context; `line` = its provenance ("p 14: 200 points, 2048 trials, seed 42")
+std::string simulate_bias(lash_ctx *ctx, int p, uint32_t points, uint32_t trials, uint64_t seed, std::vector<double> &raw, std::vector<double> &bias,
+                          std::string &line)
+{
+    const uint32_t all = 5u * (1u << p) + 1u;
+    const uint32_t n = points ? std::min(points, all) : lash_hll_bias_default_points(p);
+    raw.assign(n, 0.0);
+    bias.assign(n, 0.0);
+    const int rc = lash_hll_bias_simulate(ctx, p, n, trials, seed, nullptr, raw.data(), bias.data());
+    if (rc != LASH_OK) return std::string("cannot simulate the HLL++ bias table: ") + lash_strerror(rc) + " " + lash_ctx_last_error(ctx);
+    char buf[160];
+    snprintf(buf, sizeof buf, "p %d: %u points, %u trials, seed %llu", p, n, trials ? trials : 2048u, (unsigned long long)seed);
+    line = buf;
+    return "";
+}
+
+const char *const SIM_NOTE = "HLL++ bias table simulated on the GPU (regenerated measurements, not streaming_algorithms' tables)";
 
 // LASH_CLI_TIMING: where the wall time of a run goes
 struct Timing {
@@ -545,6 +565,20 @@ std::string run_dist(const DistOptions &opt)
         const int brc = lash_hll_bias_load(opt.hll_bias_file.c_str(), &bias);
         if (brc != LASH_OK) return "cannot read HLL++ bias tables from " + opt.hll_bias_file + ": " + lash_strerror(brc);
     }
+    if (hll && opt.hll_bias_sim) {                                   // once, on the first device, before the cardinalities
+        lash_ctx *ctx = nullptr;
+        const int dv = opt.devices.empty() ? opt.device : opt.devices[0];
+        int rc = lash_ctx_create(&ctx, dv);
+        if (rc != LASH_OK) return std::string("--hll-bias-sim: ") + lash_strerror(rc);
+        std::vector<double> raw, b;
+        std::string line;
+        err = simulate_bias(ctx, in.prec, 0, 0, 42, raw, b, line);
+        lash_ctx_destroy(ctx);
+        if (!err.empty()) return err;
+        if (lash_hll_bias_from_arrays(&bias, in.prec, raw.data(), b.data(), (uint32_t)raw.size()) != LASH_OK) return "--hll-bias-sim: bad table";
+        fprintf(stderr, "[lash dist] --hll-bias-sim: %s, %s\n", SIM_NOTE, line.c_str());
+        timing.mark("--hll-bias-sim: the table simulated");
+    }
     struct BiasGuard { lash_hll_bias *b; ~BiasGuard() { lash_hll_bias_free(b); } } bias_guard{bias};
 
     // Without --devices, two workers share the GPU: while one formats and writes its block the other has the next block's
@@ -592,6 +626,36 @@ std::string run_dist(const DistOptions &opt)
     run.out = nullptr;
     timing.mark("all rows written");
     return run.fail;
+}
+
+std::string run_hll_bias(const HllBiasOptions &opt)
+{
+    lash_ctx *ctx = nullptr;
+    const int rc = lash_ctx_create(&ctx, opt.device);
+    if (rc != LASH_OK) return lash_strerror(rc);
+    struct CtxGuard { lash_ctx *c; ~CtxGuard() { lash_ctx_destroy(c); } } guard{ctx};
+    std::string text = std::string("# ") + SIM_NOTE + ", written by `lash hll-bias`\n"
+                       "# format: \"p <p> <n>\" then n lines \"<raw estimate> <bias>\" (lash dist --hll-bias)\n";
+    for (int p : opt.ps) {
+        std::vector<double> raw, bias;
+        std::string line;
+        const std::string err = simulate_bias(ctx, p, opt.points, opt.trials, opt.seed, raw, bias, line);
+        if (!err.empty()) return err;
+        char buf[96];
+        text += "# " + line + "\n";
+        snprintf(buf, sizeof buf, "p %d %zu\n", p, raw.size());
+        text += buf;
+        for (size_t j = 0; j < raw.size(); ++j) {
+            snprintf(buf, sizeof buf, "%.17g %.17g\n", raw[j], bias[j]);          // 17 digits: the same doubles when read back
+            text += buf;
+        }
+        fprintf(stderr, "[lash hll-bias] %s, %s\n", SIM_NOTE, line.c_str());
+    }
+    FILE *f = fopen(opt.output.c_str(), "w");
+    if (!f) return "cannot create " + opt.output;
+    const bool ok = fwrite(text.data(), 1, text.size(), f) == text.size();
+    if (fclose(f) != 0 || !ok) return "cannot write " + opt.output;
+    return "";
 }
 
 }  // namespace lashhost

@@ -25,10 +25,22 @@ struct DistOptions {
     bool has_derep = false;    // --derep D: greedy representatives of a triangle run in row order; "within D" iff --max-dist D prints the pair
     double derep_dist = 0.0;
     std::string hll_bias_file; // --hll-bias / $LASH_HLL_BIAS: HLL++ bias tables (lash_hll_bias_load); empty = that regime is refused
+    bool hll_bias_sim = false; // --hll-bias-sim: for hll sketches, simulate the table of their p on the first device (lash_hll_bias_simulate,
+                               // defaults) and go on as if it had come from --hll-bias; nothing at all for hmh / ull
     lash_layout layout;        // --layout / $LASH_LAYOUT (include/lash_gfx950.h)
     DistOptions() { lash_layout_default(&layout); }
 };
 
 std::string run_dist(const DistOptions &opt);
+
+// `lash hll-bias`: the HLL++ bias tables of the precisions `ps`, simulated on `device`, as the text file lash_hll_bias_load reads
+struct HllBiasOptions {
+    std::string output;
+    std::vector<int> ps;       // each 4..18
+    uint32_t points = 0, trials = 0;   // 0 = the defaults of lash_hll_bias_simulate; points above 5 * 2^p + 1 are cut to that for a small p
+    uint64_t seed = 42;
+    int device = 0;
+};
+std::string run_hll_bias(const HllBiasOptions &opt);
 
 }  // namespace lashhost

@@ -121,7 +121,7 @@ std::string dist_block_rows(int algo, int p, int k, int model, bool fp32, const 
                             RowText &text)
 {
     static const char *bias_msg = ": cardinality estimate <= 5 * 2^p needs the HLL++ bias tables of streaming_algorithms, which are "
-                                  "not built in (pass --hll-bias <file from tools/ref_probe/extract_hll_bias.py>, or sketch with a smaller -p)";
+                                  "not built in (pass --hll-bias-sim to simulate them, --hll-bias <file from lash hll-bias or tools/ref_probe/extract_hll_bias.py>, or sketch with a smaller -p)";
     const bool hll = algo == LASH_HLL, ull = algo == LASH_ULL;
     const uint32_t n_rows = i1 - i0;
     // slots: row r at off[r], room for its upper bound (list form: the column names' bytes come from a running sum)

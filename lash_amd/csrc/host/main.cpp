@@ -2,9 +2,10 @@
 // (/root/reference/src/main.rs:26-177) on top of liblash_gfx950.so.
 //   lash sketch -f LIST [-o sketch] [-k 16] [-t N] [-a hmh|hll|ull] [-p 10] [-s 42]        (main.rs:30-96, 180-279)
 //   lash dist   -q PREFIX -r PREFIX [-o dist] [-t N] [-e fgra|ml] [-m 1|0] [--fp32] [--dm]   (main.rs:107-176, 280-617)
+//   lash hll-bias -o FILE [-p P[,P...]] [--points N] [--trials T] [--seed S] [--device D]    (not upstream: HLL++ bias tables, simulated)
 // Extras that do not exist upstream: --gpus N / --device D / --devices LIST (which GPUs to use, one worker each), --batch-mb M, --stream-mb M (files
 // larger than M MiB are streamed in chunks with on-device accumulation), --hmh-x-low, --per-record (one sketch per FASTA record, the records
-// found on the GPU); dist: --device D, --block-rows N,
+// found on the GPU); dist: --device D, --block-rows N, --hll-bias FILE / --hll-bias-sim (HLL++ bias tables from a file / simulated on the GPU),
 // --file-order (rows / columns in list-file order instead of the reference's seeded hash-map order), --max-dist D (print only
 // the pairs with distance <= D), --top K (only each name's K nearest), --cluster D (single-linkage clusters of an all-vs-all instead
 // of pairs), --derep D (greedy representatives of an all-vs-all in row order) (reference rows per GPU call); both: --layout SPEC (or $LASH_LAYOUT): the crate-internal rules as data, see `lash_layout`
@@ -40,7 +41,8 @@ void usage()
             "Fast and Memory Efficient (Meta)genome Sketching via HyperLogLog, HyperMinhash and UltraLogLog (MI355X build)\n\n"
             "Usage: lash <COMMAND>\n\nCommands:\n"
             "  sketch  Sketches genomes and serializes them, sketches are compressed\n"
-            "  dist    Computes distance between sketches\n\n"
+            "  dist    Computes distance between sketches\n"
+            "  hll-bias  Simulates the HLL++ bias tables on the GPU and writes the file dist --hll-bias reads\n\n"
             "sketch options:\n"
             "  -f, --file <file>            One file containing list of FASTA/FASTQ files (.gz/.zstd supported), one per line\n"
             "  -o, --output <output>        Input a prefix/name for your output files [default: sketch]\n"
@@ -69,8 +71,19 @@ void usage()
             "                     else a member of the first such representative.  Row order is the priority: pass --file-order to\n"
             "                     set it with the list file.  Output: Representative<TAB>Member, one line per name; not with --dm,\n"
             "                     --top, --max-dist, --cluster or more than one entry in --devices\n"
-            "      --hll-bias <file>  HLL++ bias tables (tools/ref_probe/extract_hll_bias.py) [default: $LASH_HLL_BIAS];\n"
-            "                     without them hll estimates <= 5 * 2^p are refused\n");
+            "      --hll-bias <file>  HLL++ bias tables (lash hll-bias, or tools/ref_probe/extract_hll_bias.py) [default: $LASH_HLL_BIAS];\n"
+            "                     without them hll estimates <= 5 * 2^p are refused\n"
+            "      --hll-bias-sim hll sketches only: simulate the bias table of their precision on the GPU at start-up (as lash hll-bias\n"
+            "                     does with its defaults) and use it; regenerated measurements, not the reference crate's numbers.\n"
+            "                     Not with --hll-bias; $LASH_HLL_BIAS is ignored\n"
+            "hll-bias options:\n"
+            "  -o, --output <file>          Where the tables go (text: \"p <p> <n>\" then n lines \"<raw estimate> <bias>\")\n"
+            "  -p, --precision <p[,p...]>   Precisions to simulate, each 4-18 [default: 4,5,...,18]\n"
+            "      --points <N>             Cardinalities per table, evenly spaced over 0..5*2^p: 6 to 5*2^p+1 (more is cut to that)\n"
+            "                               [default: 200]\n"
+            "      --trials <T>             Random sets per table [default: 2048]\n"
+            "      --seed <S>               Seed of the sets; the same options give the same file [default: 42]\n"
+            "      --device <D>             GPU to use [default: 0]\n");
 }
 
 bool parse(int argc, char **argv, int first, const std::map<std::string, std::string> &alias,
@@ -187,7 +200,8 @@ int cmd_dist(int argc, char **argv)
     std::string err;
     const std::map<std::string, std::string> alias = {{"q", "query"}, {"r", "reference"}, {"o", "output_file"}, {"t", "threads"},
                                                       {"e", "estimator"}, {"m", "model"}};
-    if (!parse(argc, argv, 2, alias, {"fp32", "dm", "file-order"}, a, err)) { fprintf(stderr, "error: %s\n", err.c_str()); return 2; }
+    if (!parse(argc, argv, 2, alias, {"fp32", "dm", "file-order", "hll-bias-sim", "help"}, a, err)) { fprintf(stderr, "error: %s\n", err.c_str()); return 2; }
+    if (a.flags.count("help")) { usage(); return 0; }
     if (!a.kv.count("query") || !a.kv.count("reference")) {
         fprintf(stderr, "error: the following required arguments were not provided:\n  --query <query>\n  --reference <reference>\n");
         return 2;
@@ -208,8 +222,13 @@ int cmd_dist(int argc, char **argv)
     opt.fp32 = a.flags.count("fp32") != 0;
     opt.matrix = a.flags.count("dm") != 0;
     opt.file_order = a.flags.count("file-order") != 0;
+    opt.hll_bias_sim = a.flags.count("hll-bias-sim") != 0;
+    if (opt.hll_bias_sim && a.kv.count("hll-bias")) {
+        fprintf(stderr, "error: --hll-bias-sim cannot be used with --hll-bias (simulate the tables or read them from a file, not both)\n");
+        return 2;
+    }
     if (a.kv.count("hll-bias")) opt.hll_bias_file = a.kv["hll-bias"];
-    else if (const char *e = getenv("LASH_HLL_BIAS")) opt.hll_bias_file = e;
+    else if (const char *e = opt.hll_bias_sim ? nullptr : getenv("LASH_HLL_BIAS")) opt.hll_bias_file = e;
     opt.device = (int)dev;
     if (a.kv.count("devices")) {
         const std::string &l = a.kv["devices"];
@@ -278,6 +297,54 @@ int cmd_dist(int argc, char **argv)
     return 0;
 }
 
+int cmd_hll_bias(int argc, char **argv)
+{
+    Args a;
+    std::string err;
+    const std::map<std::string, std::string> alias = {{"o", "output"}, {"p", "precision"}};
+    if (!parse(argc, argv, 2, alias, {"help"}, a, err)) { fprintf(stderr, "error: %s\n", err.c_str()); return 2; }
+    if (a.flags.count("help")) { usage(); return 0; }
+    if (!a.kv.count("output")) { fprintf(stderr, "error: the following required arguments were not provided:\n  --output <file>\n"); return 2; }
+    HllBiasOptions opt;
+    opt.output = a.kv["output"];
+    uint64_t points = 0, trials = 0, dev = 0;
+    if (a.kv.count("precision")) {
+        const std::string &l = a.kv["precision"];
+        size_t at = 0;
+        while (at <= l.size()) {
+            const size_t c = l.find(',', at);
+            uint64_t p = 0;
+            if (!to_u64(l.substr(at, c == std::string::npos ? std::string::npos : c - at), p) || p < 4 || p > 18) {
+                fprintf(stderr, "error: invalid value '%s' for --precision: a list of integers from 4 to 18 is required\n", l.c_str());
+                return 2;
+            }
+            for (int q : opt.ps)
+                if (q == (int)p) { fprintf(stderr, "error: invalid value '%s' for --precision: %d is named twice\n", l.c_str(), q); return 2; }
+            opt.ps.push_back((int)p);
+            if (c == std::string::npos) break;
+            at = c + 1;
+        }
+    } else for (int p = 4; p <= 18; ++p) opt.ps.push_back(p);
+    if (a.kv.count("points") && (!to_u64(a.kv["points"], points) || points < 6 || points > 0xFFFFFFFFull)) {
+        fprintf(stderr, "error: invalid value '%s' for --points: an integer of at least 6 is required (the bias is read from the 6 nearest)\n",
+                a.kv["points"].c_str());
+        return 2;
+    }
+    if (a.kv.count("trials") && (!to_u64(a.kv["trials"], trials) || trials < 1 || trials > (1u << 20))) {
+        fprintf(stderr, "error: invalid value '%s' for --trials: an integer from 1 to 1048576 is required\n", a.kv["trials"].c_str());
+        return 2;
+    }
+    if (a.kv.count("seed") && !to_u64(a.kv["seed"], opt.seed)) { fprintf(stderr, "error: invalid value for --seed\n"); return 2; }
+    if (a.kv.count("device") && !to_u64(a.kv["device"], dev)) { fprintf(stderr, "error: invalid value for --device\n"); return 2; }
+    opt.points = (uint32_t)points;
+    opt.trials = (uint32_t)trials;
+    opt.device = (int)dev;
+    err = run_hll_bias(opt);
+    if (!err.empty()) { fprintf(stderr, "Error: %s\n", err.c_str()); return 1; }
+    printf("HLL++ bias tables written.\n");
+    return 0;
+}
+
 }  // namespace
 
 static void epoch_mark(const char *what)
@@ -296,6 +363,7 @@ int main(int argc, char **argv)
     const std::string cmd = argv[1];
     if (cmd == "sketch") { const int rc = cmd_sketch(argc, argv); epoch_mark("main returning"); return rc; }
     if (cmd == "dist") return cmd_dist(argc, argv);
+    if (cmd == "hll-bias") return cmd_hll_bias(argc, argv);
     if (cmd == "--version" || cmd == "-V") { printf("Genome Sketching via HyperLogLog, HyperMinhash and UltraLogLog %s\n", VERSION); return 0; }
     usage();
     return cmd == "--help" || cmd == "-h" || cmd == "help" ? 0 : 2;

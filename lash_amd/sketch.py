@@ -15,8 +15,9 @@ ULL_ESTIMATORS = {"fgra": 0, "ml": 1}
 
 class HllBias:
     """HLL++ empirical bias tables (include/lash_gfx950.h: lash_hll_bias).  They are not part of this repository: load the
-    text file tools/ref_probe/extract_hll_bias.py writes, or build from arrays (tests).  Without them the estimate <= 5 * 2^p
-    regime of streaming_algorithms' len() is refused with ERANGE."""
+    text file tools/ref_probe/extract_hll_bias.py or `lash hll-bias` writes, build from arrays, or simulate them on the GPU
+    (HllBias.simulated: regenerated numbers, not the crate's).  Without them the estimate <= 5 * 2^p regime of
+    streaming_algorithms' len() is refused with ERANGE."""
 
     def __init__(self, path=None):
         self._lib = _lib.load()
@@ -37,6 +38,15 @@ class HllBias:
 
     def has(self, p):
         return bool(self._lib.lash_hll_bias_has(self._h, int(p)))
+
+    @classmethod
+    def simulated(cls, ctx, ps, points=None, trials=None, seed=42):
+        """Tables for the precisions `ps` (an int or an iterable) from Context.hll_bias_simulate"""
+        tb = cls()
+        for p in ([ps] if isinstance(ps, int) else ps):
+            _, raw, bias = ctx.hll_bias_simulate(p, points, trials, seed)
+            tb.set(p, raw, bias)
+        return tb
 
     def __del__(self):
         if getattr(self, "_h", None) and self._h.value:
@@ -506,6 +516,20 @@ class Context:
         self._check(self._lib.lash_ull_pair_union_estimates(self._h, int(p), ULL_ESTIMATORS[estimator], ref.ctypes.data, ref.shape[0],
                                                             qry.ctypes.data, qry.shape[0], est.ctypes.data))
         return est
+
+    def hll_bias_simulate(self, p, points=None, trials=None, seed=42):
+        """One precision's HLL++ bias table by Monte-Carlo on the GPU (lash_hll_bias_simulate): (n uint64, raw, bias float64), one
+        entry per checkpoint cardinality n_j = j * 5 * 2^p / (points - 1).  None = the defaults (min(200, 5 * 2^p + 1) points,
+        2048 trials).  Deterministic in (p, points, trials, seed)."""
+        n_pts = int(points) if points else int(self._lib.lash_hll_bias_default_points(int(p)))
+        if not 0 <= n_pts < 2**32 or not 0 <= int(trials or 0) < 2**32:
+            raise LashError(_lib.EINVAL, self._lib.lash_strerror(_lib.EINVAL).decode())
+        n = np.zeros(max(n_pts, 1), dtype=np.uint64)
+        raw = np.zeros(max(n_pts, 1), dtype=np.float64)
+        bias = np.zeros(max(n_pts, 1), dtype=np.float64)
+        self._check(self._lib.lash_hll_bias_simulate(self._h, int(p), n_pts, int(trials or 0), int(seed) & (2**64 - 1), n.ctypes.data,
+                                                     raw.ctypes.data, bias.ctypes.data))
+        return n, raw, bias
 
     # -- dist side, resident form (include/lash_gfx950.h: lash_sketch_set_*) ---------------------------------------------
     def sketch_set(self, algo, p, images, order=None):
