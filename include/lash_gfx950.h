@@ -380,6 +380,23 @@ int    lash_dist_rows(int algo, int p, int k, int model, int fp32, uint32_t n_re
  * cardinalities are both <= 2^19 (every other pair is a closed form, taken here).  NULL: those pairs are computed here on the host,
  * a walk over 65 536 cells with four pow() each (4 ms to 0.2 s PER PAIR, as in the crate): viruses, plasmids, short contigs. */
 
+/* The measure a distance is taken of (`lash dist --containment`, not upstream).  s: the similarity above after its clamp; a_r / a_q:
+ * the reference's / the query's cardinality.
+ *   LASH_MEASURE_JACCARD            frac = 2s/(1+s): the reference's Mash distance, what every entry without a measure computes
+ *   LASH_MEASURE_CONTAIN_QUERY      frac = s/(1+s) * (a_r + a_q) / a_q: how much of the query is in the reference
+ *   LASH_MEASURE_CONTAIN_REFERENCE  frac = s/(1+s) * (a_r + a_q) / a_r: how much of the reference is in the query
+ * s/(1+s) * (a_r + a_q) estimates the shared k-mers (hll / ull: a_r + a_q - union exactly).  s <= 0 gives d = 1 exactly, frac >= 1
+ * gives d = +0 exactly, otherwise the model's distance of frac as for the Jaccard fraction; with a_r == a_q frac is 2s/(1+s) bit for
+ * bit (csrc/dist_pair.h states the rule once, for the host and the device).  Containment is directional: the _measure entries below
+ * take rectangles only, triangle != 0 with a containment is LASH_EINVAL, as is any other value of `measure`.  Each _measure entry is
+ * its namesake with one more argument, and its namesake is the entry with LASH_MEASURE_JACCARD. */
+#define LASH_MEASURE_JACCARD 0
+#define LASH_MEASURE_CONTAIN_QUERY 1
+#define LASH_MEASURE_CONTAIN_REFERENCE 2
+int    lash_dist_rows_measure(int algo, int p, int k, int model, int fp32, uint32_t n_ref, uint32_t n_qry, const double *ref_card,
+                              const double *qry_card, const uint32_t *c_or_zero, const uint32_t *n_counts, const double *sum_or_union,
+                              const lash_hll_bias *tables, const double *hmh_ec, int measure, double *out_dist, uint64_t *bad_pair);
+
 /* ---- dist side, resident form: all-vs-all on whole collections (BASELINE configs[3]: 10^5 sketches, 5 * 10^9 printed pairs) ----
  * `lash dist` keeps both sketch files in memory for the run (utils.rs:95-127, 202-242, 303-337), takes one cardinality per
  * sketch (utils.rs:170-173, 213-219, 314-315) and walks reference rows x query columns — the lower triangle only when both are
@@ -433,6 +450,11 @@ int      lash_sketch_set_pair_block_within(lash_ctx *ctx, const lash_sketch_set 
                                            uint32_t n_cols, int triangle, int k, int model, int fp32, int ull_estimator,
                                            const lash_hll_bias *tables, double max_dist, uint32_t *out_row, uint32_t *out_col,
                                            double *out_dist, uint64_t cap, uint64_t *n_kept, uint64_t *bad_pair, uint64_t *n_candidates);
+/* the same under `measure` (LASH_MEASURE_*, above lash_dist_rows_measure): d is lash_dist_rows_measure's number */
+int      lash_sketch_set_pair_block_within_measure(lash_ctx *ctx, const lash_sketch_set *ref, uint32_t r0, uint32_t r1, const lash_sketch_set *qry,
+                                                   uint32_t n_cols, int triangle, int k, int model, int fp32, int ull_estimator,
+                                                   const lash_hll_bias *tables, int measure, double max_dist, uint32_t *out_row, uint32_t *out_col,
+                                                   double *out_dist, uint64_t cap, uint64_t *n_kept, uint64_t *bad_pair, uint64_t *n_candidates);
 
 /* pair_block_top: `lash dist --top K`.  A pair's rank key is (d, row, col): d its printed distance (lash_dist_rows' number, in f32
  * under fp32, with the "same name -> 0" rule), then its position in the unfiltered output; NaN is never ranked.  N_K(X) = the K
@@ -457,6 +479,12 @@ int      lash_sketch_set_pair_block_top(lash_ctx *ctx, const lash_sketch_set *re
                                         const lash_hll_bias *tables, uint32_t top_k, double max_dist, const uint32_t *same_col,
                                         const lash_top_key *col_bound, const lash_top_key *row_bound, uint32_t *out_row, uint32_t *out_col,
                                         double *out_dist, uint64_t cap, uint64_t *n_kept, uint64_t *bad_pair, uint64_t *n_candidates);
+/* the same under `measure` (LASH_MEASURE_*): ranked by lash_dist_rows_measure's number; a containment is a rectangle, so per column */
+int      lash_sketch_set_pair_block_top_measure(lash_ctx *ctx, const lash_sketch_set *ref, uint32_t r0, uint32_t r1, const lash_sketch_set *qry,
+                                                uint32_t n_cols, int triangle, int k, int model, int fp32, int ull_estimator,
+                                                const lash_hll_bias *tables, int measure, uint32_t top_k, double max_dist, const uint32_t *same_col,
+                                                const lash_top_key *col_bound, const lash_top_key *row_bound, uint32_t *out_row, uint32_t *out_col,
+                                                double *out_dist, uint64_t cap, uint64_t *n_kept, uint64_t *bad_pair, uint64_t *n_candidates);
 typedef struct lash_top lash_top;
 int      lash_top_create(uint32_t n_names, uint32_t top_k, int triangle, lash_top **out);
 int      lash_top_add(lash_top *t, const uint32_t *row, const uint32_t *col, const double *dist, uint64_t n);

@@ -13,6 +13,7 @@ OK, EINVAL, ENODEV, EHIP, ENOMEM, ELIMIT, ERANGE, EFORMAT = 0, -1, -2, -3, -4, -
 HMH, HLL, ULL = 0, 1, 2
 F_HMH_X_LOW, F_ACCUMULATE, F_NO_DIRECT, F_AMINO, F_STREAM_ONLY, F_NO_SOLE = 1, 2, 4, 8, 16, 32
 FMT_FASTA, FMT_FASTQ = 1, 2
+MEASURE_JACCARD, MEASURE_CONTAIN_QUERY, MEASURE_CONTAIN_REFERENCE = 0, 1, 2
 ABI_VERSION = 5
 
 
@@ -116,6 +117,7 @@ PROTOTYPES = {
     "lash_hll_bias_default_points": (_u32, [_int]),
     "lash_hll_cardinality": (_int, [_vp, _int, _vp, C.POINTER(C.c_double)]),
     "lash_dist_rows": (_int, [_int, _int, _int, _int, _int, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_u64)]),
+    "lash_dist_rows_measure": (_int, [_int, _int, _int, _int, _int, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _vp, C.POINTER(_u64)]),
     "lash_hmh_pair_expected_collisions": (_int, [_vp, _vp, _u32, _vp, _u32, _vp]),
     "lash_sketch_set_create": (_int, [_vp, _int, _int, _vp, _u32, _vp, _u32, C.POINTER(_vp)]),
     "lash_sketch_set_create_device": (_int, [_vp, _int, _int, _vp, _u32, C.POINTER(_vp)]),
@@ -128,8 +130,12 @@ PROTOTYPES = {
     "lash_sketch_set_pair_block_device": (_int, [_vp, _vp, _u32, _u32, _vp, _u32, _int, _int, _vp, _vp, _vp]),
     "lash_sketch_set_pair_block_within": (_int, [_vp, _vp, _u32, _u32, _vp, _u32, _int, _int, _int, _int, _int, _vp, C.c_double, _vp, _vp, _vp,
                                                   _u64, C.POINTER(_u64), C.POINTER(_u64), C.POINTER(_u64)]),
+    "lash_sketch_set_pair_block_within_measure": (_int, [_vp, _vp, _u32, _u32, _vp, _u32, _int, _int, _int, _int, _int, _vp, _int, C.c_double, _vp,
+                                                          _vp, _vp, _u64, C.POINTER(_u64), C.POINTER(_u64), C.POINTER(_u64)]),
     "lash_sketch_set_pair_block_top": (_int, [_vp, _vp, _u32, _u32, _vp, _u32, _int, _int, _int, _int, _int, _vp, _u32, C.c_double, _vp, _vp,
                                                _vp, _vp, _vp, _vp, _u64, C.POINTER(_u64), C.POINTER(_u64), C.POINTER(_u64)]),
+    "lash_sketch_set_pair_block_top_measure": (_int, [_vp, _vp, _u32, _u32, _vp, _u32, _int, _int, _int, _int, _int, _vp, _int, _u32, C.c_double,
+                                                       _vp, _vp, _vp, _vp, _vp, _vp, _u64, C.POINTER(_u64), C.POINTER(_u64), C.POINTER(_u64)]),
     "lash_top_create": (_int, [_u32, _u32, _int, C.POINTER(_vp)]),
     "lash_top_add": (_int, [_vp, _vp, _vp, _vp, _u64]),
     "lash_top_bounds": (_int, [_vp, _u32, _u32, _u32, _vp, _vp]),

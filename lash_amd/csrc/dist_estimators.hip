@@ -148,7 +148,7 @@ bool hll_len(int p, uint64_t zero, double sum, const lash_hll_bias *tables, doub
 namespace lash {
 
 bool dist_pair_host(int algo, int p, int k, int model, int fp32, double ref_card, double qry_card, uint32_t c_or_zero, uint32_t n_count,
-                    double sum_or_union, const lash_hll_bias *tables, const double *hmh_ec, double *out)
+                    double sum_or_union, const lash_hll_bias *tables, const double *hmh_ec, double *out, int measure)
 {
     double sim = 0.0;
     if (algo == LASH_HLL) {                                                                   // utils.rs:352-365
@@ -164,7 +164,7 @@ bool dist_pair_host(int algo, int p, int k, int model, int fp32, double ref_card
             if (!pairmath::hmh_ec_closed_form(qry_card, ref_card, &ec)) ec = hmh_ec ? *hmh_ec : hmh_ec_cell_walk(qry_card, ref_card);
         sim = pairmath::hmh_similarity(c, n, ec);                                             // Sketch::similarity
     }
-    *out = pairmath::distance_from_similarity(sim, algo == LASH_ULL, k, model, fp32 != 0);
+    *out = pairmath::distance_from_similarity(sim, algo == LASH_ULL, k, model, fp32 != 0, measure, ref_card, qry_card);
     return true;
 }
 
@@ -250,6 +250,17 @@ int lash_dist_rows(int algo, int p, int k, int model, int fp32, uint32_t n_ref, 
                    const double *qry_card, const uint32_t *c_or_zero, const uint32_t *n_counts, const double *sum_or_union,
                    const lash_hll_bias *tables, const double *hmh_ec, double *out_dist, uint64_t *bad_pair)
 {
+    return lash_dist_rows_measure(algo, p, k, model, fp32, n_ref, n_qry, ref_card, qry_card, c_or_zero, n_counts, sum_or_union, tables, hmh_ec,
+                                  LASH_MEASURE_JACCARD, out_dist, bad_pair);
+}
+
+int lash_dist_rows_measure(int algo, int p, int k, int model, int fp32, uint32_t n_ref, uint32_t n_qry, const double *ref_card,
+                           const double *qry_card, const uint32_t *c_or_zero, const uint32_t *n_counts, const double *sum_or_union,
+                           const lash_hll_bias *tables, const double *hmh_ec, int measure, double *out_dist, uint64_t *bad_pair)
+{
+    static_assert(LASH_MEASURE_JACCARD == lash::pairmath::MEASURE_JACCARD && LASH_MEASURE_CONTAIN_QUERY == lash::pairmath::MEASURE_CONTAIN_QUERY &&
+                  LASH_MEASURE_CONTAIN_REFERENCE == lash::pairmath::MEASURE_CONTAIN_REFERENCE, "LASH_MEASURE_* are dist_pair.h's");
+    if (measure < LASH_MEASURE_JACCARD || measure > LASH_MEASURE_CONTAIN_REFERENCE) return LASH_EINVAL;
     if (k < 1 || k > 32 || (model != 0 && model != 1) || !ref_card || !qry_card || !out_dist) return LASH_EINVAL;
     if (algo == LASH_HMH ? (!c_or_zero || !n_counts) : algo == LASH_HLL ? (!c_or_zero || !sum_or_union || p < 4 || p > 16)
                          : algo == LASH_ULL ? !sum_or_union : true)
@@ -258,7 +269,7 @@ int lash_dist_rows(int algo, int p, int k, int model, int fp32, uint32_t n_ref, 
         for (uint32_t j = 0; j < n_qry; ++j) {
             const uint64_t at = (uint64_t)i * n_qry + j;
             if (!lash::dist_pair_host(algo, p, k, model, fp32, ref_card[i], qry_card[j], c_or_zero ? c_or_zero[at] : 0, n_counts ? n_counts[at] : 0,
-                                      sum_or_union ? sum_or_union[at] : 0.0, tables, hmh_ec ? &hmh_ec[at] : nullptr, &out_dist[at])) {
+                                      sum_or_union ? sum_or_union[at] : 0.0, tables, hmh_ec ? &hmh_ec[at] : nullptr, &out_dist[at], measure)) {
                 if (bad_pair) *bad_pair = at;
                 return LASH_ERANGE;
             }

@@ -19,6 +19,7 @@ struct WithinPair {
 
 struct WithinArgs {
     int algo, p, k, model, fp32;
+    int measure;                                         // pairmath::MEASURE_*: --containment (rectangles only; the mark kernel of --max-dist and the key kernel of --top read it)
     double limit;                                        // D + margin
     uint32_t nr, n_cols, tiles_x;
     uint64_t n_tiles;
@@ -111,17 +112,33 @@ __host__ __device__ constexpr double filter_margin(bool fp32) { return fp32 ? 0x
 //   Cap.  The host's d never exceeds 1 (min(.., 1); 1 - f^(1/k) with f >= 0): d_hi = min(.., 1).
 //   PAIR_ONE.  sim <= 0 means the host's similarity, never above sim, is <= 0 as well, and then d = 1.0 exactly on both sides, both
 //     models, f64 and f32: no margin.  *d_lo = *d_hi = 1.
+//   Containment (a.measure != MEASURE_JACCARD, CONTAIN = true; a_r / a_q: the pair's cardinalities as pair_similarity_dev read them).
+//     near and far come from the rule of dist_pair.h that the host runs, distance_from_similarity(.., measure, a_r, a_q).  The
+//     similarity-to-fraction step stays bit-identical: its extra + * / are the host's operations, contraction off, on the host's
+//     doubles (the cardinalities in HBM are the host's).  For fixed cardinalities frac_c = s/(1+s) * (a_r + a_q) / den does not
+//     decrease as s grows (up to the few ulp by which a rounded quotient of two growing numbers may, as 2s/(1+s) itself: 2^-50
+//     against the 2^-44 the two similarities are apart and the 2^-40 of the margin), so the HLL linear-counting argument
+//     [d(sim) - margin, d(sim_low) + margin] holds as it stands.  frac_c >= 1 gives exactly 0 on both sides, which only narrows
+//     the interval.  PAIR_ONE is decided before the ratio is formed, so it stays true whatever the cardinalities are (0 and
+//     NaN included).  The margin is unchanged: the same libm calls on the same fraction.
 //   PAIR_NAN.  A NaN distance.  hmh / ull similarities are bit-identical and NaN goes through log / pow alike on both sides: the
 //     host's d is NaN too, which no filter keeps, ranks or links.  Under hll the host decides: the pair is sent back.
 enum { PAIR_INTERVAL, PAIR_ONE, PAIR_NAN };
-__device__ inline int pair_interval_dev(const WithinArgs &a, double sim, double sim_low, double *d_lo, double *d_hi)
+template <bool CONTAIN = false>
+__device__ inline int pair_interval_dev(const WithinArgs &a, double sim, double sim_low, double *d_lo, double *d_hi, double a_r = 0.0, double a_q = 0.0)
 {
     *d_lo = *d_hi = 1.0;
     if (sim <= 0.0) return PAIR_ONE;
     const bool ull = a.algo == LASH_ULL;
     const double margin = filter_margin(a.fp32 != 0);
-    const double near = pairmath::distance_from_similarity(sim, ull, a.k, a.model, a.fp32 != 0);
-    const double far = sim_low == sim ? near : pairmath::distance_from_similarity(sim_low, ull, a.k, a.model, a.fp32 != 0);   // (hll only)
+    double near, far;
+    if constexpr (CONTAIN) {
+        near = pairmath::distance_from_similarity(sim, ull, a.k, a.model, a.fp32 != 0, a.measure, a_r, a_q);
+        far = sim_low == sim ? near : pairmath::distance_from_similarity(sim_low, ull, a.k, a.model, a.fp32 != 0, a.measure, a_r, a_q);
+    } else {
+        near = pairmath::distance_from_similarity(sim, ull, a.k, a.model, a.fp32 != 0);
+        far = sim_low == sim ? near : pairmath::distance_from_similarity(sim_low, ull, a.k, a.model, a.fp32 != 0);   // (hll only)
+    }
     if (near != near || far != far) return PAIR_NAN;
     *d_lo = near - margin;
     *d_hi = fmin(far + margin, 1.0);
@@ -177,7 +194,7 @@ struct WithinBlock {
     uint32_t *d_cnt;
 };
 int within_block(lash_ctx *ctx, const lash_sketch_set *ref, uint32_t r0, uint32_t r1, const lash_sketch_set *qry, uint32_t n_cols, int triangle, int k,
-                 int model, int fp32, int ull_estimator, WithinBlock &b);
+                 int model, int fp32, int ull_estimator, WithinBlock &b, int measure = pairmath::MEASURE_JACCARD);
 
 // compaction: mask words [n_tiles][WF_WORDS] of candidates and their per-tile counts -> exclusive offsets (d_off: n_tiles + 1) -> the
 // candidates with their statistics in (row, col) order, copied back into `cand` (synchronous; dist_filter.hip's scan and write kernels)
@@ -186,13 +203,13 @@ int within_compact(lash_ctx *ctx, const WithinArgs &a, const uint64_t *d_mask, c
 // exact: one candidate of the block whose first row is r0 through the host arithmetic of lash_dist_rows.  false: that arithmetic
 // refuses the pair (the HLL++ bias-table regime without tables) and *d is not set.
 inline bool filter_pair_host(const WithinPair &w, const lash_sketch_set *ref, uint32_t r0, const lash_sketch_set *qry, int k, int model, int fp32,
-                             const lash_hll_bias *tables, double *d)
+                             const lash_hll_bias *tables, double *d, int measure = pairmath::MEASURE_JACCARD)
 {
     const int algo = ref->algo;
     double ec;
     const double *ecp = nullptr;
     if (algo == LASH_HMH && !std::isnan(w.ec_x)) { ec = hmh_ec_from_cell_sum(w.ec_x); ecp = &ec; }
-    return dist_pair_host(algo, ref->p, k, model, fp32, ref->card[r0 + w.row], qry->card[w.col], w.c_or_zero, w.n, w.sum_or_union, tables, ecp, d);
+    return dist_pair_host(algo, ref->p, k, model, fp32, ref->card[r0 + w.row], qry->card[w.col], w.c_or_zero, w.n, w.sum_or_union, tables, ecp, d, measure);
 }
 
 // exact: the candidates in order (row-major) through filter_pair_host, each handed to each(set row, col, d, block row).  LASH_ERANGE
@@ -200,11 +217,11 @@ inline bool filter_pair_host(const WithinPair &w, const lash_sketch_set *ref, ui
 // before it have been handed over.
 template <class Each>
 int filter_evaluate(const std::vector<WithinPair> &cand, const lash_sketch_set *ref, uint32_t r0, const lash_sketch_set *qry, uint32_t n_cols, int k,
-                    int model, int fp32, const lash_hll_bias *tables, uint64_t *bad_pair, Each each)
+                    int model, int fp32, const lash_hll_bias *tables, uint64_t *bad_pair, Each each, int measure = pairmath::MEASURE_JACCARD)
 {
     for (const WithinPair &w : cand) {
         double d;
-        if (!filter_pair_host(w, ref, r0, qry, k, model, fp32, tables, &d)) {
+        if (!filter_pair_host(w, ref, r0, qry, k, model, fp32, tables, &d, measure)) {
             if (bad_pair) *bad_pair = (uint64_t)w.row * n_cols + w.col;
             return LASH_ERANGE;
         }

@@ -20,12 +20,18 @@
 
 namespace lash {
 
+// CONTAIN: a.measure is a containment (--containment): the distance of the same similarity under that measure, from the pair's two
+// cardinalities.  The Jaccard instantiation is the kernel as it was.
+template <bool CONTAIN>
 __global__ void __launch_bounds__(256) within_mark_kernel(WithinArgs a, uint64_t *__restrict__ mask, uint32_t *__restrict__ tile_count)
 {
     mark_tiles(a, mask, tile_count, [&](uint32_t r, uint32_t q) {
         double sim, sim_low;
         if (!pair_similarity_dev(a, r, q, &sim, &sim_low)) return true;
-        return !(pairmath::distance_from_similarity(sim, a.algo == LASH_ULL, a.k, a.model, a.fp32 != 0) > a.limit);   // (NaN: a candidate)
+        if constexpr (CONTAIN)
+            return !(pairmath::distance_from_similarity(sim, a.algo == LASH_ULL, a.k, a.model, a.fp32 != 0, a.measure, a.row_card[r], a.col_card[q]) > a.limit);
+        else
+            return !(pairmath::distance_from_similarity(sim, a.algo == LASH_ULL, a.k, a.model, a.fp32 != 0) > a.limit);   // (NaN: a candidate)
     });
 }
 
@@ -113,9 +119,11 @@ WithinArgs within_args(const lash_sketch_set *ref, uint32_t r0, uint32_t r1, con
 }
 
 int within_block(lash_ctx *ctx, const lash_sketch_set *ref, uint32_t r0, uint32_t r1, const lash_sketch_set *qry, uint32_t n_cols, int triangle, int k,
-                 int model, int fp32, int ull_estimator, WithinBlock &b)
+                 int model, int fp32, int ull_estimator, WithinBlock &b, int measure)
 {
     b = WithinBlock{};
+    if (measure < pairmath::MEASURE_JACCARD || measure > pairmath::MEASURE_CONTAIN_REFERENCE) return LASH_EINVAL;
+    if (measure != pairmath::MEASURE_JACCARD && triangle) return LASH_EINVAL;                   // directional: no triangle
     if (!ctx || !ref || !qry || r0 > r1 || r1 > ref->n || n_cols > qry->n || k < 1 || k > 32 || (model != 0 && model != 1)) return LASH_EINVAL;
     if (ref->card.size() != ref->n || qry->card.size() != qry->n) return LASH_EINVAL;          // lash_sketch_set_cardinalities first
     if (r0 == r1 || n_cols == 0) return LASH_OK;
@@ -129,6 +137,7 @@ int within_block(lash_ctx *ctx, const lash_sketch_set *ref, uint32_t r0, uint32_
     EcBlock eb;
     if (ref->algo == LASH_HMH && (rc = lash_set_ec_block(ctx, ref, r0, r1, qry, n_cols, eb))) return rc;
     b.a = within_args(ref, r0, r1, qry, n_cols, triangle, k, model, fp32, d_c, d_n, d_u, eb);
+    b.a.measure = measure;
     const uint64_t nt = b.a.n_tiles;
     if ((rc = reserve(ctx, ctx->wf_scratch, (nt + 1) * 8 + nt * WF_WORDS * 8 + nt * 4 + 64))) return rc;
     b.d_off = static_cast<uint64_t *>(ctx->wf_scratch.ptr);
@@ -167,15 +176,27 @@ int lash_sketch_set_pair_block_within(lash_ctx *ctx, const lash_sketch_set *ref,
                                       double max_dist, uint32_t *out_row, uint32_t *out_col, double *out_dist, uint64_t cap, uint64_t *n_kept,
                                       uint64_t *bad_pair, uint64_t *n_candidates)
 {
+    return lash_sketch_set_pair_block_within_measure(ctx, ref, r0, r1, qry, n_cols, triangle, k, model, fp32, ull_estimator, tables, LASH_MEASURE_JACCARD,
+                                                     max_dist, out_row, out_col, out_dist, cap, n_kept, bad_pair, n_candidates);
+}
+
+int lash_sketch_set_pair_block_within_measure(lash_ctx *ctx, const lash_sketch_set *ref, uint32_t r0, uint32_t r1, const lash_sketch_set *qry,
+                                              uint32_t n_cols, int triangle, int k, int model, int fp32, int ull_estimator, const lash_hll_bias *tables,
+                                              int measure, double max_dist, uint32_t *out_row, uint32_t *out_col, double *out_dist, uint64_t cap,
+                                              uint64_t *n_kept, uint64_t *bad_pair, uint64_t *n_candidates)
+{
     using namespace lash;
     if (n_kept) *n_kept = 0;
     if (n_candidates) *n_candidates = 0;
     if (!n_kept || std::isnan(max_dist) || (cap && (!out_row || !out_col || !out_dist))) return LASH_EINVAL;
     int rc;
     WithinBlock b;
-    if ((rc = within_block(ctx, ref, r0, r1, qry, n_cols, triangle, k, model, fp32, ull_estimator, b)) || !b.a.n_tiles) return rc;
+    if ((rc = within_block(ctx, ref, r0, r1, qry, n_cols, triangle, k, model, fp32, ull_estimator, b, measure)) || !b.a.n_tiles) return rc;
     b.a.limit = max_dist + filter_margin(fp32 != 0);
-    hipLaunchKernelGGL(within_mark_kernel, dim3(mark_grid(b.a.n_tiles)), dim3(256), 0, ctx->stream, b.a, b.d_mask, b.d_cnt);
+    if (measure == LASH_MEASURE_JACCARD)
+        hipLaunchKernelGGL(within_mark_kernel<false>, dim3(mark_grid(b.a.n_tiles)), dim3(256), 0, ctx->stream, b.a, b.d_mask, b.d_cnt);
+    else
+        hipLaunchKernelGGL(within_mark_kernel<true>, dim3(mark_grid(b.a.n_tiles)), dim3(256), 0, ctx->stream, b.a, b.d_mask, b.d_cnt);
     HIPCHK(ctx, hipGetLastError());
     std::vector<WithinPair> cand;
     if ((rc = within_compact(ctx, b.a, b.d_mask, b.d_cnt, b.d_off, cand))) return rc;
@@ -183,7 +204,7 @@ int lash_sketch_set_pair_block_within(lash_ctx *ctx, const lash_sketch_set *ref,
     KeptRows kept{out_row, out_col, out_dist, cap, 0};
     rc = filter_evaluate(cand, ref, r0, qry, n_cols, k, model, fp32, tables, bad_pair, [&](uint32_t row, uint32_t col, double d, uint32_t) {
         if (d <= max_dist) kept.add(row, col, d);
-    });
+    }, measure);
     *n_kept = kept.n;
     return rc;
 }

@@ -103,6 +103,43 @@ __host__ __device__ inline double distance_from_similarity(double sim, bool ull,
     return fp32 ? (double)compute_distance<float>((float)frac, k, model) : compute_distance<double>(frac, k, model);
 }
 
+// `lash dist --containment` (not upstream): which fraction the Mash distance is taken of (include/lash_gfx950.h: LASH_MEASURE_*)
+enum { MEASURE_JACCARD = 0, MEASURE_CONTAIN_QUERY = 1, MEASURE_CONTAIN_REFERENCE = 2 };
+
+// The containment fraction of a pair with similarity s > 0 (clamped as above) and cardinalities a_r (reference), a_q (query):
+//   frac_c = s/(1+s) * (a_r + a_q) / den,   den = a_q (how much of the query is in the reference) or a_r (the other way round).
+// s/(1+s) * (a_r + a_q) is the shared k-mer estimate: for hll / ull, s = (a_r + a_q - u) / u, it is a_r + a_q - u exactly
+// (inclusion-exclusion); for hmh it is the Jaccard-to-intersection identity.  The association is fixed here and nowhere else:
+// (s / (1 + s)) * ((a_r + a_q) / den).  With a_r == a_q the second factor is 2 exactly and doubling commutes with the rounding
+// of the quotient, so frac_c is the 2s/(1+s) of distance_from_similarity bit for bit: equal-sized sketches print what the
+// default prints.  For fixed cardinalities frac_c does not decrease as s grows.
+__host__ __device__ inline double containment_frac(double sim, double a_r, double a_q, int measure)
+{
+#pragma clang fp contract(off)
+    const double den = measure == MEASURE_CONTAIN_QUERY ? a_q : a_r;
+    return (sim / (1.0 + sim)) * ((a_r + a_q) / den);
+}
+
+// distance_from_similarity under a measure.  MEASURE_JACCARD: that function itself.  Containment: the same clamp of the similarity;
+// then s <= 0 gives exactly 1 BEFORE any ratio is formed (whatever the cardinalities are, 0 and NaN included: what the filters call
+// PAIR_ONE); frac_c >= 1 (one side wholly inside the other, up to estimator noise) gives +0.0 exactly without a libm call, in both
+// models, f64 and f32 — -log(1) / k would be -0.0 and a frac_c above 1 a negative distance; everything else goes through
+// compute_distance as the Jaccard fraction does (a NaN similarity, ull only, stays a NaN fraction).
+__host__ __device__ inline double distance_from_similarity(double sim, bool ull, int k, int model, bool fp32, int measure, double a_r, double a_q)
+{
+#pragma clang fp contract(off)
+    if (measure == MEASURE_JACCARD) return distance_from_similarity(sim, ull, k, model, fp32);
+    if (ull) sim = sim < 0.0 ? 0.0 : sim;
+    else if (!(sim >= 0.0)) sim = 0.0;
+    if (sim <= 0.0) return 1.0;
+    const double frac = containment_frac(sim, a_r, a_q, measure);
+    if (fp32) {
+        const float f = (float)frac;
+        return f >= 1.0f ? 0.0 : (double)compute_distance<float>(f, k, model);
+    }
+    return frac >= 1.0 ? 0.0 : compute_distance<double>(frac, k, model);
+}
+
 // hyperminhash's similarity from C, N and expected_collisions (utils.rs:164 behind Sketch::similarity); c == 0 needs no ec
 __host__ __device__ inline double hmh_similarity(double c, double n, double ec)
 {

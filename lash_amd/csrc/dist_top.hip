@@ -88,6 +88,9 @@ struct TopArgs {
     uint32_t r0;
 };
 
+// CONTAIN: a.measure is a containment (--containment; rectangles only): the interval under that measure, from the pair's two
+// cardinalities.  The Jaccard instantiation is the kernel as it was.
+template <bool CONTAIN>
 __global__ void __launch_bounds__(256) top_key_kernel(WithinArgs a, TopArgs t)
 {
     const uint32_t q = blockIdx.x * 256u + threadIdx.x;
@@ -99,7 +102,8 @@ __global__ void __launch_bounds__(256) top_key_kernel(WithinArgs a, TopArgs t)
         if (q >= row_end(a, r)) { hi = KEY_NONE; lo = LO_NEVER; }                       // above the diagonal: not printed
         else if (t.same_col && t.same_col[r] == q) { hi = ord(0.0f); lo = LO_ALWAYS; }   // prints 0; the host still evaluates it
         else if (!pair_similarity_dev(a, r, q, &sim, &sim_low)) { hi = KEY_NONE; lo = LO_ALWAYS; }
-        else switch (pair_interval_dev(a, sim, sim_low, &d_lo, &d_hi)) {
+        else switch (CONTAIN ? pair_interval_dev<true>(a, sim, sim_low, &d_lo, &d_hi, a.row_card[r], a.col_card[q])
+                             : pair_interval_dev<false>(a, sim, sim_low, &d_lo, &d_hi)) {
         case PAIR_ONE: hi = lo = ord(1.0f); break;                                      // exact
         case PAIR_NAN: hi = KEY_NONE; lo = a.algo == LASH_HLL ? LO_ALWAYS : LO_NEVER; break;
         default: {
@@ -334,6 +338,16 @@ int lash_sketch_set_pair_block_top(lash_ctx *ctx, const lash_sketch_set *ref, ui
                                    uint32_t *out_row, uint32_t *out_col, double *out_dist, uint64_t cap, uint64_t *n_kept, uint64_t *bad_pair,
                                    uint64_t *n_candidates)
 {
+    return lash_sketch_set_pair_block_top_measure(ctx, ref, r0, r1, qry, n_cols, triangle, k, model, fp32, ull_estimator, tables, LASH_MEASURE_JACCARD, top_k,
+                                                  max_dist, same_col, col_bound, row_bound, out_row, out_col, out_dist, cap, n_kept, bad_pair, n_candidates);
+}
+
+int lash_sketch_set_pair_block_top_measure(lash_ctx *ctx, const lash_sketch_set *ref, uint32_t r0, uint32_t r1, const lash_sketch_set *qry, uint32_t n_cols,
+                                           int triangle, int k, int model, int fp32, int ull_estimator, const lash_hll_bias *tables, int measure,
+                                           uint32_t top_k, double max_dist, const uint32_t *same_col, const lash_top_key *col_bound,
+                                           const lash_top_key *row_bound, uint32_t *out_row, uint32_t *out_col, double *out_dist, uint64_t cap,
+                                           uint64_t *n_kept, uint64_t *bad_pair, uint64_t *n_candidates)
+{
     using namespace lash;
     static_assert(sizeof(TopKey) == sizeof(lash_top_key), "lash_top_key layout");
     if (n_kept) *n_kept = 0;
@@ -341,7 +355,7 @@ int lash_sketch_set_pair_block_top(lash_ctx *ctx, const lash_sketch_set *ref, ui
     if (!n_kept || top_k < 1 || top_k > LASH_TOP_MAX || (cap && (!out_row || !out_col || !out_dist))) return LASH_EINVAL;
     int rc;
     WithinBlock b;
-    if ((rc = within_block(ctx, ref, r0, r1, qry, n_cols, triangle, k, model, fp32, ull_estimator, b)) || !b.a.n_tiles) return rc;
+    if ((rc = within_block(ctx, ref, r0, r1, qry, n_cols, triangle, k, model, fp32, ull_estimator, b, measure)) || !b.a.n_tiles) return rc;
     const WithinArgs &a = b.a;
     const uint32_t nr = r1 - r0;
     const uint64_t np = (uint64_t)nr * n_cols;
@@ -362,7 +376,9 @@ int lash_sketch_set_pair_block_top(lash_ctx *ctx, const lash_sketch_set *ref, ui
     t.max_dist = max_dist;
     t.r0 = r0;
     const uint32_t gx = (n_cols + 255) / 256;
-    hipLaunchKernelGGL(top_key_kernel, dim3(gx, std::min<uint32_t>({nr, 65535u, std::max<uint32_t>(1, (1u << 20) / gx)})), dim3(256), 0, ctx->stream, a, t);
+    const dim3 key_grid(gx, std::min<uint32_t>({nr, 65535u, std::max<uint32_t>(1, (1u << 20) / gx)}));
+    if (measure == LASH_MEASURE_JACCARD) hipLaunchKernelGGL(top_key_kernel<false>, key_grid, dim3(256), 0, ctx->stream, a, t);
+    else hipLaunchKernelGGL(top_key_kernel<true>, key_grid, dim3(256), 0, ctx->stream, a, t);
     HIPCHK(ctx, hipGetLastError());
     hipLaunchKernelGGL(top_col_select_kernel, dim3((n_cols + SEL_COLS - 1) / SEL_COLS), dim3(64 * SEL_WAVES), 0, ctx->stream, d_hi, nr, n_cols,
                        top_k, r0, d_tc);
@@ -386,7 +402,7 @@ int lash_sketch_set_pair_block_top(lash_ctx *ctx, const lash_sketch_set *ref, ui
     rc = filter_evaluate(cand, ref, r0, qry, n_cols, k, model, fp32, tables, bad_pair, [&](uint32_t row, uint32_t col, double d, uint32_t block_row) {
         if (same_col && same_col[block_row] == col) d = 0.0;
         if (!std::isnan(d) && (std::isnan(max_dist) || d <= max_dist)) kept.add(row, col, d);
-    });
+    }, measure);
     *n_kept = kept.n;
     return rc;
 }

@@ -27,6 +27,9 @@
 // --cluster D (not upstream; same files only): single-linkage clusters, two names being linked iff --max-dist D prints their pair.  A
 // block's pairs are joined in a label array on the device (lash_sketch_set_pair_block_cluster, one lash_cluster per worker, merged at the
 // end); no pair text at all, the N lines "representative<TAB>member" are written once, at the end.
+// --containment query|reference (not upstream): the distance of the containment fraction s/(1+s) * (a_r + a_q) / a_q (or / a_r) instead of
+// 2s/(1+s) (csrc/dist_pair.h).  Directional, so the run is always the rectangle: same files print the full square, both orientations; every
+// rectangular route (all pairs, --max-dist, --top) takes it, the measure going down to the device's filters.
 // --derep D (not upstream; same files only): greedy representatives in row order, "within D" meaning that --max-dist D prints the pair.
 // A row is decided from the representatives among the rows before it (lash_sketch_set_pair_block_derep, one lash_derep), so the blocks
 // run in row order on one worker; the N lines are written once, at the end.
@@ -129,7 +132,8 @@ struct Timing {
 // what a run reads from its two sketch-file sets, checked
 struct DistInput {
     int k = 0, algo_id = 0, prec = 0, ull_est = LASH_ULL_FGRA;
-    bool same_files = false, same_sketches = false;                  // the same name file (main.rs:404); one sketch file, read once
+    bool same_files = false, same_sketches = false;                  // the triangle: the same name file (main.rs:404) and no --containment; one sketch file, read once
+    bool same_order = false;                                         // the same name file, whatever is printed
     std::vector<std::string> rnames, qnames;                         // the name files
     std::vector<uint32_t> rorder, qorder;                            // the maps' key order: the rows / columns, as indices into the name files
     std::vector<uint8_t> rimg_store, qimg_store;
@@ -139,7 +143,7 @@ struct DistInput {
     std::vector<uint32_t> same_col;                                  // --max-dist / --top: the column carrying each row's name, or NO_COLUMN
     const std::vector<uint8_t> &rimg() const { return rimg_store; }
     const std::vector<uint8_t> &qimg() const { return same_sketches ? rimg_store : qimg_store; }
-    bool one_set() const { return same_sketches && same_files; }     // the same images in the same order: one set is both sides
+    bool one_set() const { return same_sketches && same_order; }     // the same images in the same order: one set is both sides
 };
 
 std::string load_input(const DistOptions &opt, const Timing &timing, DistInput &in)
@@ -167,7 +171,8 @@ std::string load_input(const DistOptions &opt, const Timing &timing, DistInput &
     }
     if (!(err = slurp(rf["files"], txt)).empty() || !json_parse_string_array(txt, in.rnames)) return err.empty() ? "bad names JSON " + rf["files"] : err;
     if (!(err = slurp(qf["files"], txt)).empty() || !json_parse_string_array(txt, in.qnames)) return err.empty() ? "bad names JSON " + qf["files"] : err;
-    in.same_files = qf["files"] == rf["files"];                                                       // main.rs:404
+    in.same_order = qf["files"] == rf["files"];                                                       // main.rs:404
+    in.same_files = in.same_order && opt.measure == LASH_MEASURE_JACCARD;                             // (a containment is a rectangle)
     in.same_sketches = rf["sketches"] == qf["sketches"];                                              // all-vs-all: one file, read once
     if (opt.has_cluster && !(in.same_files && in.same_sketches))
         return "--cluster needs an all-vs-all run: -q and -r must name the same sketch files";
@@ -179,7 +184,7 @@ std::string load_input(const DistOptions &opt, const Timing &timing, DistInput &
         in.qorder.resize(in.qnames.size()); std::iota(in.qorder.begin(), in.qorder.end(), 0u);
     } else {
         in.rorder = hashbrown_key_order(in.rnames);
-        in.qorder = in.same_files ? in.rorder : hashbrown_key_order(in.qnames);
+        in.qorder = in.same_order ? in.rorder : hashbrown_key_order(in.qnames);
     }
 
     if (!(err = zstd_decompress_file(rf["sketches"], in.rimg_store)).empty()) return err;
@@ -361,9 +366,10 @@ struct Worker {
         lash_top_key *rb = in.same_files ? row_bound.data() : nullptr;
         lash_top_bounds(top, b.i0, b.i1, b.n_cols, col_bound.data(), rb);
         int rc = kept_rows(&kept, [&](uint64_t cap) {
-            return lash_sketch_set_pair_block_top(ctx, ds->ref, b.i0, b.i1, ds->qry, b.n_cols, in.same_files ? 1 : 0, in.k, opt.model, opt.fp32 ? 1 : 0,
-                                                  in.ull_est, run.bias, opt.top, opt.has_max_dist ? opt.max_dist : NAN, in.same_col.data() + b.i0,
-                                                  col_bound.data(), rb, w_row.data(), w_col.data(), w_dist.data(), cap, &kept, &bad, &cand);
+            return lash_sketch_set_pair_block_top_measure(ctx, ds->ref, b.i0, b.i1, ds->qry, b.n_cols, in.same_files ? 1 : 0, in.k, opt.model, opt.fp32 ? 1 : 0,
+                                                          in.ull_est, run.bias, opt.measure, opt.top, opt.has_max_dist ? opt.max_dist : NAN,
+                                                          in.same_col.data() + b.i0, col_bound.data(), rb, w_row.data(), w_col.data(), w_dist.data(), cap,
+                                                          &kept, &bad, &cand);
         });
         run.top_candidates += cand;
         if (rc == LASH_OK) rc = lash_top_add(top, w_row.data(), w_col.data(), w_dist.data(), kept);
@@ -401,9 +407,9 @@ struct Worker {
     {
         uint64_t kept = 0, bad = 0;
         const int rc = kept_rows(&kept, [&](uint64_t cap) {
-            return lash_sketch_set_pair_block_within(ctx, ds->ref, b.i0, b.i1, ds->qry, b.n_cols, in.same_files ? 1 : 0, in.k, opt.model, opt.fp32 ? 1 : 0,
-                                                     in.ull_est, run.bias, opt.max_dist, w_row.data(), w_col.data(), w_dist.data(), cap, &kept,
-                                                     &bad, nullptr);
+            return lash_sketch_set_pair_block_within_measure(ctx, ds->ref, b.i0, b.i1, ds->qry, b.n_cols, in.same_files ? 1 : 0, in.k, opt.model,
+                                                             opt.fp32 ? 1 : 0, in.ull_est, run.bias, opt.measure, opt.max_dist, w_row.data(), w_col.data(),
+                                                             w_dist.data(), cap, &kept, &bad, nullptr);
         });
         if (rc == LASH_OK)
             format_block_within(b.i0, b.i1, in.same_files, in.nq, opt.max_dist, w_row.data(), w_col.data(), w_dist.data(), kept, in.same_col.data(),
@@ -439,7 +445,7 @@ struct Worker {
         BlockTables bt;
         bt.c_or_zero = C; bt.n_counts = N; bt.sum_or_union = U; bt.hmh_ec = have_ec ? EC : nullptr; bt.ld = b.n_cols;
         return dist_block_rows(in.algo_id, in.prec, in.k, opt.model, opt.fp32, run.bias, b.i0, b.i1, in.same_files, in.nq, run.dev.rcard.data(), run.dev.qcard.data(),
-                               bt, in.row_name, in.col_name, in.col_tab, in.row_id.data(), in.col_id.data(), opt.matrix, run.fmt_threads, row_text);
+                               bt, in.row_name, in.col_name, in.col_tab, in.row_id.data(), in.col_id.data(), opt.matrix, run.fmt_threads, row_text, opt.measure);
     }
 
     // Blocks in turn, each through its mode's step, written in block order whatever order the workers finish in.

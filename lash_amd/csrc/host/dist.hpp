@@ -24,6 +24,8 @@ struct DistOptions {
     double cluster_dist = 0.0;
     bool has_derep = false;    // --derep D: greedy representatives of a triangle run in row order; "within D" iff --max-dist D prints the pair
     double derep_dist = 0.0;
+    int measure = LASH_MEASURE_JACCARD;   // --containment query|reference: LASH_MEASURE_CONTAIN_*; directional, so the run is a rectangle even
+                               // when -q and -r name the same files (list form only; not with --cluster / --derep)
     std::string hll_bias_file; // --hll-bias / $LASH_HLL_BIAS: HLL++ bias tables (lash_hll_bias_load); empty = that regime is refused
     bool hll_bias_sim = false; // --hll-bias-sim: for hll sketches, simulate the table of their p on the first device (lash_hll_bias_simulate,
                                // defaults) and go on as if it had come from --hll-bias; nothing at all for hmh / ull

@@ -118,7 +118,7 @@ std::string dist_block_rows(int algo, int p, int k, int model, bool fp32, const 
                             uint32_t n_cols_total, const double *row_card, const double *col_card, const BlockTables &t,
                             const std::vector<std::string> &row_name, const std::vector<std::string> &col_name,
                             const std::vector<std::string> &col_tab, const uint32_t *row_id, const uint32_t *col_id, bool matrix, int threads,
-                            RowText &text)
+                            RowText &text, int measure)
 {
     static const char *bias_msg = ": cardinality estimate <= 5 * 2^p needs the HLL++ bias tables of streaming_algorithms, which are "
                                   "not built in (pass --hll-bias-sim to simulate them, --hll-bias <file from lash hll-bias or tools/ref_probe/extract_hll_bias.py>, or sketch with a smaller -p)";
@@ -144,9 +144,10 @@ std::string dist_block_rows(int algo, int p, int k, int model, bool fp32, const 
         const uint32_t n_print = triangle ? std::min(i + 1, n_cols_total) : n_cols_total;                  // utils.rs:158-160
         if (dist.size() < n_print) dist.resize(n_print);
         uint64_t bad_pair = 0;
-        const int drc = lash_dist_rows(algo, p, k, model, fp32 ? 1 : 0, 1, n_print, &row_card[i], col_card, ull ? nullptr : t.c_or_zero + row,
-                                       (hll || ull) ? nullptr : t.n_counts + row, (hll || ull) ? t.sum_or_union + row : nullptr,
-                                       static_cast<const lash_hll_bias *>(hll_bias), t.hmh_ec ? t.hmh_ec + row : nullptr, dist.data(), &bad_pair);
+        const int drc = lash_dist_rows_measure(algo, p, k, model, fp32 ? 1 : 0, 1, n_print, &row_card[i], col_card, ull ? nullptr : t.c_or_zero + row,
+                                               (hll || ull) ? nullptr : t.n_counts + row, (hll || ull) ? t.sum_or_union + row : nullptr,
+                                               static_cast<const lash_hll_bias *>(hll_bias), t.hmh_ec ? t.hmh_ec + row : nullptr, measure, dist.data(),
+                                               &bad_pair);
         if (drc == LASH_ERANGE) { row_fail[i - i0] = "union of " + row_name[i] + " and " + col_name[bad_pair] + bias_msg; return; }
         if (drc != LASH_OK) { row_fail[i - i0] = lash_strerror(drc); return; }
         text.len[i - i0] = format_row(text.buf.data() + text.off[i - i0], row_name[i], col_tab, n_print, dist.data(), row_id[i], col_id, matrix);

@@ -30,6 +30,7 @@ size_t format_row(char *dst, const std::string &rname, const std::vector<std::st
 // par_iter over reference sketches, utils.rs:150,248,342).  Tables are row-major [i1 - i0][ld]; row i prints columns
 // [0, triangle ? min(i + 1, n_cols_total) : n_cols_total) (utils.rs:158-160).  row_name / row_card / row_id are indexed by the
 // global row i, col_tab / col_name / col_card / col_id by column.  Returns "" or the message `lash dist` ends with; text row i - i0 = the row.
+// measure: LASH_MEASURE_* (--containment: lash_dist_rows_measure's distances; a containment is never a triangle).
 struct BlockTables {
     const uint32_t *c_or_zero = nullptr, *n_counts = nullptr;   // hmh: C, N; hll: zero registers of the union
     const double *sum_or_union = nullptr;                       // hll: sum of the union; ull: union estimate
@@ -59,6 +60,6 @@ std::string dist_block_rows(int algo, int p, int k, int model, bool fp32, const 
                             uint32_t n_cols_total, const double *row_card, const double *col_card, const BlockTables &t,
                             const std::vector<std::string> &row_name, const std::vector<std::string> &col_name,
                             const std::vector<std::string> &col_tab, const uint32_t *row_id, const uint32_t *col_id, bool matrix, int threads,
-                            RowText &text);
+                            RowText &text, int measure = 0);
 
 }  // namespace lashhost

@@ -8,7 +8,8 @@
 // found on the GPU); dist: --device D, --block-rows N, --hll-bias FILE / --hll-bias-sim (HLL++ bias tables from a file / simulated on the GPU),
 // --file-order (rows / columns in list-file order instead of the reference's seeded hash-map order), --max-dist D (print only
 // the pairs with distance <= D), --top K (only each name's K nearest), --cluster D (single-linkage clusters of an all-vs-all instead
-// of pairs), --derep D (greedy representatives of an all-vs-all in row order) (reference rows per GPU call); both: --layout SPEC (or $LASH_LAYOUT): the crate-internal rules as data, see `lash_layout`
+// of pairs), --derep D (greedy representatives of an all-vs-all in row order), --containment query|reference (the distance of the
+// containment fraction instead of the Jaccard-derived one; always a rectangle) (reference rows per GPU call); both: --layout SPEC (or $LASH_LAYOUT): the crate-internal rules as data, see `lash_layout`
 // in include/lash_gfx950.h.
 #include <chrono>
 #include <cmath>
@@ -71,6 +72,11 @@ void usage()
             "                     else a member of the first such representative.  Row order is the priority: pass --file-order to\n"
             "                     set it with the list file.  Output: Representative<TAB>Member, one line per name; not with --dm,\n"
             "                     --top, --max-dist, --cluster or more than one entry in --devices\n"
+            "      --containment <query|reference>  the distance of the containment fraction instead of the Jaccard-derived one, for sides\n"
+            "                     of different size (a genome against a metagenome, a plasmid against its host): query = how much of the\n"
+            "                     query is in the reference, reference = how much of the reference is in the query.  Directional, so\n"
+            "                     always the rectangle: -q and -r on the same files print the full square, both orientations.  Works\n"
+            "                     with --max-dist and --top (per query); not with --dm, --cluster or --derep\n"
             "      --hll-bias <file>  HLL++ bias tables (lash hll-bias, or tools/ref_probe/extract_hll_bias.py) [default: $LASH_HLL_BIAS];\n"
             "                     without them hll estimates <= 5 * 2^p are refused\n"
             "      --hll-bias-sim hll sketches only: simulate the bias table of their precision on the GPU at start-up (as lash hll-bias\n"
@@ -288,6 +294,15 @@ int cmd_dist(int argc, char **argv)
         }
         opt.has_derep = true;
         opt.derep_dist = d;
+    }
+    if (a.kv.count("containment")) {
+        const std::string &v = a.kv["containment"];
+        if (v == "query") opt.measure = LASH_MEASURE_CONTAIN_QUERY;
+        else if (v == "reference") opt.measure = LASH_MEASURE_CONTAIN_REFERENCE;
+        else { fprintf(stderr, "error: invalid value '%s' for --containment: query or reference is required\n", v.c_str()); return 2; }
+        if (opt.matrix) { fprintf(stderr, "error: --containment cannot be used with --dm (list form only)\n"); return 2; }
+        if (opt.has_cluster) { fprintf(stderr, "error: --containment cannot be used with --cluster (clusters need a symmetric distance)\n"); return 2; }
+        if (opt.has_derep) { fprintf(stderr, "error: --containment cannot be used with --derep (representatives need a symmetric distance)\n"); return 2; }
     }
     err = layout_from_option(a.kv.count("layout") ? a.kv["layout"] : "", opt.layout);
     if (!err.empty()) { fprintf(stderr, "error: %s\n", err.c_str()); return 2; }

@@ -82,8 +82,8 @@ double hmh_cardinality_from_hist(const uint32_t *hist64, bool *exact);
 int    hll_cardinality_from_hist(const uint32_t *hist256, int p, const lash_hll_bias *tables, double *out);   // LASH_OK / LASH_ERANGE
 // one pair of lash_dist_rows (dist_estimators.hip): the distance the reference prints, before the "same name -> 0" rule.
 // hmh_ec: that pair's expected collisions when both sketches are small (NULL: walked here).  false: an HLL union in the bias-table
-// regime that `tables` does not cover
+// regime that `tables` does not cover.  measure: pairmath::MEASURE_* (dist_pair.h; 0 = the Jaccard-derived distance of the reference)
 bool   dist_pair_host(int algo, int p, int k, int model, int fp32, double ref_card, double qry_card, uint32_t c_or_zero, uint32_t n_count,
-                      double sum_or_union, const lash_hll_bias *tables, const double *hmh_ec, double *out);
+                      double sum_or_union, const lash_hll_bias *tables, const double *hmh_ec, double *out, int measure = 0);
 
 }  // namespace lash

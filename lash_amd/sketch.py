@@ -77,10 +77,15 @@ def sketch_cardinality(algo, p, image, layout=None, estimator="fgra", hll_bias=N
     return out.value
 
 
+MEASURES = {None: _lib.MEASURE_JACCARD, "jaccard": _lib.MEASURE_JACCARD, "query": _lib.MEASURE_CONTAIN_QUERY,
+            "reference": _lib.MEASURE_CONTAIN_REFERENCE}
+
+
 def dist_rows(algo, p, k, model, ref_card, qry_card, c_or_zero=None, n_counts=None, sum_or_union=None, fp32=False, hll_bias=None,
-              hmh_ec=None):
+              hmh_ec=None, containment=None):
     """The distances the reference prints for an [n_ref, n_qry] block, from the GPU's pair statistics and the per-sketch
-    cardinalities (lash_dist_rows; utils.rs:164-167, 272-278, 355-365 + main.rs:415-423).  numpy in, float64 [n_ref, n_qry] out."""
+    cardinalities (lash_dist_rows; utils.rs:164-167, 272-278, 355-365 + main.rs:415-423).  numpy in, float64 [n_ref, n_qry] out.
+    containment: None (the Jaccard-derived distance), "query" or "reference": `lash dist --containment` (lash_dist_rows_measure)."""
     lib = _lib.load()
     rc_ = np.ascontiguousarray(ref_card, dtype=np.float64)
     qc_ = np.ascontiguousarray(qry_card, dtype=np.float64)
@@ -92,10 +97,10 @@ def dist_rows(algo, p, k, model, ref_card, qry_card, c_or_zero=None, n_counts=No
     bad = C.c_uint64()
     ec = None if hmh_ec is None else np.ascontiguousarray(hmh_ec, dtype=np.float64)       # (kept alive across the call)
     assert ec is None or ec.size == nr * nq
-    rc = lib.lash_dist_rows(_algo(algo), int(p or 0), int(k), int(model), 1 if fp32 else 0, nr, nq, rc_.ctypes.data, qc_.ctypes.data,
-                            None if a is None else a.ctypes.data, None if b is None else b.ctypes.data,
-                            None if d is None else d.ctypes.data, _bias_handle(hll_bias),
-                            None if ec is None else ec.ctypes.data, out.ctypes.data, C.byref(bad))
+    rc = lib.lash_dist_rows_measure(_algo(algo), int(p or 0), int(k), int(model), 1 if fp32 else 0, nr, nq, rc_.ctypes.data, qc_.ctypes.data,
+                                    None if a is None else a.ctypes.data, None if b is None else b.ctypes.data,
+                                    None if d is None else d.ctypes.data, _bias_handle(hll_bias),
+                                    None if ec is None else ec.ctypes.data, MEASURES[containment], out.ctypes.data, C.byref(bad))
     if rc != _lib.OK:
         raise LashError(rc, lib.lash_strerror(rc).decode() + (" (pair %d)" % bad.value if rc == _lib.ERANGE else ""))
     return out
@@ -625,25 +630,26 @@ class SketchSet:
         return row[:n], col[:n], dist[:n]
 
     def pair_block_within(self, r0, r1, max_dist, k, qry=None, n_cols=None, triangle=False, model=1, fp32=False, estimator="fgra",
-                          hll_bias=None, cap=None, stats=None):
+                          hll_bias=None, cap=None, stats=None, containment=None):
         """`lash dist --max-dist`: the pairs of rows [r0, r1) x columns [0, n_cols) whose distance d (lash_dist_rows' number, before the
         "same name -> 0" rule) passes d <= max_dist, as numpy arrays (row, col, dist) in (row, col) order — filtered on the GPU, each
         survivor evaluated exactly on the host (lash_sketch_set_pair_block_within).  cap: at most that many (default: all, growing the
         buffers as needed).  stats: optional dict, gets n_kept (the full count) and n_candidates (the pairs the filter kernel let through).
-        cardinalities() must have run on both sets."""
+        cardinalities() must have run on both sets.  containment: None, "query" or "reference" as dist_rows (rectangles only: with
+        triangle the library answers LASH_EINVAL)."""
         q = qry or self
         nc = q.n if n_cols is None else int(n_cols)
-        return self._kept_rows(cap, stats, lambda out: self._lib.lash_sketch_set_pair_block_within(
+        return self._kept_rows(cap, stats, lambda out: self._lib.lash_sketch_set_pair_block_within_measure(
             self._ctx._h, self._h, int(r0), int(r1), q._h, nc, 1 if triangle else 0, int(k), int(model), 1 if fp32 else 0,
-            ULL_ESTIMATORS[estimator], _bias_handle(hll_bias), float(max_dist), *out))
+            ULL_ESTIMATORS[estimator], _bias_handle(hll_bias), MEASURES[containment], float(max_dist), *out))
 
     def pair_block_top(self, r0, r1, top, k, qry=None, n_cols=None, triangle=False, max_dist=None, same_col=None, col_bound=None,
-                       row_bound=None, model=1, fp32=False, estimator="fgra", hll_bias=None, cap=None, stats=None):
+                       row_bound=None, model=1, fp32=False, estimator="fgra", hll_bias=None, cap=None, stats=None, containment=None):
         """`lash dist --top`: the pairs of rows [r0, r1) x columns [0, n_cols) that can still be among some name's `top` nearest, as numpy
         arrays (row, col, dist) in (row, col) order, each evaluated exactly on the host (lash_sketch_set_pair_block_top): a superset of
         the block's part of every name's N_K given the bounds.  same_col: per block row the column with the row's name (its pair is 0),
         0xFFFFFFFF for none; col_bound / row_bound: TOP_KEY arrays (TopK.bounds), or None.  max_dist: also d <= max_dist.  cap / stats /
-        LashError.pair as pair_block_within."""
+        LashError.pair / containment as pair_block_within."""
         q = qry or self
         nc = q.n if n_cols is None else int(n_cols)
         sc = None if same_col is None else np.ascontiguousarray(same_col, dtype=np.uint32)
@@ -652,9 +658,9 @@ class SketchSet:
         assert sc is None or len(sc) >= int(r1) - int(r0)
         assert cb is None or len(cb) >= nc
         assert rb is None or len(rb) >= int(r1) - int(r0)
-        return self._kept_rows(cap, stats, lambda out: self._lib.lash_sketch_set_pair_block_top(
+        return self._kept_rows(cap, stats, lambda out: self._lib.lash_sketch_set_pair_block_top_measure(
             self._ctx._h, self._h, int(r0), int(r1), q._h, nc, 1 if triangle else 0, int(k), int(model), 1 if fp32 else 0,
-            ULL_ESTIMATORS[estimator], _bias_handle(hll_bias), int(top), float("nan") if max_dist is None else float(max_dist),
+            ULL_ESTIMATORS[estimator], _bias_handle(hll_bias), MEASURES[containment], int(top), float("nan") if max_dist is None else float(max_dist),
             None if sc is None else sc.ctypes.data, None if cb is None else cb.ctypes.data, None if rb is None else rb.ctypes.data, *out))
 
     def top_pairs(self, top, k, qry=None, triangle=None, max_dist=None, same_col=None, block_rows=None, **kw):

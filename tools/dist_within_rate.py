@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""tools/dist_within_rate.py [N] [WORKDIR] — `lash dist --max-dist` against the unfiltered run on the BASELINE configs[3] shape.
+"""tools/dist_within_rate.py [--containment] [N] [WORKDIR] — `lash dist --max-dist` against the unfiltered run on the BASELINE configs[3] shape.
 
 N (default 100 000) hmh k=16 sketches of 5 Mbp genomes made on the device as families of 10 (a synthetic base genome and 9 copies with
 0.1-10 % substitutions), written as the sketch-file set WORKDIR/w (default: a fresh directory under /dev/shm, removed at the end).
@@ -7,7 +7,12 @@ Then, with LASH_CLI_TIMING=1:
     lash dist -q w -r w -o WORKDIR/kept.tsv --max-dist 0.05        (rows kept: counted)
     lash dist -q w -r w -o /dev/null                               (the unfiltered run)
 and prints the wall times and stage marks.  With a WORKDIR given the files stay, so that a separate
-`rocprofv3 --kernel-trace --stats -- lash dist ... --max-dist 0.05` can read them."""
+`rocprofv3 --kernel-trace --stats -- lash dist ... --max-dist 0.05` can read them.
+--containment: the cost of `lash dist --containment query` in the filter.  A containment run is always the rectangle, so the set is
+also written under a second prefix v (the same sketches and names from other files: the default measure then runs the rectangle too), and
+    lash dist -q v -r w -o /dev/null --max-dist 0.05                          three times
+    lash dist -q v -r w -o /dev/null --max-dist 0.05 --containment query      three times
+are timed instead of the two runs above."""
 import os
 import subprocess
 import sys
@@ -23,8 +28,10 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import lash_amd  # noqa: E402
 import host_lib as H  # noqa: E402
 
-N = int(sys.argv[1]) if len(sys.argv) > 1 else 100_000
-keep_dir = sys.argv[2] if len(sys.argv) > 2 else None
+containment = "--containment" in sys.argv[1:]
+argv = [a for a in sys.argv[1:] if a != "--containment"]
+N = int(argv[0]) if len(argv) > 0 else 100_000
+keep_dir = argv[1] if len(argv) > 1 else None
 L, k, FAM = 5_000_000, 16, 10
 RATES = np.geomspace(0.001, 0.1, FAM - 1)                  # member m > 0: substitution rate RATES[m - 1]
 assert N % FAM == 0
@@ -72,7 +79,22 @@ if not os.path.exists(os.path.join(work, "w_sketches.bin")):
     torch.cuda.empty_cache()
 
 env = dict(os.environ, LASH_CLI_TIMING="1")
-for extra, out in ((["--max-dist", "0.05"], os.path.join(work, "kept.tsv")), ([], "/dev/null")):
+if containment:
+    if not os.path.exists(os.path.join(work, "v_sketches.bin")):
+        os.symlink("w_sketches.bin", os.path.join(work, "v_sketches.bin"))
+        open(os.path.join(work, "v_files.json"), "w").write(open(os.path.join(work, "w_files.json")).read())
+        H.write_parameters(os.path.join(work, "v"), "hmh", k, 0, 42)
+    for extra in ([], ["--containment", "query"]):
+        for rep in range(3):
+            t0 = time.perf_counter()
+            r = subprocess.run([H.CLI, "dist", "-q", "v", "-r", "w", "-o", "/dev/null", "-t", "16", "--max-dist", "0.05"] + extra, cwd=work,
+                               capture_output=True, text=True, env=env)
+            print("lash dist -q v -r w --max-dist 0.05 %s: run %d, rc %d, %.2f s wall" % (" ".join(extra) or "(default measure)", rep, r.returncode,
+                                                                                          time.perf_counter() - t0))
+            print(r.stderr[-1500:], flush=True)
+            if r.returncode:
+                sys.exit(1)
+for extra, out in () if containment else ((["--max-dist", "0.05"], os.path.join(work, "kept.tsv")), ([], "/dev/null")):
     t0 = time.perf_counter()
     r = subprocess.run([H.CLI, "dist", "-q", "w", "-r", "w", "-o", out, "-t", "16"] + extra, cwd=work, capture_output=True, text=True, env=env)
     wall = time.perf_counter() - t0
