@@ -313,7 +313,8 @@ hipError_t launch_hmh_pairs(const uint8_t *d_ref, uint32_t n_ref, const uint8_t 
 // the same counts through register bit planes (pair_planes.hip).  Row layout T[(w * 17 + b) * ldT + s] (b = 16: the plane of
 // non-zero registers) with ldT a multiple of hmh_planes_row_pad(); column layout S[(w * n_pad + s) * 20 + b] with n_pad a multiple
 // of hmh_planes_col_pad(); members beyond n read as zero sketches.  Either layout pointer may be NULL (not wanted); buffer sizes
-// from hmh_planes_T_words / hmh_planes_S_words.  d_nzcount (NULL, or zeroed [n]) receives each member's number of non-zero registers.
+// from hmh_planes_T_words / hmh_planes_S_words (both with the slack the pair kernel may read past the layout: a row workgroup of a
+// block that starts at a row0 % hmh_planes_row_pad() != 0, a column slice staged in whole rounds).  d_nzcount (NULL, or zeroed [n]) receives each member's number of non-zero registers.
 hipError_t launch_hmh_planes(const uint8_t *d_img, uint32_t hdr, uint64_t stride, uint32_t n, uint32_t *d_T, uint32_t ldT, uint32_t *d_S,
                              uint32_t n_pad, uint32_t *d_nzcount, hipStream_t stream);
 uint32_t   hmh_planes_col_pad();

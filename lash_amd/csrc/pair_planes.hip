@@ -127,7 +127,9 @@ __global__ void __launch_bounds__(256, 2) hmh_pairs_planes_kernel(PlanePairArgs 
     if (a.triangle && col0 > a.row0 + blockIdx.y * PL_ROWS + (PL_ROWS - 1u)) return;
     // addresses: wave-uniform base (SGPRs) + the lane's 32-bit offset, so that no 64-bit per-lane address is ever formed
     // (with per-lane pointers hipcc precomputed one register pair per plane: 64 registers of addresses, spills)
-    const uint32_t *__restrict__ T = a.T + a.row0 + blockIdx.y * PL_ROWS + wave * 128u;     // (T is padded: always readable)
+    const uint32_t *__restrict__ T = a.T + a.row0 + blockIdx.y * PL_ROWS + wave * 128u;     // (always readable: the rows past n_rows
+    // are T's zero padding up to ldT; with a row0 that is no multiple of PL_ROWS up to PL_ROWS - 1 more, which are the next plane's
+    // words or, behind the last plane of the last word, the PL_ROWS words hmh_planes_T_words adds.  None of them is ever stored.)
     const uint32_t *__restrict__ S = a.S + (uint64_t)col0 * PL_SN;
     const uint64_t ld = a.ldT, sp = (uint64_t)a.n_pad * PL_SN;
 
@@ -257,7 +259,9 @@ hipError_t launch_hmh_planes(const uint8_t *d_img, uint32_t hdr, uint64_t stride
 
 uint32_t hmh_planes_col_pad() { return PL_COLS; }
 uint32_t hmh_planes_row_pad() { return PL_ROWS; }
-size_t   hmh_planes_T_words(uint32_t ldT) { return (size_t)PL_WORDS * PL_TN * ldT; }
+// + the slack a block's last row workgroup may read: with row0 % PL_ROWS != 0 its rows run to row0 + PL_ROWS * gridDim.y - 1,
+// at most PL_ROWS - 1 past ldT, which at the last plane of the last word is that far past the layout (never written, never used)
+size_t   hmh_planes_T_words(uint32_t ldT) { return (size_t)PL_WORDS * PL_TN * ldT + PL_ROWS; }
 size_t   hmh_planes_S_words(uint32_t n_pad) { return (size_t)PL_WORDS * PL_SN * n_pad + 1024; }   // + the slack fetch_slice may read
 
 hipError_t launch_hmh_pairs_planes(const uint32_t *d_T, uint32_t ldT, uint32_t row0, uint32_t n_rows, const uint32_t *d_S, uint32_t n_pad,

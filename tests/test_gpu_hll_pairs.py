@@ -21,6 +21,8 @@ def _images(rng, n, p, kind):
         regs[hot] = rng.integers(24, 64 - p + 2, int(hot.sum()), dtype=np.uint8)
     elif kind == "sparse":                               # small genomes: mostly empty registers
         regs = np.where(rng.random((n, m)) < 0.8, 0, rng.integers(1, 12, (n, m))).astype(np.uint8)
+    elif kind == "narrow":                               # sketches of genomes: no empty register, none above 32 (lo > 0, lo + band <= 32)
+        regs = rng.integers(5, 31, (n, m), dtype=np.uint8)
     elif kind == "full_range":
         regs = rng.integers(0, 64 - p + 2, (n, m), dtype=np.uint8)
     else:                                                # every register equal (range of one value)
@@ -45,7 +47,7 @@ def _want(ref, qry):
 
 
 @pytest.mark.parametrize("p", [8, 10, 12, 14, 16])
-@pytest.mark.parametrize("kind", ["band", "sparse", "full_range", "flat"])
+@pytest.mark.parametrize("kind", ["band", "sparse", "full_range", "flat", "narrow"])
 def test_pair_statistics_are_exact(p, kind):
     import lash_amd
     rng = np.random.default_rng(p * 10 + len(kind))

@@ -26,8 +26,9 @@ def _numpy_counts(ref, qry):
 
 @pytest.mark.parametrize("full", [False, True])
 def test_hmh_planes_match_numpy(full):
-    """several row workgroups (256 rows each), several column tiles, ragged edges; registers from a small alphabet so that
-    equal / zero registers are frequent; `full`: no zero register anywhere (the 17-instruction form, N = 16384)"""
+    """one row workgroup (512 rows each, so 300 rows stay in blockIdx.y == 0; more of them, row offsets and the triangle:
+    test_gpu_pair_blocks.py), several column tiles, ragged edges; registers from a small alphabet so that equal / zero registers are
+    frequent; `full`: no zero register anywhere (the 17-instruction form, N = 16384)"""
     import lash_amd
     rng = np.random.default_rng(11 + full)
     nr, nq = 300, 150
