@@ -243,6 +243,41 @@ void     lash_rec_index_free(lash_ctx *ctx, lash_rec_index *index);
 int      lash_sketch_records_raw(lash_ctx *ctx, const lash_params *prm, const uint8_t *raw, const uint64_t *file_off, uint32_t n_files,
                                  const lash_rec_index *index, uint64_t r0, uint64_t r1, uint8_t *out_images);
 
+/* K-mer abundance filter (`lash sketch --min-count M`; Mash -m, not upstream): a k-mer a file holds fewer than M times stays out of its
+ * sketch.  A sequencing error makes up to k k-mers that exist nowhere else, and in a read set they can outnumber the real ones.
+ *   key      the masked canonical k-mer value the reference hands to add_kmer (utils.rs:464-499), as a u64 for all three sketch types
+ *            (HyperMinHash: before its truncation to 32 bits); both strands are one key; counted per file over all its records
+ *   table    each file has 2^L saturating byte counters (L = log2_cells[file], 10..36), zero at creation.  Every valid k-mer occurrence
+ *            increments cells  i1 = (key * 0x9E3779B97F4A7C15 mod 2^64) >> (64 - L)  and
+ *            i2 = ((key ^ (key >> 32)) * 0xC2B2AE3D27D4EB4F mod 2^64) >> (64 - L)  — one cell once when i1 == i2 — up to 255, exactly
+ *   keep     after the whole file has been counted an occurrence is kept iff min(cell[i1], cell[i2]) >= min_count; kept occurrences go
+ *            through add_kmer as ever, dropped ones are not hashed into the sketch
+ * Two passes, count everything and then test: the result depends on neither thread order nor batching.  Every k-mer with a true count
+ * >= M is in the sketch; one with a smaller count gets in only through collisions in BOTH of its cells.  min_count = 1 keeps everything:
+ * the images are byte for byte those of lash_sketch_files_raw.
+ *   create       one L per file; LASH_EINVAL outside 10..36, LASH_ENOMEM when the tables do not fit the device
+ *   count_raw    adds the k-mers of raw / file_off / file_fmt (as lash_sketch_files_raw takes them) to the tables.  May be called once per
+ *                chunk of files streamed in pieces cut between records: no k-mer spans records, so the cells equal one call's.  Only
+ *                prm->k and the context's layout fix the key: one filter serves every algo, p and seed
+ *   counts       the 2^L cells of one file, one byte each
+ *   sketch_files_raw_filtered   lash_sketch_files_raw with the keep rule; min_count 1..255; honours LASH_F_ACCUMULATE (chunks of a file
+ *                counted whole beforehand give the image of one call).  Always the pack-first route on the sliced kernel.  Supported where
+ *                the sketch's registers are a plain table in LDS: hmh, hll p <= 15, ull p <= 14
+ * LASH_EINVAL: LASH_F_AMINO, n_files different from the filter's, a filter of another device, min_count outside 1..255, a precision
+ * without a filtered launch (lash_ctx_last_error names the limits).  Malformed FASTQ as in lash_sketch_files_raw on both calls: the records
+ * needletail's iterator yields are counted and sketched, the file is listed by lash_ctx_format_errors.  HyperLogLog files that end with a
+ * register above 53 - p are NOT replayed (the replay would have to run on the filtered stream): their `sum` is the correctly rounded sum
+ * over the final registers and they stay reported by lash_ctx_hll_inexact_sums.  All four calls synchronize the context's stream. */
+typedef struct lash_kmer_filter lash_kmer_filter;
+int  lash_kmer_filter_create(lash_ctx *ctx, uint32_t n_files, const uint8_t *log2_cells, lash_kmer_filter **out);
+int  lash_kmer_filter_count_raw(lash_ctx *ctx, const lash_params *prm, const uint8_t *raw, const uint64_t *file_off,
+                                const uint8_t *file_fmt, uint32_t n_files, lash_kmer_filter *f);
+int  lash_kmer_filter_counts(lash_ctx *ctx, const lash_kmer_filter *f, uint32_t file, uint8_t *out);
+int  lash_sketch_files_raw_filtered(lash_ctx *ctx, const lash_params *prm, const uint8_t *raw, const uint64_t *file_off,
+                                    const uint8_t *file_fmt, uint32_t n_files, const lash_kmer_filter *f,
+                                    uint32_t min_count, uint8_t *out_images);
+void lash_kmer_filter_free(lash_ctx *ctx, lash_kmer_filter *f);
+
 /* HyperLogLog images carry `sum` = sum_j 2^-m[j] (f64).  streaming_algorithms keeps it incrementally per k-mer (sum -= 2^-old;
  * sum += 2^-new); that is exactly the sum over the final registers as long as every register is <= 53 - p, and the HIP path
  * writes that sum.  A register above 53 - p (one k-mer in 2^(52-p): p = 14 -> 1 in 2.7e11) makes the incremental value depend

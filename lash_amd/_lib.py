@@ -81,6 +81,11 @@ PROTOTYPES = {
     "lash_sketch_files_raw": (_int, [_vp, _PP, _vp, _vp, _vp, _u32, _vp]),
     "lash_sketch_files_raw_device": (_int, [_vp, _PP, _vp, _vp, _vp, _u32, _vp]),
     "lash_ctx_format_errors": (_u32, [_vp, _vp, _u32]),
+    "lash_kmer_filter_create": (_int, [_vp, _u32, _vp, C.POINTER(_vp)]),
+    "lash_kmer_filter_count_raw": (_int, [_vp, _PP, _vp, _vp, _vp, _u32, _vp]),
+    "lash_kmer_filter_counts": (_int, [_vp, _vp, _u32, _vp]),
+    "lash_sketch_files_raw_filtered": (_int, [_vp, _PP, _vp, _vp, _vp, _u32, _vp, _u32, _vp]),
+    "lash_kmer_filter_free": (None, [_vp, _vp]),
     "lash_fasta_index": (_int, [_vp, _vp, _vp, _u32, C.POINTER(_vp)]),
     "lash_fasta_index_device": (_int, [_vp, _vp, _vp, _u32, C.POINTER(_vp)]),
     "lash_rec_index_n_records": (_u64, [_vp]),

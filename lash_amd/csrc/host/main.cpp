@@ -4,7 +4,8 @@
 //   lash dist   -q PREFIX -r PREFIX [-o dist] [-t N] [-e fgra|ml] [-m 1|0] [--fp32] [--dm]   (main.rs:107-176, 280-617)
 //   lash hll-bias -o FILE [-p P[,P...]] [--points N] [--trials T] [--seed S] [--device D]    (not upstream: HLL++ bias tables, simulated)
 // Extras that do not exist upstream: --gpus N / --device D / --devices LIST (which GPUs to use, one worker each), --batch-mb M, --stream-mb M (files
-// larger than M MiB are streamed in chunks with on-device accumulation), --hmh-x-low, --per-record (one sketch per FASTA record, the records
+// larger than M MiB are streamed in chunks with on-device accumulation), --hmh-x-low, --min-count M [--count-cells-log2 L] (drop the k-mers a
+// file holds fewer than M times, counted on the GPU), --per-record (one sketch per FASTA record, the records
 // found on the GPU); dist: --device D, --block-rows N, --hll-bias FILE / --hll-bias-sim (HLL++ bias tables from a file / simulated on the GPU),
 // --file-order (rows / columns in list-file order instead of the reference's seeded hash-map order), --max-dist D (print only
 // the pairs with distance <= D), --top K (only each name's K nearest), --cluster D (single-linkage clusters of an all-vs-all instead
@@ -55,6 +56,11 @@ void usage()
             "      --aa                     Amino acid sketching (k 1-12); the reference carries this flag commented out\n"
             "      --per-record             One sketch per FASTA record instead of one per file (multi-FASTA collections; like Mash -i);\n"
             "                               {output}_files.json then holds the record ids.  FASTA only, not with --aa\n"
+            "      --min-count <M>          Keep only the k-mers a file holds at least M times (1-255; read sets: a sequencing error makes\n"
+            "                               k-mers seen once; like Mash -m).  Counted per file on the GPU in 2^L saturating cells, two cells\n"
+            "                               per k-mer; a rarer k-mer gets in only when collisions fill both.  Files are read twice.  hmh,\n"
+            "                               hll -p <= 15, ull -p <= 14; not with --aa or --per-record\n"
+            "      --count-cells-log2 <L>   with --min-count: cells per file, 10-36 [default: ceil(log2(8 x file bytes)), within 16-36]\n"
             "      --gpus <n> | --device <d> | --devices <d,d,...>  GPUs to use, one worker each [default: device 0]\n"
             "dist options:\n"
             "  -q, --query <prefix>  -r, --reference <prefix>  -o, --output_file <name> [default: dist]\n"
@@ -135,7 +141,8 @@ int cmd_sketch(int argc, char **argv)
     std::string err;
     const std::map<std::string, std::string> alias = {{"f", "file"}, {"o", "output"}, {"k", "kmer"}, {"t", "threads"},
                                                       {"a", "algorithm"}, {"p", "precision"}, {"s", "seed"}};
-    if (!parse(argc, argv, 2, alias, {"hmh-x-low", "aa", "per-record"}, a, err)) { fprintf(stderr, "error: %s\n", err.c_str()); return 2; }
+    if (!parse(argc, argv, 2, alias, {"hmh-x-low", "aa", "per-record", "help"}, a, err)) { fprintf(stderr, "error: %s\n", err.c_str()); return 2; }
+    if (a.flags.count("help")) { usage(); return 0; }
     if (!a.kv.count("file")) { fprintf(stderr, "error: the following required arguments were not provided:\n  --file <file>\n"); return 2; }
     SketchOptions opt;
     const std::string output = a.kv.count("output") ? a.kv["output"] : "sketch";
@@ -159,6 +166,29 @@ int cmd_sketch(int argc, char **argv)
     opt.per_record = a.flags.count("per-record") != 0;
     if (opt.per_record && amino) { fprintf(stderr, "error: --per-record cannot be used with --aa (records are split for nucleotide FASTA only)\n"); return 2; }
     if (amino && k > 12) { fprintf(stderr, "k-mer length for amino acid must be 1\xe2\x80\x93" "12\n"); return 101; }   // utils.rs:554 panic
+    if (a.kv.count("count-cells-log2") && !a.kv.count("min-count")) { fprintf(stderr, "error: --count-cells-log2 needs --min-count\n"); return 2; }
+    if (a.kv.count("min-count")) {
+        uint64_t m = 0, l2 = 0;
+        if (!to_u64(a.kv["min-count"], m) || m < 1 || m > 255) {
+            fprintf(stderr, "error: invalid value '%s' for --min-count: an integer from 1 to 255 is required\n", a.kv["min-count"].c_str());
+            return 2;
+        }
+        if (a.kv.count("count-cells-log2") && (!to_u64(a.kv["count-cells-log2"], l2) || l2 < 10 || l2 > 36)) {
+            fprintf(stderr, "error: invalid value '%s' for --count-cells-log2: an integer from 10 to 36 is required\n", a.kv["count-cells-log2"].c_str());
+            return 2;
+        }
+        if (amino) { fprintf(stderr, "error: --min-count cannot be used with --aa (k-mers are counted for nucleotide input only)\n"); return 2; }
+        if (opt.per_record) { fprintf(stderr, "error: --min-count cannot be used with --per-record (k-mers are counted per file)\n"); return 2; }
+        // the filtered launch exists where the sketch's registers are a plain table in LDS (include/lash_gfx950.h)
+        const uint64_t max_p = opt.algo == LASH_HLL ? 15 : 14;
+        if (opt.algo != LASH_HMH && p > max_p) {
+            fprintf(stderr, "error: --min-count supports -a %s up to -p %llu (and -a hmh); -p %llu is not supported\n", alg.c_str(),
+                    (unsigned long long)max_p, (unsigned long long)p);
+            return 2;
+        }
+        opt.min_count = (uint32_t)m;
+        opt.count_cells_log2 = (int)l2;
+    }
     opt.k = (int)k;
     opt.precision = (int)p;
     opt.seed = seed;

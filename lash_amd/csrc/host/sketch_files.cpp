@@ -411,6 +411,99 @@ std::string stream_big_file(lash_ctx *ctx, const lash_params &prm0, const std::s
     return result;
 }
 
+// --min-count: cells of a file's count table, from its (uncompressed) size alone
+int count_cells_log2_for(uint64_t bytes, int forced)
+{
+    if (forced) return forced;
+    int l2 = 16;
+    while (l2 < 36 && (1ull << l2) < 8 * std::min<uint64_t>(bytes, 1ull << 40)) ++l2;
+    return l2;
+}
+
+// --min-count for a file above --stream-mb: the file is read twice (a compressed one a third time before, for its size: the table's size
+// depends on the input only) — every chunk through lash_kmer_filter_count_raw, then every chunk again through the filtered call with
+// LASH_F_ACCUMULATE.  Chunks are cut between records, so the cells and the image equal those of the file in one piece; a record longer
+// than a chunk would repeat k-mers at the cut (find_cut's carried bases) and is refused.  One buffer, no overlap of reading and sketching.
+std::string stream_big_file_filtered(lash_ctx *ctx, const lash_params &prm0, const std::string &path, uint64_t chunk_bytes, PinnedBuf &buf,
+                                     uint8_t *image, uint64_t &bytes_seen, int threads, uint32_t min_count, int forced_log2, int &log2_used)
+{
+    if (!buf.reserve(chunk_bytes + 64)) return "out of pinned host memory";
+    lash_layout lay0;
+    (void)lash_ctx_get_layout(ctx, &lay0);
+    const bool skip_bad = lay0.fastq_skip_bad != 0;
+    uint64_t total = 0;
+    // chunk(p, n, fmt) per chunk, in order; it returns false to end the pass (and sets err when that is a failure)
+    auto pass = [&](const std::function<bool(const uint8_t *, size_t, int, std::string &)> &chunk) -> std::string {
+        ByteStream bs;
+        bs.set_threads(threads);
+        std::string err = bs.open(path);
+        if (!err.empty()) return err;
+        uint8_t *b = buf.p;
+        size_t have = 0;
+        bool eof = false;
+        int fmt = 0;
+        total = 0;
+        while (!eof) {
+            while (have < chunk_bytes) {
+                const long r = bs.read(b + have, chunk_bytes - have, err);
+                if (r < 0) return err + " (" + path + ")";
+                if (r == 0) { eof = true; break; }
+                have += (size_t)r;
+                total += (uint64_t)r;
+            }
+            if (!chunk) { have = 0; continue; }               // the sizing pass
+            if (!fmt && !(fmt = sniff_format(b, have)))
+                return have ? "Invalid input file: neither FASTA ('>') nor FASTQ ('@'): " + path : "Invalid input file: empty (" + path + ")";
+            std::vector<uint8_t> carry;
+            const size_t cut = eof ? have : find_cut(b, have, fmt, carry);
+            if (!carry.empty()) return "--min-count: a record of " + path + " is larger than a --stream-mb chunk and cannot be counted in pieces; raise --stream-mb";
+            if (!eof && cut == 0) return "cannot find a record boundary inside a " + std::to_string(chunk_bytes >> 20) + " MiB chunk of " + path;
+            if (!chunk(b, cut, fmt, err)) return err;
+            memmove(b, b + cut, have - cut);
+            have -= cut;
+        }
+        return "";
+    };
+    std::string err;
+    uint64_t size = 0;
+    struct stat st;
+    std::string perr;
+    if (peek_compressed(path, size, perr)) {
+        if (!(err = pass(nullptr)).empty()) return err;
+        size = total;
+    } else if (!perr.empty()) return perr;
+    else if (stat(path.c_str(), &st) == 0) size = (uint64_t)st.st_size;
+    log2_used = count_cells_log2_for(size, forced_log2);
+    const uint8_t l2 = (uint8_t)log2_used;
+    lash_kmer_filter *flt = nullptr;
+    int rc = lash_kmer_filter_create(ctx, 1, &l2, &flt);
+    if (rc != LASH_OK) return std::string("--min-count: a count table of 2^") + std::to_string(log2_used) + " cells: " + lash_strerror(rc);
+    auto gpu_error = [&](int code) { return std::string(lash_strerror(code)) + " " + lash_ctx_last_error(ctx); };
+    // a malformed FASTQ record ends needletail's iteration (utils.rs:457): the library keeps the chunk's records before it, later chunks add nothing
+    err = pass([&](const uint8_t *p, size_t n, int fmt, std::string &e) {
+        const uint64_t off[2] = {0, (uint64_t)n};
+        const uint8_t f = (uint8_t)fmt;
+        const int r = lash_kmer_filter_count_raw(ctx, &prm0, p, off, &f, 1, flt);
+        if (r != LASH_OK) { e = gpu_error(r); return false; }
+        return lash_ctx_format_errors(ctx, nullptr, 0) == 0 || skip_bad;
+    });
+    uint64_t calls = 0;
+    if (err.empty())
+        err = pass([&](const uint8_t *p, size_t n, int fmt, std::string &e) {
+            lash_params prm = prm0;
+            if (calls) prm.flags |= LASH_F_ACCUMULATE;
+            const uint64_t off[2] = {0, (uint64_t)n};
+            const uint8_t f = (uint8_t)fmt;
+            const int r = lash_sketch_files_raw_filtered(ctx, &prm, p, off, &f, 1, flt, min_count, image);
+            if (r != LASH_OK) { e = gpu_error(r); return false; }
+            ++calls;
+            return lash_ctx_format_errors(ctx, nullptr, 0) == 0 || skip_bad;
+        });
+    lash_kmer_filter_free(ctx, flt);
+    bytes_seen += total;
+    return err;
+}
+
 }  // namespace
 
 // test hook (host_hooks.cpp): the chunk-cut rule of the large-file streamer
@@ -499,6 +592,24 @@ std::string sketch_files(const SketchOptions &opt, const std::vector<std::string
         lash_rec_index_free(ctx, ix);
         return e;
     };
+    // --min-count: a batch's files are counted, then sketched with the keep rule, by the same worker (lash_kmer_filter_*)
+    std::mutex l2mu;
+    int l2_lo = 99, l2_hi = 0;                             // the table sizes this run chose (guarded by l2mu)
+    auto note_log2 = [&](int l2) { std::lock_guard<std::mutex> lk(l2mu); l2_lo = std::min(l2_lo, l2); l2_hi = std::max(l2_hi, l2); };
+    auto sketch_filtered = [&](lash_ctx *ctx, Batch &b) -> int {
+        const uint32_t ng = (uint32_t)(b.f1 - b.f0);
+        std::vector<uint8_t> l2(ng);
+        for (uint32_t g = 0; g < ng; ++g) {
+            l2[g] = (uint8_t)count_cells_log2_for(b.file_off[g + 1] - b.file_off[g], opt.count_cells_log2);
+            note_log2(l2[g]);
+        }
+        lash_kmer_filter *flt = nullptr;
+        int rc = lash_kmer_filter_create(ctx, ng, l2.data(), &flt);
+        if (rc == LASH_OK) rc = lash_kmer_filter_count_raw(ctx, &prm, b.buf->p, b.file_off.data(), b.fmt.data(), ng, flt);
+        if (rc == LASH_OK) rc = lash_sketch_files_raw_filtered(ctx, &prm, b.buf->p, b.file_off.data(), b.fmt.data(), ng, flt, opt.min_count, b.images.data());
+        lash_kmer_filter_free(ctx, flt);
+        return rc;
+    };
     auto gpu_worker = [&](int device) {
         lash_ctx *ctx = nullptr;
         int rc = lash_ctx_create(&ctx, device);
@@ -524,7 +635,9 @@ std::string sketch_files(const SketchOptions &opt, const std::vector<std::string
                     const uint32_t ng = (uint32_t)(b->f1 - b->f0);
                     b->images.assign((size_t)ng * ib, 0);
                     const auto g0 = std::chrono::steady_clock::now();
-                    int r2 = lash_sketch_files_raw(ctx, &prm, b->buf->p, b->file_off.data(), b->fmt.data(), ng, b->images.data());
+                    int r2;
+                    if (opt.min_count) r2 = sketch_filtered(ctx, *b);
+                    else r2 = lash_sketch_files_raw(ctx, &prm, b->buf->p, b->file_off.data(), b->fmt.data(), ng, b->images.data());
                     mark("GPU done, batch", b->index, std::chrono::duration<double>(std::chrono::steady_clock::now() - g0).count());
                     if (r2 != LASH_OK) b->err = std::string(lash_strerror(r2)) + " " + lash_ctx_last_error(ctx);
                     else if (prm.algo == LASH_HLL) {
@@ -807,7 +920,13 @@ std::string sketch_files(const SketchOptions &opt, const std::vector<std::string
                     if (rc != LASH_OK) { err = lash_strerror(rc); break; }
                 }
                 uint64_t seen = 0;
-                b->err = stream_big_file(stream_ctx, prm, files[i], stream_bytes, stream_buf, stream_buf2, b->images.data(), seen, opt.threads);
+                if (opt.min_count) {
+                    int l2 = 0;
+                    b->err = stream_big_file_filtered(stream_ctx, prm, files[i], stream_bytes, stream_buf, b->images.data(), seen, opt.threads, opt.min_count,
+                                                      opt.count_cells_log2, l2);
+                    if (l2) note_log2(l2);
+                } else
+                    b->err = stream_big_file(stream_ctx, prm, files[i], stream_bytes, stream_buf, stream_buf2, b->images.data(), seen, opt.threads);
                 n_bytes += seen;
                 std::lock_guard<std::mutex> lk(qmu);
                 b->index = batch_index++;
@@ -853,6 +972,9 @@ std::string sketch_files(const SketchOptions &opt, const std::vector<std::string
         out << json_pretty_string_array(opt.per_record ? record_names : files);
         if (!out.good()) return "write failed";
     }
+    if (opt.min_count && l2_hi)
+        fprintf(stderr, "--min-count %u: count tables of 2^%d%s cells per file\n", opt.min_count, l2_lo,
+                l2_lo == l2_hi ? "" : (" to 2^" + std::to_string(l2_hi)).c_str());
     if (stats) {
         stats->files = n_files;
         stats->records = n_records;

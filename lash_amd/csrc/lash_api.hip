@@ -251,7 +251,7 @@ void lash_ctx_destroy(lash_ctx *ctx)
     release(ctx->sole_state);
     for (DevBuf *b : {&ctx->items, &ctx->item_begin, &ctx->item_kmers, &ctx->partials, &ctx->gregs, &ctx->counter, &ctx->st_seq, &ctx->st_rec,
                       &ctx->st_img, &ctx->hll_flags, &ctx->ec_ref, &ctx->ec_qry, &ctx->ec_x, &ctx->ec_card, &ctx->wf_scratch, &ctx->wf_out, &ctx->top_buf, &ctx->hll_bm_ref,
-                      &ctx->hll_bm_qry, &ctx->hll_lohi, &ctx->fa_off, &ctx->fa_scratch})
+                      &ctx->hll_bm_qry, &ctx->hll_lohi, &ctx->fa_off, &ctx->fa_scratch, &ctx->kf_keep})
         release(*b);
     {
         lash_packed &sc = ctx->scratch;
@@ -774,6 +774,187 @@ int lash_synth_genomes_device(lash_ctx *ctx, uint64_t first_genome, uint32_t n_g
     if (!ctx || (n_genomes && n_bases && !d_out)) return LASH_EINVAL;
     (void)hipSetDevice(ctx->device);
     HIPCHK(ctx, launch_synth(first_genome, n_genomes, n_bases, d_out, ctx->stream));
+    return LASH_OK;
+}
+
+}  // extern "C"
+
+// ---- k-mer abundance filter (kmer_filter.hip; `lash sketch --min-count`) ------------------------------------------------------------
+
+// Stages `raw` and packs it into the context's scratch batch; synchronizes.  Files whose FASTQ structure broke (ctx->bad_files) are packed a
+// second time from a copy that lash_fastq_sanitize has cut down to the records needletail's iterator yields, so the counting pass and the
+// filtered sketch see exactly the records lash_sketch_files_raw sketches for such a file.
+static int filter_pack(lash_ctx *ctx, const uint8_t *raw, const uint64_t *file_off, const uint8_t *file_fmt, uint32_t n_files)
+{
+    int rc;
+    const uint64_t bytes = file_off[n_files];
+    if ((rc = reserve(ctx, ctx->st_seq, bytes + 64))) return rc;
+    const uint8_t *d_raw = static_cast<const uint8_t *>(ctx->st_seq.ptr);
+    std::vector<uint8_t> clean;
+    std::vector<uint32_t> bad;
+    for (int pass = 0; pass < 2; ++pass) {
+        const uint8_t *src = pass ? clean.data() : raw;
+        if (bytes) HIPCHK(ctx, hipMemcpyAsync(ctx->st_seq.ptr, src, bytes, hipMemcpyHostToDevice, ctx->stream));
+        if ((rc = pack_into(ctx, &ctx->scratch, ctx->stream, nullptr, d_raw, d_raw + bytes, nullptr, 0, nullptr, file_off, n_files, file_fmt))) return rc;
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+        if ((rc = check_pack_flag(ctx, &ctx->scratch))) return rc;
+        ctx->raw_files_pending = n_files;
+        if ((rc = read_format_errors(ctx))) return rc;
+        if (pass || ctx->bad_files.empty()) break;
+        bad = ctx->bad_files;
+        clean.assign(raw, raw + bytes);
+        for (uint32_t g : bad)
+            lash_fastq_sanitize(clean.data() + file_off[g], file_off[g + 1] - file_off[g], ctx->layout.fastq_skip_bad);
+    }
+    if (!bad.empty()) ctx->bad_files = bad;                          // still reported (lash_ctx_format_errors)
+    return LASH_OK;
+}
+
+static KmerFilterArgs filter_args(const lash_ctx *ctx, const lash_params *prm, const lash_kmer_filter *f)
+{
+    const lash_packed &pk = ctx->scratch;
+    KmerFilterArgs a{};
+    a.words = static_cast<const uint32_t *>(pk.words.ptr);
+    a.brk = static_cast<const uint32_t *>(pk.brk.ptr);
+    a.genomes = pk.d_descs;
+    a.nvalid = pk.d_nvalid;
+    a.cell_word = f->d_cell_word;
+    a.log2_cells = f->d_log2;
+    a.cells = static_cast<uint32_t *>(f->cells.ptr);
+    a.comp_mask = layout_dev(ctx->layout, prm->algo).comp_mask;
+    a.n_genomes = pk.n_genomes;
+    a.k = prm->k;
+    return a;
+}
+
+static uint64_t longest_file(const uint64_t *file_off, uint32_t n_files)
+{
+    uint64_t m = 0;
+    for (uint32_t g = 0; g < n_files; ++g) m = std::max(m, file_off[g + 1] - file_off[g]);
+    return m;
+}
+
+static int filter_call_check(lash_ctx *ctx, const lash_params *prm, const uint8_t *raw, const uint64_t *file_off, const uint8_t *file_fmt,
+                             uint32_t n_files, const lash_kmer_filter *f)
+{
+    if (!ctx || !f || !file_off || (n_files && !file_fmt)) return LASH_EINVAL;
+    const int rc = lash_params_check(prm);
+    if (rc) return rc;
+    if ((prm->flags & LASH_F_AMINO) || n_files != f->n_files || f->device != ctx->device) return LASH_EINVAL;
+    if (file_off[n_files] && !raw) return LASH_EINVAL;
+    return LASH_OK;
+}
+
+extern "C" {
+
+int lash_kmer_filter_create(lash_ctx *ctx, uint32_t n_files, const uint8_t *log2_cells, lash_kmer_filter **out)
+{
+    if (!ctx || !out || (n_files && !log2_cells)) return LASH_EINVAL;
+    *out = nullptr;
+    for (uint32_t g = 0; g < n_files; ++g)
+        if (log2_cells[g] < 10 || log2_cells[g] > 36) return LASH_EINVAL;
+    (void)hipSetDevice(ctx->device);
+    lash_kmer_filter *f = new (std::nothrow) lash_kmer_filter();
+    if (!f) return LASH_ENOMEM;
+    f->device = ctx->device;
+    f->n_files = n_files;
+    f->log2_cells.assign(log2_cells, log2_cells + n_files);
+    f->cell_word.assign((size_t)n_files + 1, 0);
+    for (uint32_t g = 0; g < n_files; ++g) f->cell_word[g + 1] = f->cell_word[g] + (1ull << (log2_cells[g] - 2));
+    auto run = [&]() -> int {
+        int rc;
+        if ((rc = reserve(ctx, f->cells, (size_t)f->cell_word[n_files] * 4))) return rc;
+        if (f->cell_word[n_files]) HIPCHK(ctx, hipMemsetAsync(f->cells.ptr, 0, (size_t)f->cell_word[n_files] * 4, ctx->stream));
+        std::vector<Section> sec = {{f->cell_word.data(), f->cell_word.size() * 8, 0}, {f->log2_cells.data(), f->log2_cells.size(), 0}};
+        const size_t total = layout_sections(sec);
+        if ((rc = reserve(ctx, f->tables, total))) return rc;
+        if ((rc = upload_sections(ctx, f->tables.ptr, sec, total, ctx->stream))) return rc;
+        f->d_cell_word = reinterpret_cast<const uint64_t *>(static_cast<const uint8_t *>(f->tables.ptr) + sec[0].off);
+        f->d_log2 = static_cast<const uint8_t *>(f->tables.ptr) + sec[1].off;
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+        return LASH_OK;
+    };
+    const int rc = run();
+    if (rc) {
+        (void)hipGetLastError();
+        lash_kmer_filter_free(ctx, f);
+        return rc;                                                   // (tables that do not fit: LASH_ENOMEM, from hipMalloc)
+    }
+    *out = f;
+    return LASH_OK;
+}
+
+void lash_kmer_filter_free(lash_ctx *ctx, lash_kmer_filter *f)
+{
+    if (!f) return;
+    (void)hipSetDevice(f->device);
+    if (ctx && ctx->stream) (void)hipStreamSynchronize(ctx->stream);
+    release(f->cells);
+    release(f->tables);
+    delete f;
+}
+
+int lash_kmer_filter_count_raw(lash_ctx *ctx, const lash_params *prm, const uint8_t *raw, const uint64_t *file_off, const uint8_t *file_fmt,
+                               uint32_t n_files, lash_kmer_filter *f)
+{
+    int rc = filter_call_check(ctx, prm, raw, file_off, file_fmt, n_files, f);
+    if (rc) return rc;
+    (void)hipSetDevice(ctx->device);
+    ctx->bad_files.clear();
+    if (n_files == 0) return LASH_OK;
+    if ((rc = filter_pack(ctx, raw, file_off, file_fmt, n_files))) return rc;
+    HIPCHK(ctx, launch_kmer_count(filter_args(ctx, prm, f), longest_file(file_off, n_files), ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return LASH_OK;
+}
+
+int lash_kmer_filter_counts(lash_ctx *ctx, const lash_kmer_filter *f, uint32_t file, uint8_t *out)
+{
+    if (!ctx || !f || !out || file >= f->n_files || f->device != ctx->device) return LASH_EINVAL;
+    (void)hipSetDevice(ctx->device);
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    // cell i is byte i & 3 of word i >> 2: on the (little-endian) host the words ARE the cells in order
+    HIPCHK(ctx, hipMemcpy(out, static_cast<const uint32_t *>(f->cells.ptr) + f->cell_word[file], (size_t)1 << f->log2_cells[file], hipMemcpyDeviceToHost));
+    return LASH_OK;
+}
+
+int lash_sketch_files_raw_filtered(lash_ctx *ctx, const lash_params *prm, const uint8_t *raw, const uint64_t *file_off, const uint8_t *file_fmt,
+                                   uint32_t n_files, const lash_kmer_filter *f, uint32_t min_count, uint8_t *out_images)
+{
+    int rc = filter_call_check(ctx, prm, raw, file_off, file_fmt, n_files, f);
+    if (rc) return rc;
+    if (min_count < 1 || min_count > 255 || (n_files && !out_images)) return LASH_EINVAL;
+    // the filtered launch exists for plans with a plain register table in LDS (hmh; hll p <= 15, ull p <= 14 by default)
+    if (!sketch_plan_keeps(make_sketch_plan(prm->algo, prm->k, prm->p, rule_variant(ctx->layout, prm->algo, prm->flags)))) {
+        ctx->err = "lash_sketch_files_raw_filtered: this sketch type / precision has no filtered launch (hmh, hll p <= 15, ull p <= 14)";
+        return LASH_EINVAL;
+    }
+    (void)hipSetDevice(ctx->device);
+    ctx->bad_files.clear();
+    ctx->last_packed.clear();
+    ctx->last_sole_only = false;
+    ctx->last.calls += 1;
+    if (n_files == 0) return LASH_OK;
+    if ((rc = filter_pack(ctx, raw, file_off, file_fmt, n_files))) return rc;
+    const std::vector<uint32_t> bad = ctx->bad_files;                // (sketch_from leaves them alone; kept across the launches anyway)
+    const size_t img_bytes = (size_t)n_files * image_bytes(ctx->layout, prm->algo, prm->p);
+    if ((rc = reserve(ctx, ctx->st_img, img_bytes + 64))) return rc;
+    if ((rc = reserve(ctx, ctx->kf_keep, (size_t)ctx->scratch.total_brk * 4))) return rc;
+    if ((prm->flags & LASH_F_ACCUMULATE) && img_bytes)
+        HIPCHK(ctx, hipMemcpyAsync(ctx->st_img.ptr, out_images, img_bytes, hipMemcpyHostToDevice, ctx->stream));
+    KmerFilterArgs ka = filter_args(ctx, prm, f);
+    ka.keep = static_cast<uint32_t *>(ctx->kf_keep.ptr);
+    ka.min_count = min_count;
+    HIPCHK(ctx, launch_kmer_keep(ka, longest_file(file_off, n_files), ctx->stream));
+    if ((rc = timing_begin(ctx))) return rc;
+    lash_params fp = *prm;
+    fp.flags |= LASH_F_NO_DIRECT | LASH_F_NO_SOLE;                   // always the pack-first route, every file on the sliced kernel
+    rc = sketch_from(ctx, &fp, &ctx->scratch, static_cast<uint8_t *>(ctx->st_img.ptr), ctx->cur_ev, true, ka.keep);
+    ctx->cur_ev = nullptr;
+    if (rc) return rc;
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    if (img_bytes) HIPCHK(ctx, hipMemcpy(out_images, ctx->st_img.ptr, img_bytes, hipMemcpyDeviceToHost));
+    ctx->bad_files = bad;
     return LASH_OK;
 }
 

@@ -93,6 +93,18 @@ struct lash_packed {
                                          // packed batch belongs to that table; lash_sketch_packed_device refuses another (round 6)
 };
 
+// per-file k-mer count tables of `lash sketch --min-count` (kmer_filter.hip): 2^log2_cells[g] saturating byte counters per file, four to a word
+struct lash_kmer_filter {
+    int device = 0;
+    uint32_t n_files = 0;
+    std::vector<uint8_t> log2_cells;
+    std::vector<uint64_t> cell_word;      // [n_files + 1] first 32-bit word of each file's table
+    DevBuf cells;
+    DevBuf tables;                        // device copies: [cell_word | log2_cells]
+    const uint64_t *d_cell_word = nullptr;
+    const uint8_t *d_log2 = nullptr;
+};
+
 struct lash_ctx;
 // N serialized sketches resident in HBM + what the pair kernels derive from them once (sketch_set.hip)
 struct lash_sketch_set {
@@ -159,6 +171,7 @@ struct lash_ctx {
                                          // counts | ticket]; record starts as bits at absolute byte positions
     bool last_sole_only = false;         // the last sketch call ran on that kernel alone (lash_timing::bases_last comes from its census)
     DevBuf st_seq, st_rec, st_img;       // staging for the synchronous host-buffer entries (files_raw, merge, pair statistics)
+    DevBuf kf_keep;                      // lash_sketch_files_raw_filtered: the batch's keep bits, laid out like the packed batch's brk
     DevBuf fa_off, fa_scratch;           // lash_fasta_index[_device]: the file offsets; [masks | tile counts | tile bases] of fasta_index.hip
     // lash_sketch_batch[_async]: two staging slots and two copy streams, so that the H2D copy of batch n+1 and the D2H copy of
     // batch n-1 run while the kernels of batch n do (PCIe Gen5 moves 1 B/base: the host-buffer entry is link-bound)

@@ -25,7 +25,10 @@ int sole_run(lash_ctx *ctx, const lash_params *prm, const SolePlan &sp, uint64_t
              const uint64_t *d_rec_off, uint64_t n_rec, bool any_multi, bool rec_identity, const uint64_t *genome_byte_off, const lash_packed *pk,
              uint32_t n_genomes, uint8_t *d_out_images, uint32_t *per_genome_ndel);
 int sole_call(lash_ctx *ctx, const lash_params *prm, const SolePlan &sp, uint32_t n_genomes, EvSet *ev, const std::function<int()> &run);
-int sketch_from(lash_ctx *ctx, const lash_params *prm, const lash_packed *pk, uint8_t *d_out_images, EvSet *ev, bool allow_bins = true);
+// d_keep: NULL, or the batch's keep bits (kmer_keep_kernel): the filtered launch — pk is packed, prm carries LASH_F_NO_SOLE, the plan keeps
+// a plain LDS table (sketch_plan_keeps) and never defers signatures
+int sketch_from(lash_ctx *ctx, const lash_params *prm, const lash_packed *pk, uint8_t *d_out_images, EvSet *ev, bool allow_bins = true,
+                const uint32_t *d_keep = nullptr);
 int sketch_aa(lash_ctx *ctx, const lash_params *prm, const uint8_t *d_seq, const uint64_t *d_rec_off, uint64_t n_rec,
               const uint64_t *genome_rec_off, const uint64_t *genome_byte_off, uint32_t n_genomes, uint8_t *d_out_images, bool allow_bins = true);
 

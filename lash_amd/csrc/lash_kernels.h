@@ -26,7 +26,11 @@ struct SketchArgs {
     int               accumulate;
     // direct mode (sketch_kernel<..., DIRECT>): format-0 genomes are read as ASCII straight from the caller's buffer
     const uint8_t    *seq;        // the caller's record bytes
-    const uint32_t   *brk_bytes;  // record-break bitmap in BYTE positions (== base positions while nothing is deleted)
+    union {                       // (one slot: the struct is laid out as before the filtered launch existed, so every other kernel is the code it was)
+        const uint32_t *brk_bytes;    // direct mode: record-break bitmap in BYTE positions (== base positions while nothing is deleted)
+        const uint32_t *keep;         // filtered launches (sketch_kernel<REGS_LDS_KEEP>, packed input only; kmer_filter.hip): one bit per base position, laid
+                                      // out like brk — bit i of a genome is set when the k-mer that starts at base i goes into the sketch
+    };
     const uint8_t    *safe;       // >= 128 readable bytes: load target of lanes that are not on the fast path
     uint32_t         *dirty;      // [n_genomes + 1] per genome: the direct pass hands this genome to stream_sketch_kernel (much dense
                                   // dirt, or a gap beyond its look-ahead scan); the stream launch runs only these
@@ -117,6 +121,35 @@ hipError_t launch_sketch_stream(const SketchPlan &plan, const SketchArgs &args, 
 uint32_t sketch_direct_stage_bytes(const SketchPlan &plan);
 hipError_t launch_sketch(const SketchPlan &plan, const SketchArgs &args, uint32_t n_items, hipStream_t stream,
                          bool direct = false);
+// the packed launch with args.keep ANDed into every lane's validity mask (lash_sketch_files_raw_filtered).  Only for plans with a plain
+// register table in LDS (sketch_plan_keeps): anything else is hipErrorInvalidValue
+hipError_t launch_sketch_keep(const SketchPlan &plan, const SketchArgs &args, uint32_t n_items, hipStream_t stream);
+inline bool sketch_plan_keeps(const SketchPlan &plan) { return plan.use_lds && !plan.bins && !plan.bytes && plan.parts_log2 == 0; }
+
+// ---- k-mer abundance filter (kmer_filter.hip; `lash sketch --min-count`) ------------------------------------------------------
+// Two passes over the pack stage's output.  kmer_count_kernel adds every valid k-mer occurrence of genome g to two saturating byte
+// counters of the genome's table of 2^log2_cells[g] cells (four cells to a 32-bit word, cell i in byte i & 3 of word i >> 2):
+//     i1 = (key * 0x9E3779B97F4A7C15) >> (64 - L),   i2 = ((key ^ (key >> 32)) * 0xC2B2AE3D27D4EB4F) >> (64 - L)
+// (once when i1 == i2), key = the canonical masked k-mer as add_kmer takes it.  kmer_keep_kernel then sets keep bit i of a genome
+// iff position i starts a valid k-mer and min(cell[i1], cell[i2]) >= min_count.
+struct KmerFilterArgs {
+    const uint32_t   *words;       // the packed batch
+    const uint32_t   *brk;
+    const GenomeDesc *genomes;
+    const uint64_t   *nvalid;
+    const uint64_t   *cell_word;   // [n_genomes] first 32-bit word of each genome's table in cells
+    const uint8_t    *log2_cells;  // [n_genomes]
+    uint32_t         *cells;
+    uint32_t         *keep;        // kmer_keep_kernel: the batch's keep bits, laid out like brk; every word a lane of the sketch launch reads is written
+    uint32_t          comp_mask;   // LayoutDev::comp_mask
+    uint32_t          n_genomes;
+    uint32_t          min_count;   // kmer_keep_kernel
+    int               k;
+};
+constexpr uint64_t KMER_FILTER_MUL1 = 0x9E3779B97F4A7C15ull, KMER_FILTER_MUL2 = 0xC2B2AE3D27D4EB4Full;
+// max_bytes: the longest genome of the batch (sizes the grid)
+hipError_t launch_kmer_count(const KmerFilterArgs &args, uint64_t max_bytes, hipStream_t stream);
+hipError_t launch_kmer_keep(const KmerFilterArgs &args, uint64_t max_bytes, hipStream_t stream);
 // ---- whole small genomes on persistent workgroups (sole_kernels.hip, round 5) -------------------------------------------------
 // One sketch per file whatever its size (utils.rs:450-509): a collection of viruses, plasmids, amplicons or contigs is very many
 // genomes of a few kbp.  sketch_kernel gives each a workgroup of its own, whose fixed cost — three dependent loads to find its

@@ -894,8 +894,10 @@ static int direct_launches(lash_ctx *ctx, const lash_params *prm, const SketchPl
     return LASH_OK;
 }
 
-int sketch_from(lash_ctx *ctx, const lash_params *prm, const lash_packed *pk, uint8_t *d_out_images, EvSet *ev, bool allow_bins)
+int sketch_from(lash_ctx *ctx, const lash_params *prm, const lash_packed *pk, uint8_t *d_out_images, EvSet *ev, bool allow_bins,
+                const uint32_t *d_keep)
 {
+    if (d_keep && (pk->direct || !(prm->flags & LASH_F_NO_SOLE))) return LASH_EINVAL;
     const uint32_t n_genomes = pk->n_genomes;
     lash_packed *mpk = const_cast<lash_packed *>(pk);
     // Genomes of at most sole_max bytes go to the persistent kernel (sole_kernels.hip), the others are cut into work items as ever;
@@ -928,7 +930,8 @@ int sketch_from(lash_ctx *ctx, const lash_params *prm, const lash_packed *pk, ui
     const uint64_t slots = (uint64_t)ctx->cu_count * std::min(wg_per_cu, 2048u / plan.threads);
     const ItemPlan ip = plan_items(blen, plan, slots, pk->direct, pk->stream_first, plan_knobs());
     const uint32_t n_items = (uint32_t)ip.items.size();
-    plan.defer = ip.defer;
+    plan.defer = ip.defer && !d_keep;
+    if (d_keep && !sketch_plan_keeps(plan)) return LASH_EINVAL;
     if (pk->direct)
         for (uint32_t g = 0; g < n_genomes; ++g) mpk->h_descs[g].handover = ip.handover[g];
     TRACE("sketch: planned");
@@ -944,7 +947,7 @@ int sketch_from(lash_ctx *ctx, const lash_params *prm, const lash_packed *pk, ui
     }
     BinsRun br;
     if ((rc = reserve_stage(ctx, prm, plan, ip, entries, br))) return rc;
-    if (!br.fits) return sketch_from(ctx, prm, pk, d_out_images, ev, false);
+    if (!br.fits) return sketch_from(ctx, prm, pk, d_out_images, ev, false, d_keep);
     const WorkItem *d_items;
     const uint32_t *d_item_begin, *d_item_order = nullptr;
     {
@@ -999,11 +1002,12 @@ int sketch_from(lash_ctx *ctx, const lash_params *prm, const lash_packed *pk, ui
     sa.nvalid = pk->d_nvalid;
     sa.item_order = d_item_order;
     sa.safe = static_cast<const uint8_t *>(ctx->counter.ptr) + 128;
+    if (d_keep) sa.keep = d_keep;                                  // (shares its slot with the direct route's brk_bytes; a filtered batch is never direct)
     if (pk->direct) {
         if ((rc = direct_launches(ctx, prm, plan, mpk, ip, sa, br, d_item_begin, ev))) return rc;
     } else {
         rc = launch_items(ctx, plan, prm, sa, br, ip.item_begin, d_item_begin, [&](const SketchArgs &a, uint32_t cnt) -> int {
-            HIPCHK(ctx, launch_sketch(plan, a, cnt, ctx->stream));
+            HIPCHK(ctx, d_keep ? launch_sketch_keep(plan, a, cnt, ctx->stream) : launch_sketch(plan, a, cnt, ctx->stream));
             return LASH_OK;
         });
         if (rc) return rc;

@@ -22,10 +22,17 @@
 namespace lash {
 
 // XLOW: the rule's variant (HyperMinHash x = low half; HyperLogLog bucket = top bits; sketch_rules.h, add_kmer)
-template <int ALGO, int KMODE, bool XLOW, int REGS, bool DIRECT, bool DEFER = false>
+// KEEP: a filtered launch (lash_sketch_files_raw_filtered) — the lane's validity mask is ANDed with the keep bits of its 64 positions
+// (SketchArgs::keep, written by kmer_keep_kernel), so dropped k-mers are neither hashed into the table nor counted in the census.
+// The flag travels as a value of the register-table parameter, REGS_LDS_KEEP = REGS_LDS with KEEP: the template's parameter list, and with
+// it the names of the existing instantiations (tests/test_kernel_budget.py and the profiles go by them), stay what they were.
+template <int ALGO, int KMODE, bool XLOW, int REGS_, bool DIRECT, bool DEFER = false>
 __global__ void __launch_bounds__(1024) LASH_SKETCH_WAVES_PER_EU_ATTR sketch_kernel(SketchArgs a)
 {
+    constexpr bool KEEP = REGS_ == REGS_LDS_KEEP;
+    constexpr int REGS = KEEP ? REGS_LDS : REGS_;
     static_assert(!DEFER || (ALGO == 0 && REGS == REGS_LDS), "deferred signatures: HyperMinHash, one LDS table");
+    static_assert(!KEEP || (!DIRECT && !DEFER && REGS == REGS_LDS), "keep bits: the packed launch with a plain LDS table");
     // dynamic LDS: [nreg32 register words][16 words of per-wave census]; registers start at LDS offset 0 so the
     // bucket offset goes straight into the ds_max / ds_or address
     extern __shared__ __attribute__((aligned(16))) uint32_t lds_regs[];
@@ -297,6 +304,10 @@ __global__ void __launch_bounds__(1024) LASH_SKETCH_WAVES_PER_EU_ATTR sketch_ker
         } else if (active) {
             c0 = cur.q.x; c1 = cur.q.y; c2 = cur.q.z; c3 = cur.q.w; c4 = cur.c4; c5 = cur.c5;
             kv = kmer_valid_mask(cur.b.x, cur.b.y, cur.b.z, (uint32_t)pos0, (uint32_t)nk, k);
+            if constexpr (KEEP) {
+                const uint32_t *kb = a.keep + gd.brk_off + (w0 >> 1);      // (w0 < nk_words here: kmer_keep_kernel wrote both words)
+                kv &= (uint64_t)kb[0] | ((uint64_t)kb[1] << 32);
+            }
         }
         tile_load(tile + step, nxt);                                    // (see the top of the loop)
         // wave-uniform: every lane of this wave has 64 real k-mers -> no per-k-mer masking at all
@@ -1315,12 +1326,12 @@ static uint32_t stage_stride_bytes(const SketchPlan &plan, bool direct, bool def
 uint32_t sketch_direct_stage_bytes(const SketchPlan &plan) { return (plan.threads / 64u) * stage_stride_bytes(plan, true, true); }
 uint32_t sketch_bin_wave_bytes(const SketchPlan &plan) { return plan.bins ? ((1u << (plan.bins_log2 + plan.bin_sub_shift)) * (1u + bin_row_stride(plan.bin_S))) * 4u : 0u; }
 
-template <int ALGO, int KMODE, bool XLOW, int REGS, bool DIRECT>
+template <int ALGO, int KMODE, bool XLOW, int REGS, bool DIRECT, bool KEEP = false>
 static hipError_t launch_one(const SketchPlan &plan, const SketchArgs &args, uint32_t n_items, hipStream_t stream)
 {
-    auto kern = sketch_kernel<ALGO, KMODE, XLOW, REGS, DIRECT>;
+    auto kern = sketch_kernel<ALGO, KMODE, XLOW, KEEP ? REGS_LDS_KEEP : REGS, DIRECT>;
     bool defer = false;
-    if constexpr (ALGO == 0 && REGS == REGS_LDS) {
+    if constexpr (ALGO == 0 && REGS == REGS_LDS && !KEEP) {
         if (plan.defer) { kern = sketch_kernel<ALGO, KMODE, XLOW, REGS, DIRECT, true>; defer = true; }
     }
     SketchArgs a = args;
@@ -1382,6 +1393,26 @@ hipError_t launch_sketch(const SketchPlan &plan, const SketchArgs &args, uint32_
 {
     if (n_items == 0) return hipSuccess;
     return direct ? launch_algo<true>(plan, args, n_items, stream) : launch_algo<false>(plan, args, n_items, stream);
+}
+
+template <int ALGO, bool XLOW>
+static hipError_t launch_keep_kmode(const SketchPlan &plan, const SketchArgs &args, uint32_t n, hipStream_t s)
+{
+    if (plan.k == 16) return launch_one<ALGO, KM_16, XLOW, REGS_LDS, false, true>(plan, args, n, s);
+    if (plan.k < 16) return launch_one<ALGO, KM_LT16, XLOW, REGS_LDS, false, true>(plan, args, n, s);
+    return launch_one<ALGO, KM_GT16, XLOW, REGS_LDS, false, true>(plan, args, n, s);
+}
+
+hipError_t launch_sketch_keep(const SketchPlan &plan, const SketchArgs &args, uint32_t n_items, hipStream_t stream)
+{
+    if (!sketch_plan_keeps(plan) || plan.defer || !args.keep) return hipErrorInvalidValue;
+    if (n_items == 0) return hipSuccess;
+    switch (plan.algo) {
+    case 0: return plan.variant ? launch_keep_kmode<0, true>(plan, args, n_items, stream) : launch_keep_kmode<0, false>(plan, args, n_items, stream);
+    case 1: return plan.variant ? launch_keep_kmode<1, true>(plan, args, n_items, stream) : launch_keep_kmode<1, false>(plan, args, n_items, stream);
+    case 2: return launch_keep_kmode<2, false>(plan, args, n_items, stream);
+    default: return hipErrorInvalidValue;
+    }
 }
 
 // Are all records of a genome the same length (a FASTQ read set)?  Then record starts are the multiples of that length and the

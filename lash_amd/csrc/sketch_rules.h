@@ -398,7 +398,8 @@ struct LdsThrRegsT {
 using LdsThrRegs = LdsThrRegsT<16u>;      // x = high half (the default)
 using LdsThrRegsX = LdsThrRegsT<14u>;     // x = low half
 
-enum { REGS_LDS = 0, REGS_GLOBAL = 1, REGS_BINS = 2, REGS_BYTES = 3 };
+enum { REGS_LDS = 0, REGS_GLOBAL = 1, REGS_BINS = 2, REGS_BYTES = 3,
+       REGS_LDS_KEEP = 4 };   // sketch_kernel only: REGS_LDS, with the keep bits of a filtered launch ANDed into the validity mask (kmer_filter.hip)
 
 // ------------------------------------------------------------------------------------------------------------
 // the three add_kmer rules.  `vm` is 0 or ~0: invalid k-mers degrade to no-ops (max with "empty", OR 0).
@@ -687,6 +688,23 @@ __device__ __forceinline__ void canon_gt16(int r, uint32_t c0, uint32_t c1, uint
     min_u64(f_lo, f_hi, q_lo, q_hi, can_lo, can_hi);                           // km.min(rc), utils.rs:494
 }
 
+// The canonical masked k-mer of start position r (0..15) of a word, as add_kmer takes it: can_lo, and can_hi for k > 16 (left alone
+// otherwise).  Every walk over the packed stream forms its k-mers here: the register updates below and the counting and keep passes of
+// kmer_filter.hip.
+template <int KMODE, int K = 0>
+__device__ __forceinline__ void canon_kmer(int r, uint32_t c0, uint32_t c1, uint32_t c2, uint32_t r0, uint32_t r1, uint32_t r2, const KParams &kp,
+                                           uint32_t &can_lo, uint32_t &can_hi)
+{
+    if constexpr (KMODE == KM_GT16) {
+        canon_gt16<K>(r, c0, c1, c2, r0, r1, r2, kp, can_lo, can_hi);
+    } else {
+        uint32_t fwd = r ? alignbit(c0, c1, 32 - 2 * r) : c0;
+        uint32_t rc = r ? alignbit(r1, r0, 2 * r) : r0;
+        if constexpr (KMODE == KM_LT16) { fwd >>= kp.sh_lt; rc &= kp.mask_lt; }
+        can_lo = fwd < rc ? fwd : rc;                                        // utils.rs:470,482
+    }
+}
+
 // layout.kmer_lsb_first (SURVEY App. D, U5 alternative: a k-mer's FIRST base in its least significant bits) needs no code here:
 // the iterator's value is then the group-reversed window, and with cm = the complement mask on 2k bits
 //     groups_reversed(fwd) = rc ^ cm,   its reverse complement = fwd ^ cm,
@@ -702,14 +720,7 @@ __device__ __forceinline__ uint32_t process_word(const Regs &regs, const KParams
     for (int r = 0; r < 16; ++r) {
         const uint32_t vm = MASKED ? (uint32_t)__builtin_amdgcn_sbfe((int)kvw, r, 1) : 0xFFFFFFFFu;   // 0 or ~0
         uint32_t can_lo, can_hi = 0;
-        if constexpr (KMODE == KM_GT16) {
-            canon_gt16<K>(r, c0, c1, c2, r0, r1, r2, kp, can_lo, can_hi);
-        } else {
-            uint32_t fwd = r ? alignbit(c0, c1, 32 - 2 * r) : c0;
-            uint32_t rc = r ? alignbit(r1, r0, 2 * r) : r0;
-            if constexpr (KMODE == KM_LT16) { fwd >>= kp.sh_lt; rc &= kp.mask_lt; }
-            can_lo = fwd < rc ? fwd : rc;                                        // utils.rs:470,482
-        }
+        canon_kmer<KMODE, K>(r, c0, c1, c2, r0, r1, r2, kp, can_lo, can_hi);
         const uint32_t t = add_kmer<ALGO, XLOW, MASKED, FAST, Regs, true>(regs, can_lo, can_hi, vm, kp.bitflip, kp.p, kp.ull_sh28);
         zacc = zacc < t ? zacc : t;
         if constexpr (Regs::QUEUED) { if ((r & 3) == 3) regs.check(); }        // (LdsByteQRegs: is some lane's stack full?)
@@ -731,14 +742,7 @@ __device__ __forceinline__ uint32_t process_quarter(const Regs &regs, const KPar
         const int r = (int)rq + j;
         const uint32_t vm = (uint32_t)__builtin_amdgcn_sbfe((int)kvw, r, 1);    // 0 or ~0
         uint32_t can_lo, can_hi = 0;
-        if constexpr (KMODE == KM_GT16) {
-            canon_gt16<0>(r, c0, c1, c2, r0, r1, r2, kp, can_lo, can_hi);
-        } else {
-            uint32_t fwd = r ? alignbit(c0, c1, 32 - 2 * r) : c0;
-            uint32_t rc = r ? alignbit(r1, r0, 2 * r) : r0;
-            if constexpr (KMODE == KM_LT16) { fwd >>= kp.sh_lt; rc &= kp.mask_lt; }
-            can_lo = fwd < rc ? fwd : rc;
-        }
+        canon_kmer<KMODE, 0>(r, c0, c1, c2, r0, r1, r2, kp, can_lo, can_hi);
         const uint32_t t = add_kmer<ALGO, XLOW, true, FAST, Regs, true>(regs, can_lo, can_hi, vm, kp.bitflip, kp.p, kp.ull_sh28);
         zacc = zacc < t ? zacc : t;
     }

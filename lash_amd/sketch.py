@@ -248,6 +248,52 @@ class RecordIndex:
             pass
 
 
+class KmerFilter:
+    """lash_kmer_filter: per-file k-mer count tables (Context.kmer_filter) — count() adds files or chunks of them, counts() reads
+    a file's cells, Context.sketch_files_raw_filtered applies the keep rule."""
+
+    def __init__(self, ctx, handle, log2_cells):
+        self._ctx, self._h = ctx, handle
+        self.log2_cells = [int(x) for x in log2_cells]
+
+    def count(self, k, files_bytes):
+        """adds every valid k-mer occurrence of files_bytes (one entry per file of the filter; b"" adds nothing) to the tables"""
+        prm = Context._params("hmh", k, 0, 0, 0)
+        raw, off, fmt = _raw_files(files_bytes, empty_ok=True)
+        self._ctx._check_einval(self._ctx._lib.lash_kmer_filter_count_raw(self._ctx._h, C.byref(prm), raw.ctypes.data if raw.size else None,
+                                                                          off.ctypes.data, fmt.ctypes.data if fmt.size else None, len(files_bytes), self._h))
+
+    def counts(self, file):
+        out = np.zeros(1 << self.log2_cells[file], dtype=np.uint8)
+        self._ctx._check(self._ctx._lib.lash_kmer_filter_counts(self._ctx._h, self._h, int(file), out.ctypes.data))
+        return out
+
+    def free(self):
+        if self._h is not None and getattr(self._ctx, "_h", None):
+            self._ctx._lib.lash_kmer_filter_free(self._ctx._h, self._h)
+        self._h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+def _raw_files(files_bytes, empty_ok=False):
+    """file contents -> (raw bytes back to back, offsets, formats) as lash_sketch_files_raw takes them; empty_ok: b"" stands for a file
+    that has nothing in this call (a chunk of a batch streamed in pieces)"""
+    raw = np.frombuffer(b"".join(files_bytes), dtype=np.uint8) if files_bytes else np.zeros(0, np.uint8)
+    off = np.zeros(len(files_bytes) + 1, dtype=np.uint64)
+    if files_bytes:
+        off[1:] = np.cumsum([len(f) for f in files_bytes], dtype=np.uint64)
+    for f in files_bytes:                                   # parse_fastx_file(..).expect("Invalid input file"), utils.rs:453
+        if f[:1] not in (b">", b"@") and not (empty_ok and not f):
+            raise LashError(_lib.EINVAL, "Invalid input file: the first byte must be '>' (FASTA) or '@' (FASTQ)")
+    fmt = np.array([_lib.FMT_FASTQ if f[:1] == b"@" else _lib.FMT_FASTA for f in files_bytes], dtype=np.uint8)
+    return raw, off, fmt
+
+
 class Context:
     """One lash_ctx: a GPU, a stream and the HBM workspace.  Not thread-safe (like the C object)."""
 
@@ -347,19 +393,38 @@ class Context:
         Returns images[n_files, image_bytes]."""
         prm = self._params(algo, k, p, seed, flags)
         self._check(self._lib.lash_params_check(C.byref(prm)))
-        raw = np.frombuffer(b"".join(files_bytes), dtype=np.uint8) if files_bytes else np.zeros(0, np.uint8)
-        off = np.zeros(len(files_bytes) + 1, dtype=np.uint64)
-        if files_bytes:
-            off[1:] = np.cumsum([len(f) for f in files_bytes], dtype=np.uint64)
-        for f in files_bytes:                                   # parse_fastx_file(..).expect("Invalid input file"), utils.rs:453
-            if f[:1] not in (b">", b"@"):
-                raise LashError(_lib.EINVAL, "Invalid input file: the first byte must be '>' (FASTA) or '@' (FASTQ)")
-        fmt = np.array([_lib.FMT_FASTQ if f[:1] == b"@" else _lib.FMT_FASTA for f in files_bytes], dtype=np.uint8)
+        raw, off, fmt = _raw_files(files_bytes)
         ib = self.image_bytes(prm.algo, prm.p)
         out = np.zeros((len(files_bytes), ib), dtype=np.uint8)
         self._check(self._lib.lash_sketch_files_raw(self._h, C.byref(prm), raw.ctypes.data if raw.size else None,
                                                     off.ctypes.data, fmt.ctypes.data if fmt.size else None,
                                                     len(files_bytes), out.ctypes.data if out.size else None))
+        return out
+
+    def _check_einval(self, rc):
+        if rc == _lib.EINVAL:
+            raise LashError(rc, self._lib.lash_ctx_last_error(self._h).decode() or self._lib.lash_strerror(rc).decode())
+        self._check(rc)
+
+    def kmer_filter(self, log2_cells):
+        """lash_kmer_filter_create: one count table of 2^L cells per file (`lash sketch --min-count`)"""
+        l2 = np.ascontiguousarray(log2_cells, dtype=np.uint8)
+        h = C.c_void_p()
+        self._check(self._lib.lash_kmer_filter_create(self._h, len(l2), l2.ctypes.data if l2.size else None, C.byref(h)))
+        return KmerFilter(self, h, l2)
+
+    def sketch_files_raw_filtered(self, algo, k, p, seed, files_bytes, kmer_filter, min_count, flags=0, out=None):
+        """lash_sketch_files_raw_filtered: sketch_files_raw with the k-mers whose two cells in `kmer_filter` are not both >= min_count
+        left out.  out: images to union into (with F_ACCUMULATE).  Returns images[n_files, image_bytes]."""
+        prm = self._params(algo, k, p, seed, flags)
+        self._check(self._lib.lash_params_check(C.byref(prm)))
+        raw, off, fmt = _raw_files(files_bytes, empty_ok=True)
+        if out is None:
+            out = np.zeros((len(files_bytes), self.image_bytes(prm.algo, prm.p)), dtype=np.uint8)
+        assert out.dtype == np.uint8 and out.flags.c_contiguous
+        self._check_einval(self._lib.lash_sketch_files_raw_filtered(self._h, C.byref(prm), raw.ctypes.data if raw.size else None, off.ctypes.data,
+                                                                    fmt.ctypes.data if fmt.size else None, len(files_bytes), kmer_filter._h,
+                                                                    int(min_count), out.ctypes.data if out.size else None))
         return out
 
     def fasta_index(self, raw, file_off, device=False, keep=False):
