@@ -243,6 +243,38 @@ void     lash_rec_index_free(lash_ctx *ctx, lash_rec_index *index);
 int      lash_sketch_records_raw(lash_ctx *ctx, const lash_params *prm, const uint8_t *raw, const uint64_t *file_off, uint32_t n_files,
                                  const lash_rec_index *index, uint64_t r0, uint64_t r1, uint8_t *out_images);
 
+/* One sketch per fixed-length WINDOW of every FASTA record (`lash sketch --window W`): which stretch of a chromosome is the prophage, which
+ * part of a contig is the contaminant.  lash_fasta_windows cuts the records of an index (made from the same raw / file_off on the same
+ * context) into windows on the device (fasta_windows.hip):
+ *   sequence bytes  of a record: the bytes after its header line's '\n' up to start[r + 1] that are neither '\n' nor '\r'; every other
+ *                   byte counts (N, lower case, a stray '>').  Their 0-based rank in the record is the coordinate.
+ *   windows         a record of L sequence bytes has ceil(L / window) of them, window j = coordinates [j * window, min(L, (j + 1) * window));
+ *                   L = 0 gives none; the last, shorter one is kept.  No window spans two records.  Order: record order, then j.
+ *   record[w]       the record (of the index) window w lies in;  begin[w]  its first coordinate;  length[w]  its bases, 1 .. window
+ * Every window is written as a one-record FASTA file (">\n", its bytes, "\n") into one device buffer the window index owns until it is
+ * freed: lash_win_index_bytes bytes at lash_win_index_buffer_device, window w at offset[w] (n_windows + 1 entries), ready for
+ * lash_sketch_files_raw_device.  lash_sketch_windows_raw sketches windows [w0, w1) of it: one image per window, exactly what
+ * lash_sketch_files_raw gives for those files; the HyperLogLog `sum` replay and lash_ctx_format_errors / lash_ctx_hll_inexact_sums work as
+ * there, with indices relative to w0.  With an index made by lash_fasta_index from this same `raw` pointer the bytes are not sent again;
+ * _device: the bytes are in device memory.  Both synchronize the context's stream once (the totals size the result).  window = 0, an
+ * index of another context or buffer, w0 > w1, w1 > n_windows, LASH_F_AMINO: LASH_EINVAL; no room for the buffer: LASH_ENOMEM; 2^32
+ * windows or more: LASH_ELIMIT. */
+typedef struct lash_win_index lash_win_index;
+int      lash_fasta_windows(lash_ctx *ctx, const uint8_t *raw, const uint64_t *file_off, uint32_t n_files, const lash_rec_index *index,
+                            uint64_t window, lash_win_index **out);
+int      lash_fasta_windows_device(lash_ctx *ctx, const uint8_t *d_raw, const uint64_t *file_off, uint32_t n_files, const lash_rec_index *index,
+                                   uint64_t window, lash_win_index **out);
+uint64_t lash_win_index_n_windows(const lash_win_index *windows);
+uint64_t lash_win_index_bytes(const lash_win_index *windows);
+const uint8_t *lash_win_index_buffer_device(const lash_win_index *windows);
+int      lash_win_index_record(lash_ctx *ctx, const lash_win_index *windows, uint64_t *out);  /* n_windows */
+int      lash_win_index_begin(lash_ctx *ctx, const lash_win_index *windows, uint64_t *out);   /* n_windows */
+int      lash_win_index_length(lash_ctx *ctx, const lash_win_index *windows, uint64_t *out);  /* n_windows */
+int      lash_win_index_offset(lash_ctx *ctx, const lash_win_index *windows, uint64_t *out);  /* n_windows + 1 */
+int      lash_sketch_windows_raw(lash_ctx *ctx, const lash_params *prm, const lash_win_index *windows, uint64_t w0, uint64_t w1,
+                                 uint8_t *out_images);
+void     lash_win_index_free(lash_ctx *ctx, lash_win_index *windows);
+
 /* K-mer abundance filter (`lash sketch --min-count M`; Mash -m, not upstream): a k-mer a file holds fewer than M times stays out of its
  * sketch.  A sequencing error makes up to k k-mers that exist nowhere else, and in a read set they can outnumber the real ones.
  *   key      the masked canonical k-mer value the reference hands to add_kmer (utils.rs:464-499), as a u64 for all three sketch types

@@ -94,6 +94,17 @@ PROTOTYPES = {
     "lash_rec_index_file": (_int, [_vp, _vp, _vp]),
     "lash_rec_index_free": (None, [_vp, _vp]),
     "lash_sketch_records_raw": (_int, [_vp, _PP, _vp, _vp, _u32, _vp, _u64, _u64, _vp]),
+    "lash_fasta_windows": (_int, [_vp, _vp, _vp, _u32, _vp, _u64, C.POINTER(_vp)]),
+    "lash_fasta_windows_device": (_int, [_vp, _vp, _vp, _u32, _vp, _u64, C.POINTER(_vp)]),
+    "lash_win_index_n_windows": (_u64, [_vp]),
+    "lash_win_index_bytes": (_u64, [_vp]),
+    "lash_win_index_buffer_device": (_vp, [_vp]),
+    "lash_win_index_record": (_int, [_vp, _vp, _vp]),
+    "lash_win_index_begin": (_int, [_vp, _vp, _vp]),
+    "lash_win_index_length": (_int, [_vp, _vp, _vp]),
+    "lash_win_index_offset": (_int, [_vp, _vp, _vp]),
+    "lash_sketch_windows_raw": (_int, [_vp, _PP, _vp, _u64, _u64, _vp]),
+    "lash_win_index_free": (None, [_vp, _vp]),
     "lash_hll_replay_sums_device": (_int, [_vp, _PP, _vp, _vp, _u64, _vp, _u32, _vp]),
     "lash_hll_replay_streamed_chunk": (_int, [_vp, _PP, _vp, _u64, _int, _vp, _vp, _vp, _vp]),
     "lash_ctx_hll_inexact_sums": (_u32, [_vp, _vp, _u32]),

@@ -5,7 +5,7 @@
 //   lash hll-bias -o FILE [-p P[,P...]] [--points N] [--trials T] [--seed S] [--device D]    (not upstream: HLL++ bias tables, simulated)
 // Extras that do not exist upstream: --gpus N / --device D / --devices LIST (which GPUs to use, one worker each), --batch-mb M, --stream-mb M (files
 // larger than M MiB are streamed in chunks with on-device accumulation), --hmh-x-low, --min-count M [--count-cells-log2 L] (drop the k-mers a
-// file holds fewer than M times, counted on the GPU), --per-record (one sketch per FASTA record, the records
+// file holds fewer than M times, counted on the GPU), --window (one sketch per W-base window of every record), --per-record (one sketch per FASTA record, the records
 // found on the GPU); dist: --device D, --block-rows N, --hll-bias FILE / --hll-bias-sim (HLL++ bias tables from a file / simulated on the GPU),
 // --file-order (rows / columns in list-file order instead of the reference's seeded hash-map order), --max-dist D (print only
 // the pairs with distance <= D), --top K (only each name's K nearest), --cluster D (single-linkage clusters of an all-vs-all instead
@@ -56,6 +56,10 @@ void usage()
             "      --aa                     Amino acid sketching (k 1-12); the reference carries this flag commented out\n"
             "      --per-record             One sketch per FASTA record instead of one per file (multi-FASTA collections; like Mash -i);\n"
             "                               {output}_files.json then holds the record ids.  FASTA only, not with --aa\n"
+            "      --window <W>             One sketch per W-base window of every FASTA record (W >= k; the windows are cut on the GPU, do not\n"
+            "                               overlap and never span two records; a record's last, shorter window is kept).  {output}_files.json\n"
+            "                               then holds ID:B-E, the record id and the 1-based inclusive range.  FASTA only, not with --aa or\n"
+            "                               --min-count; --per-record changes nothing\n"
             "      --min-count <M>          Keep only the k-mers a file holds at least M times (1-255; read sets: a sequencing error makes\n"
             "                               k-mers seen once; like Mash -m).  Counted per file on the GPU in 2^L saturating cells, two cells\n"
             "                               per k-mer; a rarer k-mer gets in only when collisions fill both.  Files are read twice.  hmh,\n"
@@ -164,6 +168,17 @@ int cmd_sketch(int argc, char **argv)
     if (k < 1 || k > 32) { fprintf(stderr, "k-mer length must be 1-32\n"); return 101; }       // utils.rs:501 panic
     const bool amino = a.flags.count("aa") != 0;                                               // main.rs:97-104 (commented out there)
     opt.per_record = a.flags.count("per-record") != 0;
+    if (a.kv.count("window")) {
+        uint64_t w = 0;
+        if (!to_u64(a.kv["window"], w) || w < 1) {
+            fprintf(stderr, "error: invalid value '%s' for --window: a positive integer is required\n", a.kv["window"].c_str());
+            return 2;
+        }
+        if (amino) { fprintf(stderr, "error: --window cannot be used with --aa (windows are cut for nucleotide FASTA only)\n"); return 2; }
+        if (w < k) { fprintf(stderr, "error: --window %llu is shorter than -k %llu: no window would hold a k-mer\n", (unsigned long long)w, (unsigned long long)k); return 2; }
+        if (a.kv.count("min-count")) { fprintf(stderr, "error: --window cannot be used with --min-count (k-mers are counted per file)\n"); return 2; }
+        opt.window = w;
+    }
     if (opt.per_record && amino) { fprintf(stderr, "error: --per-record cannot be used with --aa (records are split for nucleotide FASTA only)\n"); return 2; }
     if (amino && k > 12) { fprintf(stderr, "k-mer length for amino acid must be 1\xe2\x80\x93" "12\n"); return 101; }   // utils.rs:554 panic
     if (a.kv.count("count-cells-log2") && !a.kv.count("min-count")) { fprintf(stderr, "error: --count-cells-log2 needs --min-count\n"); return 2; }
@@ -217,10 +232,15 @@ int cmd_sketch(int argc, char **argv)
     if (!err.empty()) { fprintf(stderr, "Error: %s\n", err.c_str()); return 1; }
     SketchStats st;
     err = sketch_files(opt, files, output, &st);
+    if (opt.window && err.rfind("--window takes FASTA input", 0) == 0) { fprintf(stderr, "error: %s\n", err.c_str()); return 2; }   // a refusal of the flag
     if (!err.empty()) { fprintf(stderr, "Error: %s\n", err.c_str()); return 1; }
     err = write_parameters_json(output, alg, opt.k, opt.precision, opt.seed, amino);
     if (!err.empty()) { fprintf(stderr, "Error: %s\n", err.c_str()); return 1; }
-    if (opt.per_record)
+    if (opt.window)
+        fprintf(stderr, "sketched %llu windows of %llu files (%.3f GB of FASTA text) in %.2f s on %zu GPU(s), %llu batches\n",
+                (unsigned long long)st.records, (unsigned long long)st.files, st.bytes / 1e9, st.seconds, opt.devices.size(),
+                (unsigned long long)st.batches);
+    else if (opt.per_record)
         fprintf(stderr, "sketched %llu records of %llu files (%.3f GB of FASTA text) in %.2f s on %zu GPU(s), %llu batches\n",
                 (unsigned long long)st.records, (unsigned long long)st.files, st.bytes / 1e9, st.seconds, opt.devices.size(),
                 (unsigned long long)st.batches);

@@ -513,6 +513,9 @@ std::string sketch_files(const SketchOptions &opt, const std::vector<std::string
                          SketchStats *stats)
 {
     const auto t_start = std::chrono::steady_clock::now();
+    // --window splits at records as --per-record does, then cuts every record into windows: the same batches, parts and hand-off
+    const bool by_record = opt.per_record || opt.window != 0;
+    const std::string split_flag = opt.window ? "--window" : "--per-record";
     // LASH_CLI_TIMING=1: pipeline marks on stderr (seconds since sketch_files() started)
     const bool timing = getenv("LASH_CLI_TIMING") != nullptr;
     std::mutex tmu;
@@ -560,6 +563,49 @@ std::string sketch_files(const SketchOptions &opt, const std::vector<std::string
         std::vector<uint32_t> id_len(n);
         if ((rc = lash_rec_index_start(ctx, ix, start.data())) == LASH_OK) rc = lash_rec_index_id_len(ctx, ix, id_len.data());
         std::string e;
+        if (rc == LASH_OK && opt.window) {
+            // --window: the records cut into windows on the device (lash_fasta_windows), named ID:B-E (1-based, inclusive), and sketched in
+            // sub-calls bounded as the records' are
+            lash_win_index *wi = nullptr;
+            rc = lash_fasta_windows(ctx, b.buf->p, b.file_off.data(), nf, ix, opt.window, &wi);
+            const uint64_t nw = rc == LASH_OK ? lash_win_index_n_windows(wi) : 0;
+            std::vector<uint64_t> wrec(nw), wbeg(nw), wlen(nw);
+            if (rc == LASH_OK) rc = lash_win_index_record(ctx, wi, wrec.data());
+            if (rc == LASH_OK) rc = lash_win_index_begin(ctx, wi, wbeg.data());
+            if (rc == LASH_OK) rc = lash_win_index_length(ctx, wi, wlen.data());
+            if (rc == LASH_OK) {
+                b.names.reserve(nw);
+                for (uint64_t w = 0; w < nw; ++w)
+                    b.names.push_back(std::string(reinterpret_cast<const char *>(b.buf->p) + start[wrec[w]] + 1, id_len[wrec[w]]) + ":" +
+                                      std::to_string(wbeg[w] + 1) + "-" + std::to_string(wbeg[w] + wlen[w]));
+                const uint64_t step = std::max<uint64_t>(1, kRecordImageCap / std::max<size_t>(ib, 1));
+                for (uint64_t w0 = 0; w0 < nw && rc == LASH_OK; w0 += step) {
+                    const uint64_t w1 = std::min(nw, w0 + step);
+                    std::vector<uint8_t> part((size_t)(w1 - w0) * ib, 0);
+                    rc = lash_sketch_windows_raw(ctx, &prm, wi, w0, w1, part.data());
+                    if (rc != LASH_OK) break;
+                    if (prm.algo == LASH_HLL) {
+                        std::vector<uint32_t> idx((size_t)(w1 - w0));
+                        const uint32_t nc = lash_ctx_hll_inexact_sums(ctx, idx.data(), (uint32_t)idx.size());
+                        for (uint32_t i = 0; i < nc && i < idx.size(); ++i)
+                            fprintf(stderr, "note: window '%s' of %s: a HyperLogLog register exceeds 53 - p; the header's sum field is the exact sum and may "
+                                            "differ from lash's incrementally rounded value in its last bits\n", b.names[w0 + idx[i]].c_str(), files[b.f0].c_str());
+                    }
+                    std::unique_lock<std::mutex> lk(qmu);
+                    cv_done.wait(lk, [&] {
+                        return b.parts_bytes < kRecordImageCap ||
+                               (writer_want != b.index && !live.count(writer_want) && !finished.count(writer_want));
+                    });
+                    b.parts_bytes += part.size();
+                    b.parts.push_back(std::move(part));
+                    cv_done.notify_all();
+                }
+            }
+            if (rc != LASH_OK) e = std::string(lash_strerror(rc)) + " " + lash_ctx_last_error(ctx);
+            lash_win_index_free(ctx, wi);
+            lash_rec_index_free(ctx, ix);
+            return e;
+        }
         if (rc == LASH_OK) {
             b.names.reserve(n);
             for (uint64_t r = 0; r < n; ++r) b.names.emplace_back(reinterpret_cast<const char *>(b.buf->p) + start[r] + 1, id_len[r]);
@@ -623,11 +669,11 @@ std::string sketch_files(const SketchOptions &opt, const std::vector<std::string
                 if (todo.empty()) break;
                 b = todo.front();
                 todo.pop_front();
-                if (opt.per_record) { live[b->index] = b; cv_done.notify_all(); }
+                if (by_record) { live[b->index] = b; cv_done.notify_all(); }
             }
             if (b->err.empty()) {
                 if (rc != LASH_OK) b->err = lash_strerror(rc);
-                else if (opt.per_record) {
+                else if (by_record) {
                     const auto g0 = std::chrono::steady_clock::now();
                     b->err = sketch_records(ctx, *b);
                     mark("GPU done, batch", b->index, std::chrono::duration<double>(std::chrono::steady_clock::now() - g0).count());
@@ -703,7 +749,7 @@ std::string sketch_files(const SketchOptions &opt, const std::vector<std::string
             }
             if (werr.empty() && !b->err.empty()) werr = b->err;
             if (werr.empty() && !b->images.empty()) werr = zw.write(b->images.data(), b->images.size());
-            if (opt.per_record) { n_records += b->names.size(); record_names.insert(record_names.end(), b->names.begin(), b->names.end()); }
+            if (by_record) { n_records += b->names.size(); record_names.insert(record_names.end(), b->names.begin(), b->names.end()); }
         }
         if (werr.empty()) werr = zw.finish();
     });
@@ -812,7 +858,7 @@ std::string sketch_files(const SketchOptions &opt, const std::vector<std::string
                         if (e.empty()) {
                             const int f = sniff_format(dst, s.size);
                             if (!f) e = "Invalid input file: neither FASTA ('>') nor FASTQ ('@'): " + files[i];
-                            else if (opt.per_record && f != LASH_FMT_FASTA) e = "--per-record takes FASTA input; this file starts with '@' (FASTQ): " + files[i];
+                            else if (by_record && f != LASH_FMT_FASTA) e = split_flag + " takes FASTA input; this file starts with '@' (FASTQ): " + files[i];
                             b->fmt[i - b->f0] = (uint8_t)(f ? f : LASH_FMT_FASTA);
                             // (malformed FASTQ records: found on the device, the file is then re-done by the library with
                             // needletail's rule — utils.rs:457 — or, under layout fastq_err=skip, without the bad records)
@@ -840,7 +886,7 @@ std::string sketch_files(const SketchOptions &opt, const std::vector<std::string
                     pump_inflates();
                 }
             }
-            if (slots[i].big && opt.per_record) {
+            if (slots[i].big && by_record) {
                 // a large multi-FASTA goes to the GPU workers as a sequence of batches, each a chunk of at most --stream-mb that ends
                 // before the last record start in it; a record is never split
                 finalize();
@@ -879,7 +925,7 @@ std::string sketch_files(const SketchOptions &opt, const std::vector<std::string
                         }
                         if (e.empty() && first) {
                             if (have == 0) e = "Invalid input file: empty (" + files[i] + ")";
-                            else if (p[0] == '@') e = "--per-record takes FASTA input; this file starts with '@' (FASTQ): " + files[i];
+                            else if (p[0] == '@') e = split_flag + " takes FASTA input; this file starts with '@' (FASTQ): " + files[i];
                             else if (p[0] != '>') e = "Invalid input file: neither FASTA ('>') nor FASTQ ('@'): " + files[i];
                         }
                         if (e.empty()) {
@@ -890,7 +936,7 @@ std::string sketch_files(const SketchOptions &opt, const std::vector<std::string
                                 size_t id_end = 1;
                                 while (id_end < have && id_end < 200 && p[id_end] != ' ' && p[id_end] != '\t' && p[id_end] != '\r' && p[id_end] != '\n') ++id_end;
                                 e = "record '" + std::string(reinterpret_cast<const char *>(p) + 1, id_end - 1) + "' of " + files[i] + " does not fit in a chunk of " +
-                                    std::to_string(stream_bytes >> 20) + " MiB: --per-record never splits a record, raise --stream-mb";
+                                    std::to_string(stream_bytes >> 20) + " MiB: " + split_flag + " never splits a record, raise --stream-mb";
                             }
                         }
                         if (e.empty()) tail.assign(p + cut, p + have);
@@ -961,7 +1007,7 @@ std::string sketch_files(const SketchOptions &opt, const std::vector<std::string
     mark("writer done", 0);
     if (err.empty()) err = werr;
     if (!err.empty()) {
-        if (opt.per_record) (void)remove((output_name + "_sketches.bin").c_str());   // a refused --per-record run leaves no output
+        if (by_record) (void)remove((output_name + "_sketches.bin").c_str());   // a refused --per-record run leaves no output
         return err;
     }
 
@@ -969,7 +1015,7 @@ std::string sketch_files(const SketchOptions &opt, const std::vector<std::string
     {
         std::ofstream out(output_name + "_files.json", std::ios::binary);
         if (!out) return "cannot create " + output_name + "_files.json";
-        out << json_pretty_string_array(opt.per_record ? record_names : files);
+        out << json_pretty_string_array(by_record ? record_names : files);
         if (!out.good()) return "write failed";
     }
     if (opt.min_count && l2_hi)

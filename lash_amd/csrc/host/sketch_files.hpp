@@ -28,6 +28,7 @@ struct SketchOptions {
                                          // of this size with on-device accumulation (BASELINE configs[4]); < 4 GiB
     uint32_t flags = 0;              // LASH_F_HMH_X_LOW, LASH_F_AMINO (--aa)
     bool per_record = false;         // --per-record: one sketch per FASTA record instead of one per file (records found on the GPU)
+    uint64_t window = 0;             // --window W: one sketch per W-base window of every FASTA record (cut on the GPU); 0: off
     uint32_t min_count = 0;          // --min-count M: 0 = off, else only the k-mers a file holds at least M times reach its sketch (lash_kmer_filter_*)
     int count_cells_log2 = 0;        // --count-cells-log2 L: cells of a file's count table; 0 = ceil(log2(8 x file bytes)) within 16..36
     lash_layout layout;              // set by layout_from_option(); every context gets it

@@ -251,7 +251,7 @@ void lash_ctx_destroy(lash_ctx *ctx)
     release(ctx->sole_state);
     for (DevBuf *b : {&ctx->items, &ctx->item_begin, &ctx->item_kmers, &ctx->partials, &ctx->gregs, &ctx->counter, &ctx->st_seq, &ctx->st_rec,
                       &ctx->st_img, &ctx->hll_flags, &ctx->ec_ref, &ctx->ec_qry, &ctx->ec_x, &ctx->ec_card, &ctx->wf_scratch, &ctx->wf_out, &ctx->top_buf, &ctx->hll_bm_ref,
-                      &ctx->hll_bm_qry, &ctx->hll_lohi, &ctx->fa_off, &ctx->fa_scratch, &ctx->kf_keep})
+                      &ctx->hll_bm_qry, &ctx->hll_lohi, &ctx->fa_off, &ctx->fa_scratch, &ctx->fw_scratch, &ctx->kf_keep})
         release(*b);
     {
         lash_packed &sc = ctx->scratch;
@@ -680,7 +680,8 @@ int lash_sketch_files_raw(lash_ctx *ctx, const lash_params *prm, const uint8_t *
 }  // extern "C"
 
 // lash_sketch_files_raw; d_raw != NULL: the bytes of `raw` are already in device memory there (lash_sketch_records_raw: the record index
-// keeps the copy it was made from), so nothing is staged and file_off may start anywhere in the buffer
+// keeps the copy it was made from), so nothing is staged and file_off may start anywhere in the buffer.  raw == NULL with d_raw: the bytes
+// exist on the device only (lash_sketch_windows_raw: the rewritten windows); the rare file that is redone on the host is fetched from there
 int lashi::files_raw_staged(lash_ctx *ctx, const lash_params *prm, const uint8_t *raw, const uint8_t *d_raw, const uint64_t *file_off,
                             const uint8_t *file_fmt, uint32_t n_files, uint8_t *out_images)
 {
@@ -689,7 +690,7 @@ int lashi::files_raw_staged(lash_ctx *ctx, const lash_params *prm, const uint8_t
     if (rc) return rc;
     (void)hipSetDevice(ctx->device);
     const uint64_t bytes = file_off[n_files];
-    if (bytes && !raw) return LASH_EINVAL;
+    if (bytes && !raw && (!d_raw || (prm->flags & LASH_F_AMINO))) return LASH_EINVAL;
     if (prm->flags & LASH_F_AMINO) {
         // protein FASTA / FASTQ: parsed here on the host with needletail's record rules, sketched by the record entry
         std::vector<uint8_t> seq;
@@ -747,7 +748,13 @@ int lashi::files_raw_staged(lash_ctx *ctx, const lash_params *prm, const uint8_t
     for (uint32_t g : bad) {                                       // exact reference semantics for the malformed ones
         std::vector<uint8_t> seq;
         std::vector<uint64_t> rec_off(1, 0);
-        parse_fastx_strict(raw + file_off[g], (size_t)(file_off[g + 1] - file_off[g]), &seq, &rec_off, ctx->layout.fastq_skip_bad != 0);
+        const size_t fb = (size_t)(file_off[g + 1] - file_off[g]);
+        std::vector<uint8_t> fetched;
+        if (!raw && fb) {
+            fetched.resize(fb);
+            HIPCHK(ctx, hipMemcpy(fetched.data(), d_raw + file_off[g], fb, hipMemcpyDeviceToHost));
+        }
+        parse_fastx_strict(raw ? raw + file_off[g] : fetched.data(), fb, &seq, &rec_off, ctx->layout.fastq_skip_bad != 0);
         const uint64_t goff[2] = {0, (uint64_t)rec_off.size() - 1};
         const uint8_t dummy = 0;
         rc = lash_sketch_batch(ctx, prm, seq.empty() ? &dummy : seq.data(), rec_off.data(), rec_off.size() - 1, goff, 1, out_images + (size_t)g * ib);

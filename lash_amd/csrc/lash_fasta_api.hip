@@ -1,6 +1,8 @@
 // lash_fasta_api.hip — the per-record entries of liblash_gfx950.so (include/lash_gfx950.h): lash_fasta_index[_device] and its accessors, the
 // device-side record index of raw multi-FASTA bytes (fasta_index.hip), and lash_sketch_records_raw, which hands a range of that index
-// to the raw-file route with records where it has files (`lash sketch --per-record`).
+// to the raw-file route with records where it has files (`lash sketch --per-record`); lash_fasta_windows[_device], which rewrites the records
+// of an index as fixed-length windows (fasta_windows.hip), and lash_sketch_windows_raw, which hands a range of those to the same route
+// (`lash sketch --window`).
 #include "lash_ctx.h"
 #include "lash_internal.h"
 
@@ -12,6 +14,14 @@ struct lash_rec_index {
     DevBuf raw;                                  // lash_fasta_index (host bytes): the device copy the index was made from, kept so that
     const uint8_t *h_raw = nullptr;              // lash_sketch_records_raw on the same host buffer does not send the bytes again
     mutable std::vector<uint64_t> h_start;       // host copy of start[], fetched by the first lash_sketch_records_raw
+};
+
+struct lash_win_index {
+    int device = 0;
+    uint64_t n = 0, window = 0, bytes = 0;       // windows; their length; size of buf == off[n]
+    DevBuf record, begin, length, off;           // [n] u64 each, off [n + 1]: where every window's one-record FASTA file starts in buf
+    DevBuf buf;                                  // the windows, each as ">\n" + its bases + "\n"
+    mutable std::vector<uint64_t> h_off;         // host copy of off[], fetched by the first lash_sketch_windows_raw
 };
 
 extern "C" {
@@ -128,6 +138,114 @@ int lash_sketch_records_raw(lash_ctx *ctx, const lash_params *prm, const uint8_t
     std::vector<uint64_t> off((size_t)n + 1);
     for (uint32_t i = 0; i <= n; ++i) off[i] = ix->h_start[r0 + i] - ix->h_start[r0];
     return lash_sketch_files_raw(ctx, prm, raw + ix->h_start[r0], off.data(), fmt.data(), n, out_images);
+}
+
+void lash_win_index_free(lash_ctx *ctx, lash_win_index *wi)
+{
+    if (!wi) return;
+    if (ctx) {
+        (void)hipSetDevice(ctx->device);
+        if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
+    }
+    for (DevBuf *b : {&wi->record, &wi->begin, &wi->length, &wi->off, &wi->buf}) release(*b);
+    delete wi;
+}
+
+int lash_fasta_windows_device(lash_ctx *ctx, const uint8_t *d_raw, const uint64_t *file_off, uint32_t n_files, const lash_rec_index *ix,
+                              uint64_t window, lash_win_index **out)
+{
+    if (!ctx || !out || !file_off || !ix || window == 0) return LASH_EINVAL;
+    *out = nullptr;
+    if (ix->device != ctx->device || n_files != ix->n_files || file_off[n_files] != ix->total) return LASH_EINVAL;   // another context or buffer
+    if (ix->total && !d_raw) return LASH_EINVAL;
+    (void)hipSetDevice(ctx->device);
+    const uint32_t tb = fasta_index_tile_bytes(), n_tiles = (uint32_t)((ix->total + tb - 1) / tb);
+    int rc;
+    if ((rc = reserve(ctx, ctx->fw_scratch, fasta_windows_scratch_bytes(n_tiles, ix->n)))) return rc;
+    uint8_t *scratch = static_cast<uint8_t *>(ctx->fw_scratch.ptr);
+    const uint64_t *d_start = static_cast<const uint64_t *>(ix->start.ptr), *d_s = nullptr, *d_n = nullptr;
+    HIPCHK(ctx, launch_fasta_windows_count(d_raw, ix->total, d_start, ix->n, n_tiles, window, scratch, &d_s, &d_n, ctx->stream));
+    uint64_t seq_bytes = 0, n_win = 0;
+    HIPCHK(ctx, hipMemcpyAsync(&seq_bytes, d_s, 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(&n_win, d_n, 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    if (n_win > 0xFFFFFFFFull) return LASH_ELIMIT;                 // window numbers are the raw-file route's file numbers: 32 bits
+    lash_win_index *wi = new (std::nothrow) lash_win_index();
+    if (!wi) return LASH_ENOMEM;
+    wi->device = ctx->device;
+    wi->n = n_win;
+    wi->window = window;
+    wi->bytes = seq_bytes + 3 * n_win;
+    auto room = [&](DevBuf &b, size_t bytes) -> int {
+        HIPCHK(ctx, hipMalloc(&b.ptr, bytes));
+        b.cap = bytes;
+        return LASH_OK;
+    };
+    const size_t tab = ((size_t)n_win + 1) * 8;
+    if ((rc = room(wi->record, tab)) || (rc = room(wi->begin, tab)) || (rc = room(wi->length, tab)) || (rc = room(wi->off, tab)) ||
+        (rc = room(wi->buf, (size_t)wi->bytes + 64))) {
+        lash_win_index_free(ctx, wi);
+        return rc;
+    }
+    const hipError_t e = launch_fasta_windows_write(d_raw, ix->total, d_start, ix->n, n_tiles, window, scratch, n_win,
+                                                    static_cast<uint64_t *>(wi->record.ptr), static_cast<uint64_t *>(wi->begin.ptr),
+                                                    static_cast<uint64_t *>(wi->length.ptr), static_cast<uint64_t *>(wi->off.ptr),
+                                                    static_cast<uint8_t *>(wi->buf.ptr), ctx->stream);
+    if (e != hipSuccess) { lash_win_index_free(ctx, wi); return fail(ctx, LASH_EHIP, "launch_fasta_windows_write", e); }
+    *out = wi;
+    return LASH_OK;
+}
+
+int lash_fasta_windows(lash_ctx *ctx, const uint8_t *raw, const uint64_t *file_off, uint32_t n_files, const lash_rec_index *ix,
+                       uint64_t window, lash_win_index **out)
+{
+    if (!ctx || !out || !file_off || !ix || window == 0) return LASH_EINVAL;
+    *out = nullptr;
+    if (ix->device != ctx->device || n_files != ix->n_files || file_off[n_files] != ix->total) return LASH_EINVAL;
+    if (ix->total && !raw) return LASH_EINVAL;
+    if (ix->raw.ptr && ix->h_raw == raw)                           // the index holds these bytes on the device
+        return lash_fasta_windows_device(ctx, static_cast<const uint8_t *>(ix->raw.ptr), file_off, n_files, ix, window, out);
+    (void)hipSetDevice(ctx->device);
+    int rc;
+    if ((rc = reserve(ctx, ctx->st_seq, ix->total + 64))) return rc;
+    if (ix->total) HIPCHK(ctx, hipMemcpyAsync(ctx->st_seq.ptr, raw, ix->total, hipMemcpyHostToDevice, ctx->stream));
+    rc = lash_fasta_windows_device(ctx, static_cast<const uint8_t *>(ctx->st_seq.ptr), file_off, n_files, ix, window, out);
+    if (rc == LASH_OK) HIPCHK(ctx, hipStreamSynchronize(ctx->stream));       // the staging buffer is the context's: done with it before anyone reuses it
+    return rc;
+}
+
+uint64_t lash_win_index_n_windows(const lash_win_index *wi) { return wi ? wi->n : 0; }
+uint64_t lash_win_index_bytes(const lash_win_index *wi) { return wi ? wi->bytes : 0; }
+const uint8_t *lash_win_index_buffer_device(const lash_win_index *wi) { return wi ? static_cast<const uint8_t *>(wi->buf.ptr) : nullptr; }
+
+static int win_copy(lash_ctx *ctx, const lash_win_index *wi, const DevBuf &b, void *dst, size_t bytes)
+{
+    if (!ctx || !wi || (bytes && !dst) || ctx->device != wi->device) return LASH_EINVAL;
+    (void)hipSetDevice(ctx->device);
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    if (bytes) HIPCHK(ctx, hipMemcpy(dst, b.ptr, bytes, hipMemcpyDeviceToHost));
+    return LASH_OK;
+}
+
+int lash_win_index_record(lash_ctx *ctx, const lash_win_index *wi, uint64_t *out) { return win_copy(ctx, wi, wi ? wi->record : DevBuf{}, out, wi ? (size_t)wi->n * 8 : 0); }
+int lash_win_index_begin(lash_ctx *ctx, const lash_win_index *wi, uint64_t *out) { return win_copy(ctx, wi, wi ? wi->begin : DevBuf{}, out, wi ? (size_t)wi->n * 8 : 0); }
+int lash_win_index_length(lash_ctx *ctx, const lash_win_index *wi, uint64_t *out) { return win_copy(ctx, wi, wi ? wi->length : DevBuf{}, out, wi ? (size_t)wi->n * 8 : 0); }
+int lash_win_index_offset(lash_ctx *ctx, const lash_win_index *wi, uint64_t *out) { return win_copy(ctx, wi, wi ? wi->off : DevBuf{}, out, wi ? ((size_t)wi->n + 1) * 8 : 0); }
+
+int lash_sketch_windows_raw(lash_ctx *ctx, const lash_params *prm, const lash_win_index *wi, uint64_t w0, uint64_t w1, uint8_t *out_images)
+{
+    if (!ctx || !wi || w0 > w1 || w1 > wi->n || (w1 > w0 && !out_images) || wi->device != ctx->device) return LASH_EINVAL;
+    int rc = lash_params_check(prm);
+    if (rc) return rc;
+    if (prm->flags & LASH_F_AMINO) return LASH_EINVAL;
+    if (wi->h_off.empty()) {
+        wi->h_off.resize((size_t)wi->n + 1);
+        if ((rc = lash_win_index_offset(ctx, wi, wi->h_off.data()))) { wi->h_off.clear(); return rc; }
+    }
+    // windows [w0, w1) as the files of one raw call: each is a well-formed one-record FASTA file, and they lie back to back in buf
+    const uint32_t n = (uint32_t)(w1 - w0);
+    const std::vector<uint8_t> fmt(n, (uint8_t)LASH_FMT_FASTA);
+    return files_raw_staged(ctx, prm, nullptr, static_cast<const uint8_t *>(wi->buf.ptr), wi->h_off.data() + w0, fmt.data(), n, out_images);
 }
 
 }  // extern "C"

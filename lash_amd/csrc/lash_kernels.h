@@ -250,6 +250,17 @@ hipError_t launch_fasta_mark(const uint8_t *d_raw, uint64_t total, const uint64_
                              uint8_t *d_scratch, const uint32_t **d_n_records_and_bad, hipStream_t stream);
 hipError_t launch_fasta_write(const uint8_t *d_raw, uint64_t total, const uint64_t *d_file_off, uint32_t n_files, uint32_t n_tiles,
                               uint8_t *d_scratch, uint32_t n_records, uint64_t *d_start, uint32_t *d_file, uint32_t *d_id_len, hipStream_t stream);
+// fasta_windows.hip: fixed-length windows of the records of such an index, rewritten as one-record FASTA files (lash_fasta_windows).
+// launch_fasta_windows_count queues the passes up to the two totals (sequence bytes S, windows n: one u64 each, device); once the caller has
+// read them and made room (d_out: S + 3n bytes; d_record / d_begin / d_length: n u64; d_off: n + 1 u64), launch_fasta_windows_write queues
+// the window table and the scatter.  d_start: the index's start[n_records + 1]; d_scratch: fasta_windows_scratch_bytes(n_tiles, n_records).
+size_t fasta_windows_scratch_bytes(uint32_t n_tiles, uint32_t n_records);
+hipError_t launch_fasta_windows_count(const uint8_t *d_raw, uint64_t total, const uint64_t *d_start, uint32_t n_records, uint32_t n_tiles,
+                                      uint64_t window, uint8_t *d_scratch, const uint64_t **d_seq_bytes, const uint64_t **d_n_windows,
+                                      hipStream_t stream);
+hipError_t launch_fasta_windows_write(const uint8_t *d_raw, uint64_t total, const uint64_t *d_start, uint32_t n_records, uint32_t n_tiles,
+                                      uint64_t window, uint8_t *d_scratch, uint64_t n_windows, uint64_t *d_record, uint64_t *d_begin,
+                                      uint64_t *d_length, uint64_t *d_off, uint8_t *d_out, hipStream_t stream);
 
 struct FinalizeArgs {
     const uint8_t  *partials;

@@ -220,6 +220,44 @@ class Packed:
             pass
 
 
+class WindowIndex:
+    """Device-resident windows of the records of a RecordIndex, rewritten as one-record FASTA files (lash_win_index*)."""
+
+    def __init__(self, ctx, handle):
+        self._ctx, self._h = ctx, handle
+        self.n_windows = int(_lib.load().lash_win_index_n_windows(handle))
+        self.nbytes = int(_lib.load().lash_win_index_bytes(handle))
+
+    def arrays(self):
+        """(record[n], begin[n], length[n]) u64, each one copy to the host"""
+        lib, n = _lib.load(), self.n_windows
+        out = [np.zeros(n, np.uint64) for _ in range(3)]
+        for fn, a in zip((lib.lash_win_index_record, lib.lash_win_index_begin, lib.lash_win_index_length), out):
+            self._ctx._check(fn(self._ctx._h, self._h, a.ctypes.data))
+        return tuple(out)
+
+    def offsets(self):
+        """offset[n + 1] u64: where every window's file starts in the device buffer"""
+        off = np.zeros(self.n_windows + 1, np.uint64)
+        self._ctx._check(_lib.load().lash_win_index_offset(self._ctx._h, self._h, off.ctypes.data))
+        return off
+
+    @property
+    def device_ptr(self):
+        return _lib.load().lash_win_index_buffer_device(self._h) or 0
+
+    def free(self):
+        if self._h:
+            _lib.load().lash_win_index_free(self._ctx._h, self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
 class RecordIndex:
     """Device-resident record index of raw multi-FASTA bytes (lash_rec_index*)."""
 
@@ -448,6 +486,36 @@ class Context:
             return ix.arrays()
         finally:
             ix.free()
+
+    def fasta_windows(self, raw, file_off, index, window, device=False, keep=False):
+        """lash_fasta_windows: the records of `index` (a RecordIndex made from the same raw / file_off) cut into windows of `window` bases
+        on the GPU.  raw as for fasta_index.  Returns (record[n], begin[n], length[n]) u64; keep=True returns a WindowIndex (for
+        sketch_windows) instead."""
+        off = np.ascontiguousarray(file_off, dtype=np.uint64)
+        if not device:
+            raw = np.frombuffer(raw, dtype=np.uint8) if isinstance(raw, (bytes, bytearray)) else np.ascontiguousarray(raw, dtype=np.uint8)
+            assert raw.size >= int(off[-1])
+        h = C.c_void_p()
+        fn = self._lib.lash_fasta_windows_device if device else self._lib.lash_fasta_windows
+        self._check_einval(fn(self._h, _ptr(raw) if int(off[-1]) else None, off.ctypes.data, len(off) - 1, index._h, int(window), C.byref(h)))
+        wi = WindowIndex(self, h)
+        if keep:
+            return wi
+        try:
+            return wi.arrays()
+        finally:
+            wi.free()
+
+    def sketch_windows(self, algo, k, p, seed, windows, w0=0, w1=None, flags=0):
+        """lash_sketch_windows_raw: one image per window, windows [w0, w1) of a WindowIndex.  Returns images[w1 - w0, image_bytes]."""
+        prm = self._params(algo, k, p, seed, flags)
+        self._check(self._lib.lash_params_check(C.byref(prm)))
+        if w1 is None:
+            w1 = windows.n_windows
+        out = np.zeros((max(int(w1) - int(w0), 0), self.image_bytes(prm.algo, prm.p)), dtype=np.uint8)
+        self._check_einval(self._lib.lash_sketch_windows_raw(self._h, C.byref(prm), windows._h, int(w0), int(w1),
+                                                             out.ctypes.data if out.size else None))
+        return out
 
     def sketch_records_raw(self, algo, k, p, seed, raw, file_off, index=None, r0=0, r1=None, flags=0):
         """lash_sketch_records_raw: one image per FASTA record of raw (host bytes), records [r0, r1) of `index` (a RecordIndex made
