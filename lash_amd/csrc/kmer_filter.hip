@@ -40,7 +40,7 @@ __device__ __forceinline__ void kmer_filter_walk(const KmerFilterArgs &a)
         const uint64_t nk = L - (uint64_t)k + 1;                           // k-mer start positions of the genome (< 2^32 - 64)
         const uint32_t nk_words = (uint32_t)((nk + 15) >> 4);              // word w holds a k-mer start <=> w < nk_words
         const uint32_t *__restrict__ w = a.words + gd.word_off;
-        const bool multi_rec = gd.format != 0u || gd.rec_end - gd.rec_begin > 1;   // (a single record's bitmap is never written: sketch_kernel)
+        const bool multi_rec = gd.format != 0u || gd.rec_end - gd.rec_begin > 1;   // (as sketch_kernel; always true here: the filter takes raw files only, format != 0)
         const uint32_t *__restrict__ bk = a.brk + gd.brk_off;
         uint32_t *cells = a.cells + a.cell_word[g];
         const uint32_t sh = 64u - (uint32_t)a.log2_cells[g];
