@@ -11,6 +11,7 @@
 #include <atomic>
 #include <thread>
 
+#include "chunk_reader.hpp"
 #include "dist_format.hpp"
 #include "fastx.hpp"
 #include "inflate_fast.hpp"
@@ -167,6 +168,40 @@ uint64_t lash_host_stream_find_cut(const uint8_t *buf, uint64_t n, int fmt, uint
     *carry_len = carry.size();
     if (!carry.empty()) memcpy(carry_out, carry.data(), std::min<size_t>(carry.size(), 64));
     return cut;
+}
+
+// chunk_reader.hpp: the reader of the large-file routes over `path` in chunks of `chunk` bytes under `rule` (0 none, 1 carry, 2 between
+// records, 3 whole records; rule_text as ChunkReader takes it), the rest of every chunk moved to the front of the same buffer.  Returns
+// NULL, the chunks' bytes up to their cuts one after another in *pieces, and 2 * n_pieces numbers in *lens — every piece's length and the
+// length of the carried line after it, the lines one after another in *carries (all malloc'd); else the error text (malloc'd).
+char *lash_host_chunk_reader(const char *path, uint64_t chunk, int rule, int threads, const char *rule_text, uint8_t **pieces, uint64_t **lens,
+                             uint64_t *n_pieces, uint8_t **carries)
+{
+    ChunkReader rd(path, (size_t)chunk, threads, (CutRule)rule, rule_text);
+    std::string err = rd.open();
+    std::vector<uint8_t> buf((size_t)chunk + 64), all, all_carry;
+    std::vector<uint64_t> ln;
+    size_t have = 0;
+    while (err.empty() && !rd.eof()) {
+        err = rd.fill(buf.data(), have);
+        if (err.empty()) err = rd.classify(buf.data());
+        if (err.empty()) err = rd.cut(buf.data());
+        if (!err.empty()) break;
+        all.insert(all.end(), buf.begin(), buf.begin() + rd.cut_at());
+        all_carry.insert(all_carry.end(), rd.carry().begin(), rd.carry().end());
+        ln.push_back(rd.cut_at());
+        ln.push_back(rd.carry().size());
+        have = rd.move_rest(buf.data(), buf.data());
+    }
+    if (!err.empty()) return dup_str(err);
+    *n_pieces = ln.size() / 2;
+    *pieces = (uint8_t *)malloc(all.size() + 1);
+    if (!all.empty()) memcpy(*pieces, all.data(), all.size());
+    *carries = (uint8_t *)malloc(all_carry.size() + 1);
+    if (!all_carry.empty()) memcpy(*carries, all_carry.data(), all_carry.size());
+    *lens = (uint64_t *)malloc((ln.size() + 1) * 8);
+    if (!ln.empty()) memcpy(*lens, ln.data(), ln.size() * 8);
+    return nullptr;
 }
 
 char *lash_host_write_parameters(const char *output_name, const char *algorithm, int k, int precision, uint64_t seed)

@@ -4,6 +4,10 @@
 // grouped into batches in file order, sketched on one or more GPUs (one lash_ctx per device, one host thread each,
 // contiguous batches => output order == file order, utils.rs:509), and the images are streamed through zstd
 // level 3 into {output_name}_sketches.bin (utils.rs:567-574); {output_name}_files.json follows (utils.rs:577-580).
+// Two units carry what the routes share: batch_queue.hpp is the hand-off between the planner, the GPU workers and the in-order writer
+// (in-flight caps, recycled pinned buffers, parts of a --per-record / --window batch leaving while it is still being sketched), and
+// chunk_reader.hpp reads a file above --stream-mb in chunks under the route's cut rule (plain: inside a record with a carried line;
+// --min-count and --aa: between records; --per-record / --window: whole records).  sketch_files.cpp holds the routes and the plan.
 #pragma once
 #include <cstdint>
 #include <string>

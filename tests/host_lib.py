@@ -30,6 +30,9 @@ def _load():
     lib.lash_host_zstd_write.argtypes = [C.c_char_p, C.c_void_p, C.c_uint64, C.c_int, C.c_int]
     lib.lash_host_stream_find_cut.restype = C.c_uint64
     lib.lash_host_stream_find_cut.argtypes = [C.c_char_p, C.c_uint64, C.c_int, C.c_char_p, C.POINTER(C.c_uint64)]
+    lib.lash_host_chunk_reader.restype = C.c_void_p
+    lib.lash_host_chunk_reader.argtypes = [C.c_char_p, C.c_uint64, C.c_int, C.c_int, C.c_char_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
+                                           C.POINTER(C.c_uint64), C.POINTER(C.c_void_p)]
     lib.lash_host_pgzip_read.restype = C.c_void_p
     lib.lash_host_pgzip_read.argtypes = [C.c_char_p, C.c_int, C.c_uint64, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     lib.lash_host_zstd_read.restype = C.c_void_p
@@ -113,6 +116,29 @@ def stream_find_cut(buf: bytes, fmt: int):
     n = C.c_uint64()
     cut = lib.lash_host_stream_find_cut(buf, len(buf), fmt, carry, C.byref(n))
     return int(cut), carry.raw[:n.value]
+
+
+CUT_RULES = {"none": 0, "carry": 1, "between_records": 2, "whole_records": 3}
+
+
+def chunk_reader(path, chunk, rule, threads=1, rule_text=""):
+    """The large-file routes' chunk reader (host/chunk_reader.hpp) over a file: [(piece, carry)] — every chunk's bytes up to its cut and
+    the line carried into the next chunk; raises ValueError with the reader's message."""
+    pieces, lens, carries = C.c_void_p(), C.c_void_p(), C.c_void_p()
+    n = C.c_uint64()
+    err = lib.lash_host_chunk_reader(path.encode(), chunk, CUT_RULES[rule], threads, rule_text.encode(), C.byref(pieces), C.byref(lens),
+                                     C.byref(n), C.byref(carries))
+    if err:
+        raise ValueError(_take_str(err))
+    ln = np.frombuffer(C.string_at(lens, 16 * n.value), dtype=np.uint64).astype(np.int64).reshape(-1, 2)
+    all_p, all_c = C.string_at(pieces, int(ln[:, 0].sum())), C.string_at(carries, int(ln[:, 1].sum()))
+    for p in (pieces, lens, carries):
+        lib.lash_host_free(p)
+    out, a, b = [], 0, 0
+    for lp, lc in ln.tolist():
+        out.append((all_p[a:a + lp], all_c[b:b + lc]))
+        a, b = a + lp, b + lc
+    return out
 
 
 def pgzip_read(path, threads, read_size=1 << 20):

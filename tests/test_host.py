@@ -544,3 +544,140 @@ def test_fastq_error_switch_stop_or_skip():
     a = _fastq_records_after_errors(files["bad_plus_in_the_middle"], False)
     b = _fastq_records_after_errors(files["bad_plus_in_the_middle"], True)
     assert a == seqs[:3] and b == seqs[:3] + seqs[4:6]
+
+
+def _streamed_fasta(seed):
+    """the multi-FASTA of test_streaming_chunks_cover_exactly_the_kmers_of_the_file: about 300 kB, records from a few bases to 120 kB,
+    N runs, lines of 7 / 60 / 80 bases or one line per record"""
+    import random
+    import oracle_lib as O
+    rng = random.Random(seed)
+    g = O.synth_genome(900 + seed, 400_000).tobytes()
+    parts, pos = [], 0
+    while pos < 300_000:
+        n = rng.choice([rng.randint(1, 300), rng.randint(5_000, 40_000), rng.randint(60_000, 120_000)])
+        s = bytearray(g[pos:pos + n])
+        if rng.random() < 0.6 and len(s) > 10:
+            i = rng.randrange(len(s))
+            run = rng.choice([1, 40, 3_000, 30_000])
+            s[i:i + run] = b"N" * len(s[i:i + run])
+        w = rng.choice([60, 80, 10**9, 7])
+        parts.append(b">r%d\n" % len(parts) + b"\n".join(bytes(s[i:i + w]) for i in range(0, len(s), w)) + b"\n")
+        pos += n
+    return b"".join(parts)
+
+
+def _streamed_fastq(seed):
+    """the 3000 records of test_streaming_chunks_of_fastq_split_between_records: quality and header lines that start with '@' and '+'"""
+    import random
+    rng = random.Random(100 + seed)
+    recs = []
+    for i in range(3000):
+        L = rng.choice([1, 36, 100, 150, rng.randint(1, 300)])
+        s = bytes(rng.choice(b"ACGTN") for _ in range(L))
+        q = bytes(rng.choice(b"@+I#F>A") for _ in range(L))
+        recs.append(b"@r%d %s\n" % (i, rng.choice([b"", b"@+x"])) + s + b"\n+" + rng.choice([b"", b"r%d" % i]) + b"\n" + q + b"\n")
+    return b"".join(recs)
+
+
+def _restated_chunks(data, chunk, fmt):
+    """[(piece, carry)] by the loop of the two tests above: fill up to the chunk size, cut with stream_find_cut unless the file has ended,
+    start the next chunk with the carried line and what followed the cut"""
+    out, buf, rest = [], b"", data
+    while rest or buf:
+        take = chunk - len(buf)
+        buf, rest = buf + rest[:take], rest[take:]
+        cut, carry = H.stream_find_cut(buf, fmt) if rest else (len(buf), b"")
+        out.append((buf[:cut], carry))
+        buf = carry + buf[cut:]
+    return out
+
+
+def _plain_and_multi_member_gz(tmp_path, data, name):
+    """(path, threads) of the bytes as they are and as a .gz of seven members, read by one thread and by four"""
+    plain, gz = tmp_path / name, tmp_path / (name + ".gz")
+    plain.write_bytes(data)
+    step = len(data) // 7 + 1
+    gz.write_bytes(b"".join(gzip.compress(data[i:i + step], 1) for i in range(0, len(data), step)))
+    return [(str(plain), 1), (str(gz), 1), (str(gz), 4)]
+
+
+@pytest.mark.parametrize("seed", range(6))
+def test_chunk_reader_cuts_fasta_as_the_restated_loop_does(tmp_path, seed):
+    """host/chunk_reader.cpp under the `carry` rule — the loop the plain streamed route runs — against the Python loop of
+    test_streaming_chunks_cover_exactly_the_kmers_of_the_file: the same pieces and carried lines, piece for piece."""
+    data = _streamed_fasta(seed)
+    for path, threads in _plain_and_multi_member_gz(tmp_path, data, "whole.fa"):
+        for chunk in (20_000, 33_333, 50_000):
+            assert H.chunk_reader(path, chunk, "carry", threads) == _restated_chunks(data, chunk, 1), (path, threads, chunk)
+
+
+@pytest.mark.parametrize("seed", range(4))
+def test_chunk_reader_cuts_fastq_as_the_restated_loop_does(tmp_path, seed):
+    """the same for the FASTQ of test_streaming_chunks_of_fastq_split_between_records, under both rules that FASTQ may take: nothing is
+    ever carried, so `between_records` gives the pieces of `carry`"""
+    data = _streamed_fastq(seed)
+    for path, threads in _plain_and_multi_member_gz(tmp_path, data, "w.fq"):
+        for chunk in (4_000, 10_007, 50_000):
+            want = _restated_chunks(data, chunk, 2)
+            assert all(c == b"" for _, c in want)
+            assert H.chunk_reader(path, chunk, "carry", threads) == want, (path, threads, chunk)
+            assert H.chunk_reader(path, chunk, "between_records", threads, "unused") == want, (path, threads, chunk)
+
+
+def test_chunk_reader_rules_and_refusals(tmp_path):
+    """The two rules that never cut a record, the sizing pass, and every refusal with its text."""
+    import random
+    rng = random.Random(7)
+    rec = lambda i, n: b">rec%d some words\n" % i + b"\n".join(bytes(rng.choice(b"ACGT") for _ in range(min(70, n - j))) for j in range(0, n, 70)) + b"\n"
+    small = b"".join(rec(i, rng.randint(1, 6_000)) for i in range(12))                 # every record fits in a 20 000-byte chunk
+    big = small + rec(99, 30_000) + rec(100, 50)                                       # record 99 does not
+    cases = _plain_and_multi_member_gz(tmp_path, small, "small.fa")
+    too_long = "--min-count: a record of X is larger than a --stream-mb chunk and cannot be counted in pieces; raise --stream-mb"
+    for path, threads in cases:
+        for rule in ("whole_records", "between_records"):
+            got = H.chunk_reader(path, 20_000, rule, threads, "--per-record" if rule == "whole_records" else too_long)
+            assert len(got) > 1 and b"".join(p for p, _ in got) == small
+            assert all(p.startswith(b">") and p.endswith(b"\n") and c == b"" for p, c in got)
+            assert all(len(p) <= 20_000 for p, _ in got)
+        # the sizing pass: no format, no cut, every byte once
+        got = H.chunk_reader(path, 20_000, "none", threads)
+        assert b"".join(p for p, _ in got) == small and all(len(p) == 20_000 for p, _ in got[:-1])
+    # whole_records looks for its cut through the whole chunk, between_records only through its second half: a record of 15.2 kB
+    # after one of 0.1 kB is cut off at offset 121 of a 15 300-byte chunk
+    tiny_then_long = rec(0, 100) + rec(1, 15_000) + rec(2, 100)
+    (tmp_path / "t.fa").write_bytes(tiny_then_long)
+    got = H.chunk_reader(str(tmp_path / "t.fa"), 15_300, "whole_records", 1, "--per-record")
+    assert [p.split(b" ")[0] for p, _ in got] == [b">rec0", b">rec1", b">rec2"] and b"".join(p for p, _ in got) == tiny_then_long
+    with pytest.raises(ValueError, match="larger than a --stream-mb chunk"):
+        H.chunk_reader(str(tmp_path / "t.fa"), 15_300, "between_records", 1, too_long)
+    for path, threads in _plain_and_multi_member_gz(tmp_path, big, "big.fa"):
+        with pytest.raises(ValueError, match="larger than a --stream-mb chunk"):
+            H.chunk_reader(path, 20_000, "between_records", threads, too_long)
+        with pytest.raises(ValueError) as e:
+            H.chunk_reader(path, 20_000, "whole_records", threads, "--window")
+        assert "record 'rec99' of " + path in str(e.value) and "--window never splits a record, raise --stream-mb" in str(e.value)
+        assert len(H.chunk_reader(path, 20_000, "carry", threads)) > 2                 # the plain route cuts inside it
+    for data, text in ((b"", "Invalid input file: empty (%s)"), (b"not a sequence file\n" * 10, "Invalid input file: neither FASTA ('>') nor FASTQ ('@'): %s")):
+        (tmp_path / "bad.txt").write_bytes(data)
+        for rule in ("carry", "between_records", "whole_records"):
+            with pytest.raises(ValueError) as e:
+                H.chunk_reader(str(tmp_path / "bad.txt"), 20_000, rule, 1, "--per-record")
+            assert str(e.value) == text % (tmp_path / "bad.txt")
+    (tmp_path / "r.fq").write_bytes(_streamed_fastq(0)[:30_000])
+    with pytest.raises(ValueError) as e:
+        H.chunk_reader(str(tmp_path / "r.fq"), 20_000, "whole_records", 1, "--per-record")
+    assert str(e.value) == "--per-record takes FASTA input; this file starts with '@' (FASTQ): %s" % (tmp_path / "r.fq")
+
+
+def test_batch_queue_under_thread_and_address_sanitizers(tmp_path):
+    """host/batch_queue.hpp, the hand-off between planner, GPU workers and writer, driven by tests/host_queue_check.cpp (fake buffers, 1 and 3
+    workers, an in-flight cap of 3): a stand-alone executable built with ThreadSanitizer, then with AddressSanitizer + UBSan."""
+    src = os.path.join(os.path.dirname(os.path.abspath(__file__)), "host_queue_check.cpp")
+    kinds = {"tsan": "-fsanitize=thread", "asan": "-fsanitize=address,undefined"}
+    builds = {k: subprocess.Popen(["g++", "-O1", "-g", "-std=c++17", "-pthread", f, "-o", str(tmp_path / k), src]) for k, f in kinds.items()}   # side by side
+    for name, build in builds.items():
+        assert build.wait() == 0, name
+        r = subprocess.run([str(tmp_path / name)], capture_output=True, text=True, timeout=60)
+        assert r.returncode == 0 and "all scenarios passed" in r.stdout, (name, r.stdout[-2000:], r.stderr[-4000:])
+        assert "Sanitizer" not in r.stderr and "runtime error" not in r.stderr, (name, r.stderr[-4000:])
