@@ -275,6 +275,44 @@ int      lash_sketch_windows_raw(lash_ctx *ctx, const lash_params *prm, const la
                                  uint8_t *out_images);
 void     lash_win_index_free(lash_ctx *ctx, lash_win_index *windows);
 
+/* Six-frame PROTEIN sketches of nucleotide FASTA (`lash sketch --translate`): genomes too far apart for nucleotide k-mers are compared in protein
+ * space, and a user with assemblies has no proteins.  lash_fasta_translate translates the records of an index (made from the same raw / file_off
+ * on the same context) on the device (fasta_translate.hip) into one buffer the result owns until it is freed.  The rule does not depend on k:
+ *   sequence bytes  S[0..L) of a record: as for lash_fasta_windows (the bytes after the header line's LF that are neither LF nor CR)
+ *   bases           ACGTacgt, case ignored (soft-masked sequence translates like any other); every other byte, N and U included, is no base
+ *   frames          f = 0, 1, 2 read S from offset f; f = 3, 4, 5 read the reverse complement R[t] = comp(S[L - 1 - t]) from offset f - 3;
+ *                   frame f has n_f = max(0, floor((L - offset) / 3)) codons, a trailing partial codon is dropped
+ *   codons          three bases: the standard genetic code (NCBI table 1; table 11 maps codons alike), a stop gives '*'; a codon with a
+ *                   no-base gives 'X'.  '*' and 'X' are BREAK BYTES
+ *   buffer          records in index order, frames 0..5 in order, each frame its n_f bytes and one '*': record r takes 6 + 2 * max(0, L_r - 2) bytes
+ *   segments        a segment ends after every break byte: segment s = bytes [seg_off[s], seg_off[s + 1]), seg_off[0] = 0, as many segments
+ *                   as break bytes, a segment may be one byte long; rec_seg[r] (n_records + 1 entries) = the first segment of record r
+ * lash_sketch_translated sketches groups of records: group g = records [group_rec_off[g], group_rec_off[g + 1]) of the index (ascending,
+ * within [0, n_records]; they need not start at 0 or cover everything), one image per group: the LASH_F_AMINO sketch whose records are the
+ * group's segments.  It is lash_sketch_batch_device with LASH_F_AMINO OR-ed into prm->flags on (buffer, seg_off, the groups' segment and byte
+ * offsets), the images copied to the host, the stream synchronized; LASH_F_ACCUMULATE, LASH_F_HMH_X_LOW and the context's layout (aa_codes
+ * included) apply.  A segment's trailing break byte counts toward its raw length and is deleted by the amino-acid filter, so no k-mer spans a
+ * stop, an ambiguous codon, two frames or two records, and a segment of fewer than k residues yields none.  A sketch made this way and a
+ * LASH_F_AMINO sketch of a proteome hold the same kind of k-mers.
+ * With an index made by lash_fasta_index from this same `raw` pointer the bytes are not sent again; _device: the bytes are in device memory.
+ * Both synchronize the context's stream (the totals size the result).  Device memory: the buffer is about twice the sequence bytes and seg_off
+ * about 0.75 bytes per base of random DNA: budget 5 x the raw bytes with the input and the scratch.  LASH_EINVAL: an index or a translation
+ * of another context or buffer, group offsets descending or beyond n_records, k outside 1..12; LASH_ENOMEM: no room; LASH_ELIMIT: 2^32
+ * segments or more in one group. */
+typedef struct lash_tr_index lash_tr_index;
+int      lash_fasta_translate(lash_ctx *ctx, const uint8_t *raw, const uint64_t *file_off, uint32_t n_files, const lash_rec_index *index,
+                              lash_tr_index **out);
+int      lash_fasta_translate_device(lash_ctx *ctx, const uint8_t *d_raw, const uint64_t *file_off, uint32_t n_files, const lash_rec_index *index,
+                                     lash_tr_index **out);
+uint64_t lash_tr_index_n_segments(const lash_tr_index *translated);
+uint64_t lash_tr_index_bytes(const lash_tr_index *translated);
+const uint8_t *lash_tr_index_buffer_device(const lash_tr_index *translated);
+int      lash_tr_index_seg_off(lash_ctx *ctx, const lash_tr_index *translated, uint64_t *out);   /* n_segments + 1 */
+int      lash_tr_index_rec_seg(lash_ctx *ctx, const lash_tr_index *translated, uint64_t *out);   /* n_records + 1 */
+int      lash_sketch_translated(lash_ctx *ctx, const lash_params *prm, const lash_tr_index *translated, const uint64_t *group_rec_off,
+                                uint32_t n_groups, uint8_t *out_images);
+void     lash_tr_index_free(lash_ctx *ctx, lash_tr_index *translated);
+
 /* K-mer abundance filter (`lash sketch --min-count M`; Mash -m, not upstream): a k-mer a file holds fewer than M times stays out of its
  * sketch.  A sequencing error makes up to k k-mers that exist nowhere else, and in a read set they can outnumber the real ones.
  *   key      the masked canonical k-mer value the reference hands to add_kmer (utils.rs:464-499), as a u64 for all three sketch types

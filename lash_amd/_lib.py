@@ -105,6 +105,15 @@ PROTOTYPES = {
     "lash_win_index_offset": (_int, [_vp, _vp, _vp]),
     "lash_sketch_windows_raw": (_int, [_vp, _PP, _vp, _u64, _u64, _vp]),
     "lash_win_index_free": (None, [_vp, _vp]),
+    "lash_fasta_translate": (_int, [_vp, _vp, _vp, _u32, _vp, C.POINTER(_vp)]),
+    "lash_fasta_translate_device": (_int, [_vp, _vp, _vp, _u32, _vp, C.POINTER(_vp)]),
+    "lash_tr_index_n_segments": (_u64, [_vp]),
+    "lash_tr_index_bytes": (_u64, [_vp]),
+    "lash_tr_index_buffer_device": (_vp, [_vp]),
+    "lash_tr_index_seg_off": (_int, [_vp, _vp, _vp]),
+    "lash_tr_index_rec_seg": (_int, [_vp, _vp, _vp]),
+    "lash_sketch_translated": (_int, [_vp, _PP, _vp, _vp, _u32, _vp]),
+    "lash_tr_index_free": (None, [_vp, _vp]),
     "lash_hll_replay_sums_device": (_int, [_vp, _PP, _vp, _vp, _u64, _vp, _u32, _vp]),
     "lash_hll_replay_streamed_chunk": (_int, [_vp, _PP, _vp, _u64, _int, _vp, _vp, _vp, _vp]),
     "lash_ctx_hll_inexact_sums": (_u32, [_vp, _vp, _u32]),

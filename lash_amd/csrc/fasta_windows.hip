@@ -204,6 +204,22 @@ static void fw_sections(uint8_t *scratch, uint32_t n_tiles, uint32_t n, uint32_t
     win_base = seq0 + n + 1;
 }
 
+void fasta_windows_rank_view(uint8_t *d_scratch, uint32_t n_tiles, uint32_t n_records, const uint32_t **d_lanes, const uint64_t **d_tile_base,
+                             const uint64_t **d_seq0)
+{
+    uint32_t *lanes; uint64_t *tile_base, *seq_begin, *seq0, *win_base;
+    fw_sections(d_scratch, n_tiles, n_records, lanes, tile_base, seq_begin, seq0, win_base);
+    *d_lanes = lanes;
+    *d_tile_base = tile_base;
+    *d_seq0 = seq0;
+}
+
+hipError_t launch_scan_u64(uint64_t *d_a, uint32_t n, hipStream_t stream)
+{
+    hipLaunchKernelGGL(fw_scan_kernel, dim3(1), dim3(1024), 0, stream, d_a, n);
+    return hipGetLastError();
+}
+
 hipError_t launch_fasta_windows_count(const uint8_t *d_raw, uint64_t total, const uint64_t *d_start, uint32_t n_records, uint32_t n_tiles,
                                       uint64_t window, uint8_t *d_scratch, const uint64_t **d_seq_bytes, const uint64_t **d_n_windows,
                                       hipStream_t stream)

@@ -5,7 +5,7 @@
 //   lash hll-bias -o FILE [-p P[,P...]] [--points N] [--trials T] [--seed S] [--device D]    (not upstream: HLL++ bias tables, simulated)
 // Extras that do not exist upstream: --gpus N / --device D / --devices LIST (which GPUs to use, one worker each), --batch-mb M, --stream-mb M (files
 // larger than M MiB are streamed in chunks with on-device accumulation), --hmh-x-low, --min-count M [--count-cells-log2 L] (drop the k-mers a
-// file holds fewer than M times, counted on the GPU), --window (one sketch per W-base window of every record), --per-record (one sketch per FASTA record, the records
+// file holds fewer than M times, counted on the GPU), --window (one sketch per W-base window of every record), --translate (six-frame protein sketches of nucleotide FASTA, translated on the GPU), --per-record (one sketch per FASTA record, the records
 // found on the GPU); dist: --device D, --block-rows N, --hll-bias FILE / --hll-bias-sim (HLL++ bias tables from a file / simulated on the GPU),
 // --file-order (rows / columns in list-file order instead of the reference's seeded hash-map order), --max-dist D (print only
 // the pairs with distance <= D), --top K (only each name's K nearest), --cluster D (single-linkage clusters of an all-vs-all instead
@@ -60,6 +60,12 @@ void usage()
             "                               overlap and never span two records; a record's last, shorter window is kept).  {output}_files.json\n"
             "                               then holds ID:B-E, the record id and the 1-based inclusive range.  FASTA only, not with --aa or\n"
             "                               --min-count; --per-record changes nothing\n"
+            "      --translate              Protein sketches of nucleotide FASTA: every record is translated on the GPU in all six reading frames\n"
+            "                               (standard code; ACGT in either case, any other byte makes its codon ambiguous) and sketched like --aa,\n"
+            "                               no k-mer spanning a stop, an ambiguous codon, two frames or two records.  Needs -k 1..12 (the default\n"
+            "                               16 is refused).  One sketch per file, or per record with --per-record; the output reads like --aa\n"
+            "                               output (molecule: amino_acid).  FASTA only; takes about 5 x --batch-mb of device memory; not with\n"
+            "                               --aa, --min-count or --window\n"
             "      --min-count <M>          Keep only the k-mers a file holds at least M times (1-255; read sets: a sequencing error makes\n"
             "                               k-mers seen once; like Mash -m).  Counted per file on the GPU in 2^L saturating cells, two cells\n"
             "                               per k-mer; a rarer k-mer gets in only when collisions fill both.  Files are read twice.  hmh,\n"
@@ -145,7 +151,7 @@ int cmd_sketch(int argc, char **argv)
     std::string err;
     const std::map<std::string, std::string> alias = {{"f", "file"}, {"o", "output"}, {"k", "kmer"}, {"t", "threads"},
                                                       {"a", "algorithm"}, {"p", "precision"}, {"s", "seed"}};
-    if (!parse(argc, argv, 2, alias, {"hmh-x-low", "aa", "per-record", "help"}, a, err)) { fprintf(stderr, "error: %s\n", err.c_str()); return 2; }
+    if (!parse(argc, argv, 2, alias, {"hmh-x-low", "aa", "per-record", "translate", "help"}, a, err)) { fprintf(stderr, "error: %s\n", err.c_str()); return 2; }
     if (a.flags.count("help")) { usage(); return 0; }
     if (!a.kv.count("file")) { fprintf(stderr, "error: the following required arguments were not provided:\n  --file <file>\n"); return 2; }
     SketchOptions opt;
@@ -168,6 +174,10 @@ int cmd_sketch(int argc, char **argv)
     if (k < 1 || k > 32) { fprintf(stderr, "k-mer length must be 1-32\n"); return 101; }       // utils.rs:501 panic
     const bool amino = a.flags.count("aa") != 0;                                               // main.rs:97-104 (commented out there)
     opt.per_record = a.flags.count("per-record") != 0;
+    opt.translate = a.flags.count("translate") != 0;
+    if (opt.translate && amino) { fprintf(stderr, "error: --translate cannot be used with --aa (--translate takes nucleotide input and makes the proteins itself)\n"); return 2; }
+    if (opt.translate && a.kv.count("min-count")) { fprintf(stderr, "error: --translate cannot be used with --min-count (k-mers are counted for nucleotide sketches only)\n"); return 2; }
+    if (opt.translate && a.kv.count("window")) { fprintf(stderr, "error: --translate cannot be used with --window (windows of translated records are not supported)\n"); return 2; }
     if (a.kv.count("window")) {
         uint64_t w = 0;
         if (!to_u64(a.kv["window"], w) || w < 1) {
@@ -179,6 +189,7 @@ int cmd_sketch(int argc, char **argv)
         if (a.kv.count("min-count")) { fprintf(stderr, "error: --window cannot be used with --min-count (k-mers are counted per file)\n"); return 2; }
         opt.window = w;
     }
+    if (opt.translate && k > 12) { fprintf(stderr, "k-mer length for amino acid must be 1\xe2\x80\x93" "12\n"); return 101; }   // the --aa message
     if (opt.per_record && amino) { fprintf(stderr, "error: --per-record cannot be used with --aa (records are split for nucleotide FASTA only)\n"); return 2; }
     if (amino && k > 12) { fprintf(stderr, "k-mer length for amino acid must be 1\xe2\x80\x93" "12\n"); return 101; }   // utils.rs:554 panic
     if (a.kv.count("count-cells-log2") && !a.kv.count("min-count")) { fprintf(stderr, "error: --count-cells-log2 needs --min-count\n"); return 2; }
@@ -210,7 +221,7 @@ int cmd_sketch(int argc, char **argv)
     opt.threads = (int)std::max<uint64_t>(1, threads);
     opt.batch_bytes = std::max<uint64_t>(1, batch_mb) << 20;
     opt.stream_bytes = std::max<uint64_t>(1, stream_mb) << 20;
-    opt.flags = (a.flags.count("hmh-x-low") ? LASH_F_HMH_X_LOW : 0) | (amino ? LASH_F_AMINO : 0);
+    opt.flags = (a.flags.count("hmh-x-low") ? LASH_F_HMH_X_LOW : 0) | (amino || opt.translate ? LASH_F_AMINO : 0);
     err = layout_from_option(a.kv.count("layout") ? a.kv["layout"] : "", opt.layout);
     if (!err.empty()) { fprintf(stderr, "error: %s\n", err.c_str()); return 2; }
     if (a.kv.count("devices")) {                              // explicit worker list, e.g. 0,1,2,3 (repeats allowed: 0,0 = two workers on GPU 0)
@@ -234,7 +245,7 @@ int cmd_sketch(int argc, char **argv)
     err = sketch_files(opt, files, output, &st);
     if (opt.window && err.rfind("--window takes FASTA input", 0) == 0) { fprintf(stderr, "error: %s\n", err.c_str()); return 2; }   // a refusal of the flag
     if (!err.empty()) { fprintf(stderr, "Error: %s\n", err.c_str()); return 1; }
-    err = write_parameters_json(output, alg, opt.k, opt.precision, opt.seed, amino);
+    err = write_parameters_json(output, alg, opt.k, opt.precision, opt.seed, amino || opt.translate);
     if (!err.empty()) { fprintf(stderr, "Error: %s\n", err.c_str()); return 1; }
     if (opt.window)
         fprintf(stderr, "sketched %llu windows of %llu files (%.3f GB of FASTA text) in %.2f s on %zu GPU(s), %llu batches\n",

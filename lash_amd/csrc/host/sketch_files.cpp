@@ -373,6 +373,47 @@ std::string stream_big_file_filtered(lash_ctx *ctx, const lash_params &prm0, con
     return err;
 }
 
+// --translate needs about five times a batch in device memory (the input, the coordinates, two residues per base, the segment table)
+std::string translate_error(lash_ctx *ctx, int rc)
+{
+    return gpu_error(ctx, rc) + (rc == LASH_ENOMEM ? " (--translate takes about 5 x the batch in device memory: lower --batch-mb / --stream-mb)" : "");
+}
+
+// --translate for a file above --stream-mb, one sketch: chunks of whole records (a k-mer never spans two records, so the union of the
+// chunks' images is the file's), each indexed, translated and sketched into the one image, with LASH_F_ACCUMULATE from the second on.
+// One buffer, no overlap of reading and sketching.
+std::string stream_big_file_translated(lash_ctx *ctx, const lash_params &prm0, const std::string &path, uint64_t chunk_bytes, PinnedBuf &buf,
+                                       uint8_t *image, uint64_t &bytes_seen, int threads)
+{
+    if (!buf.reserve(chunk_bytes + 64)) return "out of pinned host memory";
+    ChunkReader rd(path, chunk_bytes, threads, CutRule::whole_records, "--translate");
+    std::string err = rd.open();
+    size_t have = 0;
+    uint64_t calls = 0;
+    while (err.empty() && !rd.eof()) {
+        err = rd.fill(buf.p, have);
+        if (err.empty()) err = rd.classify(buf.p);
+        if (err.empty()) err = rd.cut(buf.p);
+        if (!err.empty()) break;
+        lash_params prm = prm0;
+        if (calls) prm.flags |= LASH_F_ACCUMULATE;
+        const uint64_t off[2] = {0, (uint64_t)rd.cut_at()};
+        lash_rec_index *ix = nullptr;
+        lash_tr_index *ti = nullptr;
+        int rc = lash_fasta_index(ctx, buf.p, off, 1, &ix);
+        if (rc == LASH_OK) rc = lash_fasta_translate(ctx, buf.p, off, 1, ix, &ti);
+        const uint64_t goff[2] = {0, lash_rec_index_n_records(ix)};
+        if (rc == LASH_OK) rc = lash_sketch_translated(ctx, &prm, ti, goff, 1, image);
+        if (rc != LASH_OK) err = translate_error(ctx, rc);
+        lash_tr_index_free(ctx, ti);
+        lash_rec_index_free(ctx, ix);
+        ++calls;
+        if (err.empty()) have = rd.move_rest(buf.p, buf.p);
+    }
+    bytes_seen += rd.bytes_read();
+    return err;
+}
+
 // what the routes of one `lash sketch` run share
 struct Run {
     const std::chrono::steady_clock::time_point t_start;
@@ -382,7 +423,7 @@ struct Run {
     const size_t ib;                                       // bytes of one image
     // --window splits at records as --per-record does, then cuts every record into windows: the same batches, parts and hand-off
     const bool by_record;
-    const std::string split_flag;                          // "--window" or "--per-record", for messages
+    const std::string split_flag;                          // "--window", "--translate" or "--per-record", for messages
     BatchQueue q;
     uint64_t n_bytes = 0, n_batches = 0;                   // the planner's: input bytes seen, batches planned
     const bool timing = getenv("LASH_CLI_TIMING") != nullptr;
@@ -413,6 +454,7 @@ std::string sketch_records(Run &run, lash_ctx *ctx, Batch &b)
     const char *raw = reinterpret_cast<const char *>(b.buf->p);
     lash_rec_index *ix = nullptr;
     lash_win_index *wi = nullptr;
+    lash_tr_index *ti = nullptr;
     int rc = lash_fasta_index(ctx, b.buf->p, b.file_off.data(), nf, &ix);
     if (rc != LASH_OK) return gpu_error(ctx, rc);
     uint64_t n = lash_rec_index_n_records(ix);             // the items to sketch: records, or their windows
@@ -433,21 +475,29 @@ std::string sketch_records(Run &run, lash_ctx *ctx, Batch &b)
     } else if (rc == LASH_OK) {
         b.names.reserve(n);
         for (uint64_t r = 0; r < n; ++r) b.names.emplace_back(raw + start[r] + 1, id_len[r]);
+        // --translate: the six frames of every record as residues (lash_fasta_translate); a record is then a group of one
+        if (run.opt.translate) rc = lash_fasta_translate(ctx, b.buf->p, b.file_off.data(), nf, ix, &ti);
     }
     const std::string item = run.opt.window ? "window '" : "record '";
     const uint64_t step = std::max<uint64_t>(1, kRecordImageCap / std::max<size_t>(run.ib, 1));
     for (uint64_t i0 = 0; i0 < n && rc == LASH_OK; i0 += step) {
         const uint64_t i1 = std::min(n, i0 + step);
         std::vector<uint8_t> part((size_t)(i1 - i0) * run.ib, 0);
-        rc = wi ? lash_sketch_windows_raw(ctx, &run.prm, wi, i0, i1, part.data())
-                : lash_sketch_records_raw(ctx, &run.prm, b.buf->p, b.file_off.data(), nf, ix, i0, i1, part.data());
+        if (ti) {
+            std::vector<uint64_t> goff((size_t)(i1 - i0) + 1);
+            for (uint64_t i = i0; i <= i1; ++i) goff[i - i0] = i;
+            rc = lash_sketch_translated(ctx, &run.prm, ti, goff.data(), (uint32_t)(i1 - i0), part.data());
+        } else
+            rc = wi ? lash_sketch_windows_raw(ctx, &run.prm, wi, i0, i1, part.data())
+                    : lash_sketch_records_raw(ctx, &run.prm, b.buf->p, b.file_off.data(), nf, ix, i0, i1, part.data());
         if (rc != LASH_OK) break;
         // (no note is expected: a call that does not accumulate re-does such records exactly)
         if (run.prm.algo == LASH_HLL)
             hll_notes_of_last_call(ctx, (uint32_t)(i1 - i0), [&](uint32_t i) { return item + b.names[i0 + i] + "' of " + run.files[b.f0]; });
         run.q.add_part(b, std::move(part), kRecordImageCap);
     }
-    const std::string e = rc == LASH_OK ? "" : gpu_error(ctx, rc);
+    const std::string e = rc == LASH_OK ? "" : run.opt.translate ? translate_error(ctx, rc) : gpu_error(ctx, rc);
+    lash_tr_index_free(ctx, ti);
     lash_win_index_free(ctx, wi);
     lash_rec_index_free(ctx, ix);
     return e;
@@ -470,9 +520,33 @@ int sketch_filtered(Run &run, lash_ctx *ctx, Batch &b)
     return rc;
 }
 
+// --translate, one image per file: the batch's records are found and translated on the device, a file is the group of its records
+std::string sketch_translated_batch(Run &run, lash_ctx *ctx, Batch &b)
+{
+    const uint32_t ng = (uint32_t)(b.f1 - b.f0);
+    lash_rec_index *ix = nullptr;
+    lash_tr_index *ti = nullptr;
+    int rc = lash_fasta_index(ctx, b.buf->p, b.file_off.data(), ng, &ix);
+    if (rc != LASH_OK) return gpu_error(ctx, rc);
+    const uint64_t n = lash_rec_index_n_records(ix);
+    std::vector<uint32_t> file(n);
+    std::vector<uint64_t> goff((size_t)ng + 1, 0);
+    if ((rc = lash_rec_index_file(ctx, ix, file.data())) == LASH_OK) {
+        for (uint64_t r = 0; r < n; ++r) ++goff[file[r] + 1];              // records come in file order
+        for (uint32_t g = 0; g < ng; ++g) goff[g + 1] += goff[g];
+        rc = lash_fasta_translate(ctx, b.buf->p, b.file_off.data(), ng, ix, &ti);
+    }
+    if (rc == LASH_OK) rc = lash_sketch_translated(ctx, &run.prm, ti, goff.data(), ng, b.images.data());
+    const std::string e = rc == LASH_OK ? "" : translate_error(ctx, rc);
+    lash_tr_index_free(ctx, ti);
+    lash_rec_index_free(ctx, ix);
+    return e;
+}
+
 // one image per file of the batch; the FASTA/FASTQ parse runs on the GPU (lash_sketch_files_raw)
 std::string sketch_batch(Run &run, lash_ctx *ctx, Batch &b)
 {
+    if (run.opt.translate) return sketch_translated_batch(run, ctx, b);
     const uint32_t ng = (uint32_t)(b.f1 - b.f0);
     const int rc = run.opt.min_count ? sketch_filtered(run, ctx, b)
                                      : lash_sketch_files_raw(ctx, &run.prm, b.buf->p, b.file_off.data(), b.fmt.data(), ng, b.images.data());
@@ -609,7 +683,9 @@ std::string plan_streamed_file(Run &run, Streamer &st, size_t i, uint64_t stream
         if (rc == LASH_OK) rc = lash_ctx_set_layout(st.ctx, &run.opt.layout);
         if (rc != LASH_OK) return lash_strerror(rc);
     }
-    if (run.opt.min_count) {
+    if (run.opt.translate)
+        b->err = stream_big_file_translated(st.ctx, run.prm, run.files[i], stream_bytes, st.buf, b->images.data(), run.n_bytes, run.opt.threads);
+    else if (run.opt.min_count) {
         int l2 = 0;
         b->err = stream_big_file_filtered(st.ctx, run.prm, run.files[i], stream_bytes, st.buf, b->images.data(), run.n_bytes, run.opt.threads,
                                           run.opt.min_count, run.opt.count_cells_log2, l2);
@@ -640,7 +716,7 @@ std::string sketch_files(const SketchOptions &opt, const std::vector<std::string
         if (d < 0 || d >= n_dev_avail) return "device index out of range";
     const size_t n_files = files.size();
     Run run{t_start, opt, files, prm, lash_layout_image_bytes(&opt.layout, opt.algo, opt.precision), opt.per_record || opt.window != 0,
-            opt.window ? "--window" : "--per-record"};
+            opt.window ? "--window" : opt.translate ? "--translate" : "--per-record"};
     // Enough batches to keep every device fed and to read ahead while the HIP contexts come up (~0.3 s), but not more
     // page-locked memory than ~512 MiB: pinning costs ~0.18 s per GB and is the slowest thing the host does here.
     const size_t in_flight_cap = std::max<size_t>(2 * devices.size() + 1, (size_t)((512ull << 20) / std::max<uint64_t>(opt.batch_bytes, 1)));
@@ -719,7 +795,7 @@ std::string sketch_files(const SketchOptions &opt, const std::vector<std::string
                         if (e.empty()) {
                             const int f = sniff_format(dst, s.size);
                             if (!f) e = error_not_fastx(files[i]);
-                            else if (run.by_record && f != LASH_FMT_FASTA) e = error_not_fasta(run.split_flag, files[i]);
+                            else if ((run.by_record || opt.translate) && f != LASH_FMT_FASTA) e = error_not_fasta(run.split_flag, files[i]);
                             b->fmt[i - b->f0] = (uint8_t)(f ? f : LASH_FMT_FASTA);
                             // (malformed FASTQ records: found on the device, the file is then re-done by the library with
                             // needletail's rule — utils.rs:457 — or, under layout fastq_err=skip, without the bad records)

@@ -7,7 +7,7 @@
 // Two units carry what the routes share: batch_queue.hpp is the hand-off between the planner, the GPU workers and the in-order writer
 // (in-flight caps, recycled pinned buffers, parts of a --per-record / --window batch leaving while it is still being sketched), and
 // chunk_reader.hpp reads a file above --stream-mb in chunks under the route's cut rule (plain: inside a record with a carried line;
-// --min-count and --aa: between records; --per-record / --window: whole records).  sketch_files.cpp holds the routes and the plan.
+// --min-count and --aa: between records; --per-record / --window / --translate: whole records).  sketch_files.cpp holds the routes and the plan.
 #pragma once
 #include <cstdint>
 #include <string>
@@ -33,6 +33,7 @@ struct SketchOptions {
     uint32_t flags = 0;              // LASH_F_HMH_X_LOW, LASH_F_AMINO (--aa)
     bool per_record = false;         // --per-record: one sketch per FASTA record instead of one per file (records found on the GPU)
     uint64_t window = 0;             // --window W: one sketch per W-base window of every FASTA record (cut on the GPU); 0: off
+    bool translate = false;          // --translate: nucleotide FASTA in, six-frame protein sketches out (translated on the GPU; flags carry LASH_F_AMINO)
     uint32_t min_count = 0;          // --min-count M: 0 = off, else only the k-mers a file holds at least M times reach its sketch (lash_kmer_filter_*)
     int count_cells_log2 = 0;        // --count-cells-log2 L: cells of a file's count table; 0 = ceil(log2(8 x file bytes)) within 16..36
     lash_layout layout;              // set by layout_from_option(); every context gets it

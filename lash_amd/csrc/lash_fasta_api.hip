@@ -2,7 +2,9 @@
 // device-side record index of raw multi-FASTA bytes (fasta_index.hip), and lash_sketch_records_raw, which hands a range of that index
 // to the raw-file route with records where it has files (`lash sketch --per-record`); lash_fasta_windows[_device], which rewrites the records
 // of an index as fixed-length windows (fasta_windows.hip), and lash_sketch_windows_raw, which hands a range of those to the same route
-// (`lash sketch --window`).
+// (`lash sketch --window`); lash_fasta_translate[_device], which writes the six reading frames of the records of an index as residues cut into
+// segments (fasta_translate.hip), and lash_sketch_translated, which hands groups of those records to the amino-acid route (`lash sketch
+// --translate`).
 #include "lash_ctx.h"
 #include "lash_internal.h"
 
@@ -22,6 +24,15 @@ struct lash_win_index {
     DevBuf record, begin, length, off;           // [n] u64 each, off [n + 1]: where every window's one-record FASTA file starts in buf
     DevBuf buf;                                  // the windows, each as ">\n" + its bases + "\n"
     mutable std::vector<uint64_t> h_off;         // host copy of off[], fetched by the first lash_sketch_windows_raw
+};
+
+struct lash_tr_index {
+    int device = 0;
+    uint32_t n = 0;                              // records of the index it was made from
+    uint64_t bytes = 0, n_seg = 0;               // size of buf == out_base[n] == seg_off[n_seg]; segments == break bytes
+    DevBuf buf;                                  // the frames of every record: residues, 'X', '*'
+    DevBuf seg_off, rec_seg, out_base;           // [n_seg + 1], [n + 1], [n + 1] u64
+    std::vector<uint64_t> h_rec_seg, h_out_base; // host copies: the groups of lash_sketch_translated are planned from them
 };
 
 extern "C" {
@@ -246,6 +257,141 @@ int lash_sketch_windows_raw(lash_ctx *ctx, const lash_params *prm, const lash_wi
     const uint32_t n = (uint32_t)(w1 - w0);
     const std::vector<uint8_t> fmt(n, (uint8_t)LASH_FMT_FASTA);
     return files_raw_staged(ctx, prm, nullptr, static_cast<const uint8_t *>(wi->buf.ptr), wi->h_off.data() + w0, fmt.data(), n, out_images);
+}
+
+void lash_tr_index_free(lash_ctx *ctx, lash_tr_index *ti)
+{
+    if (!ti) return;
+    if (ctx) {
+        (void)hipSetDevice(ctx->device);
+        if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
+    }
+    for (DevBuf *b : {&ti->buf, &ti->seg_off, &ti->rec_seg, &ti->out_base}) release(*b);
+    delete ti;
+}
+
+int lash_fasta_translate_device(lash_ctx *ctx, const uint8_t *d_raw, const uint64_t *file_off, uint32_t n_files, const lash_rec_index *ix,
+                                lash_tr_index **out)
+{
+    if (!ctx || !out || !file_off || !ix) return LASH_EINVAL;
+    *out = nullptr;
+    if (ix->device != ctx->device || n_files != ix->n_files || file_off[n_files] != ix->total) return LASH_EINVAL;   // another context or buffer
+    if (ix->total && !d_raw) return LASH_EINVAL;
+    (void)hipSetDevice(ctx->device);
+    const uint32_t tb = fasta_index_tile_bytes(), n_tiles = (uint32_t)((ix->total + tb - 1) / tb);
+    int rc;
+    if ((rc = reserve(ctx, ctx->fw_scratch, fasta_windows_scratch_bytes(n_tiles, ix->n)))) return rc;
+    uint8_t *scratch = static_cast<uint8_t *>(ctx->fw_scratch.ptr);
+    const uint64_t *d_start = static_cast<const uint64_t *>(ix->start.ptr);
+    lash_tr_index *ti = new (std::nothrow) lash_tr_index();
+    if (!ti) return LASH_ENOMEM;
+    ti->device = ctx->device;
+    ti->n = ix->n;
+    DevBuf tile_cnt{};
+    auto room = [&](DevBuf &b, size_t bytes) -> int {
+        HIPCHK(ctx, hipMalloc(&b.ptr, bytes));
+        b.cap = bytes;
+        return LASH_OK;
+    };
+    // every exit below this line leaves through done(): the stream is drained before anything queued on it loses its memory
+    auto done = [&](int code) -> int {
+        if (code != LASH_OK) { lash_tr_index_free(ctx, ti); (void)hipStreamSynchronize(ctx->stream); }
+        release(tile_cnt);
+        return code;
+    };
+    auto chk = [&](hipError_t e, const char *what) -> int {
+        return e == hipSuccess ? LASH_OK : fail(ctx, e == hipErrorOutOfMemory ? LASH_ENOMEM : LASH_EHIP, what, e);
+    };
+    const size_t tab = ((size_t)ix->n + 1) * 8;
+    if ((rc = room(ti->out_base, tab)) || (rc = room(ti->rec_seg, tab))) return done(rc);
+    uint64_t *d_out_base = static_cast<uint64_t *>(ti->out_base.ptr);
+    if ((rc = chk(launch_fasta_translate_sizes(d_raw, ix->total, d_start, ix->n, n_tiles, scratch, d_out_base, ctx->stream), "launch_fasta_translate_sizes")))
+        return done(rc);
+    ti->h_out_base.resize((size_t)ix->n + 1);
+    if ((rc = chk(hipMemcpyAsync(ti->h_out_base.data(), d_out_base, tab, hipMemcpyDeviceToHost, ctx->stream), "hipMemcpyAsync")) ||
+        (rc = chk(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize")))
+        return done(rc);
+    ti->bytes = ti->h_out_base[ix->n];
+    const size_t n_out_tiles = (size_t)((ti->bytes + fasta_translate_tile_bytes() - 1) / fasta_translate_tile_bytes());
+    if ((rc = room(ti->buf, (size_t)ti->bytes + 64)) || (rc = room(tile_cnt, (n_out_tiles + 2) * 8))) return done(rc);
+    uint8_t *d_buf = static_cast<uint8_t *>(ti->buf.ptr);
+    uint64_t *d_tile = static_cast<uint64_t *>(tile_cnt.ptr);
+    if ((rc = chk(hipMemsetAsync(d_buf + ti->bytes, 0, 64, ctx->stream), "hipMemsetAsync")) ||     // (the slack lanes of the sketch kernel may load)
+        (rc = chk(launch_fasta_translate_write(d_raw, ix->total, d_start, ix->n, n_tiles, scratch, d_out_base, ti->bytes, d_buf, d_tile, ctx->stream),
+                  "launch_fasta_translate_write")) ||
+        (rc = chk(hipMemcpyAsync(&ti->n_seg, d_tile + n_out_tiles, 8, hipMemcpyDeviceToHost, ctx->stream), "hipMemcpyAsync")) ||
+        (rc = chk(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize")))
+        return done(rc);
+    if ((rc = room(ti->seg_off, ((size_t)ti->n_seg + 1) * 8))) return done(rc);
+    ti->h_rec_seg.resize((size_t)ix->n + 1);
+    if ((rc = chk(launch_fasta_translate_segments(d_buf, ti->bytes, d_tile, d_out_base, ix->n, ti->n_seg, static_cast<uint64_t *>(ti->seg_off.ptr),
+                                                  static_cast<uint64_t *>(ti->rec_seg.ptr), ctx->stream), "launch_fasta_translate_segments")) ||
+        (rc = chk(hipMemcpyAsync(ti->h_rec_seg.data(), ti->rec_seg.ptr, tab, hipMemcpyDeviceToHost, ctx->stream), "hipMemcpyAsync")) ||
+        (rc = chk(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize")))
+        return done(rc);
+    *out = ti;
+    return done(LASH_OK);
+}
+
+int lash_fasta_translate(lash_ctx *ctx, const uint8_t *raw, const uint64_t *file_off, uint32_t n_files, const lash_rec_index *ix, lash_tr_index **out)
+{
+    if (!ctx || !out || !file_off || !ix) return LASH_EINVAL;
+    *out = nullptr;
+    if (ix->device != ctx->device || n_files != ix->n_files || file_off[n_files] != ix->total) return LASH_EINVAL;
+    if (ix->total && !raw) return LASH_EINVAL;
+    if (ix->raw.ptr && ix->h_raw == raw)                           // the index holds these bytes on the device
+        return lash_fasta_translate_device(ctx, static_cast<const uint8_t *>(ix->raw.ptr), file_off, n_files, ix, out);
+    (void)hipSetDevice(ctx->device);
+    int rc;
+    if ((rc = reserve(ctx, ctx->st_seq, ix->total + 64))) return rc;
+    if (ix->total) HIPCHK(ctx, hipMemcpyAsync(ctx->st_seq.ptr, raw, ix->total, hipMemcpyHostToDevice, ctx->stream));
+    // (the call drains the stream before it returns: the context's staging buffer is free again)
+    return lash_fasta_translate_device(ctx, static_cast<const uint8_t *>(ctx->st_seq.ptr), file_off, n_files, ix, out);
+}
+
+uint64_t lash_tr_index_n_segments(const lash_tr_index *ti) { return ti ? ti->n_seg : 0; }
+uint64_t lash_tr_index_bytes(const lash_tr_index *ti) { return ti ? ti->bytes : 0; }
+const uint8_t *lash_tr_index_buffer_device(const lash_tr_index *ti) { return ti ? static_cast<const uint8_t *>(ti->buf.ptr) : nullptr; }
+
+static int tr_copy(lash_ctx *ctx, const lash_tr_index *ti, const DevBuf &b, void *dst, size_t bytes)
+{
+    if (!ctx || !ti || !dst || ctx->device != ti->device) return LASH_EINVAL;
+    (void)hipSetDevice(ctx->device);
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    if (bytes) HIPCHK(ctx, hipMemcpy(dst, b.ptr, bytes, hipMemcpyDeviceToHost));
+    return LASH_OK;
+}
+
+int lash_tr_index_seg_off(lash_ctx *ctx, const lash_tr_index *ti, uint64_t *out) { return tr_copy(ctx, ti, ti ? ti->seg_off : DevBuf{}, out, ti ? ((size_t)ti->n_seg + 1) * 8 : 0); }
+int lash_tr_index_rec_seg(lash_ctx *ctx, const lash_tr_index *ti, uint64_t *out) { return tr_copy(ctx, ti, ti ? ti->rec_seg : DevBuf{}, out, ti ? ((size_t)ti->n + 1) * 8 : 0); }
+
+int lash_sketch_translated(lash_ctx *ctx, const lash_params *prm, const lash_tr_index *ti, const uint64_t *group_rec_off, uint32_t n_groups,
+                           uint8_t *out_images)
+{
+    if (!ctx || !prm || !ti || !group_rec_off || (n_groups && !out_images) || ti->device != ctx->device) return LASH_EINVAL;
+    lash_params p = *prm;
+    p.flags |= LASH_F_AMINO;
+    int rc = lash_params_check(&p);                                // k 1..12 among the rest
+    if (rc) return rc;
+    // group g = records [group_rec_off[g], group_rec_off[g + 1]): its segments and bytes are contiguous, a record starts at a segment boundary
+    std::vector<uint64_t> gseg((size_t)n_groups + 1), gbyte((size_t)n_groups + 1);
+    for (uint32_t g = 0; g <= n_groups; ++g) {
+        if (group_rec_off[g] > ti->n || (g && group_rec_off[g] < group_rec_off[g - 1])) return LASH_EINVAL;
+        gseg[g] = ti->h_rec_seg[group_rec_off[g]];
+        gbyte[g] = ti->h_out_base[group_rec_off[g]];
+        if (g && gseg[g] - gseg[g - 1] > 0xFFFFFFFFull) return LASH_ELIMIT;
+    }
+    if (n_groups == 0) return LASH_OK;
+    (void)hipSetDevice(ctx->device);
+    const size_t img_bytes = (size_t)n_groups * image_bytes(ctx->layout, p.algo, p.p);
+    if ((rc = reserve(ctx, ctx->st_img, img_bytes + 64))) return rc;
+    if (p.flags & LASH_F_ACCUMULATE) HIPCHK(ctx, hipMemcpyAsync(ctx->st_img.ptr, out_images, img_bytes, hipMemcpyHostToDevice, ctx->stream));
+    rc = lash_sketch_batch_device(ctx, &p, static_cast<const uint8_t *>(ti->buf.ptr), static_cast<const uint64_t *>(ti->seg_off.ptr), ti->n_seg, gseg.data(),
+                                  gbyte.data(), n_groups, static_cast<uint8_t *>(ctx->st_img.ptr));
+    if (rc) return rc;
+    HIPCHK(ctx, hipMemcpyAsync(out_images, ctx->st_img.ptr, img_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return LASH_OK;
 }
 
 }  // extern "C"

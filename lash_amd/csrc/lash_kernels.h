@@ -261,6 +261,28 @@ hipError_t launch_fasta_windows_count(const uint8_t *d_raw, uint64_t total, cons
 hipError_t launch_fasta_windows_write(const uint8_t *d_raw, uint64_t total, const uint64_t *d_start, uint32_t n_records, uint32_t n_tiles,
                                       uint64_t window, uint8_t *d_scratch, uint64_t n_windows, uint64_t *d_record, uint64_t *d_begin,
                                       uint64_t *d_length, uint64_t *d_off, uint8_t *d_out, hipStream_t stream);
+// what launch_fasta_windows_count left in d_scratch, for another stage that needs sequence coordinates (fasta_translate.hip): the lane words
+// (bits 0..15: which of the lane's 16 bytes are sequence bytes; bits 16..: sequence bytes of the tile before the lane), the exclusive scan
+// of the tiles' counts, and seq0[r] (n_records + 1): sequence bytes before record r, so L_r = seq0[r + 1] - seq0[r]
+void fasta_windows_rank_view(uint8_t *d_scratch, uint32_t n_tiles, uint32_t n_records, const uint32_t **d_lanes, const uint64_t **d_tile_base,
+                             const uint64_t **d_seq0);
+// one workgroup, in place: d_a[i] = d_a[0] + ... + d_a[i - 1] for i in [0, n], d_a[n] the total (n + 1 entries)
+hipError_t launch_scan_u64(uint64_t *d_a, uint32_t n, hipStream_t stream);
+// fasta_translate.hip: the six reading frames of every record of such an index, translated (NCBI table 1) into one buffer of residues
+// (`lash sketch --translate`; lash_fasta_translate).  Record r takes 6 + 2 * max(0, L_r - 2) bytes at out_base[r]: frames 0..5 in order, each
+// its residues and one '*'.  launch_fasta_translate_sizes queues the coordinate passes (it runs launch_fasta_windows_count on d_scratch,
+// fasta_windows_scratch_bytes) and the scan to d_out_base[n_records + 1]; once the caller has read the total B = out_base[n_records] and made
+// room (d_out: B + 64 bytes; d_tile_cnt: B / 4096 + 2 u64), launch_fasta_translate_write fills the buffer and leaves the scanned number of
+// break bytes ('*', 'X') per 4 KiB output tile in d_tile_cnt, the total n_seg in its last entry; with that read and d_seg_off (n_seg + 1) there,
+// launch_fasta_translate_segments writes seg_off (the position after every break byte, in order) and rec_seg[n_records + 1].
+uint32_t fasta_translate_tile_bytes();
+hipError_t launch_fasta_translate_sizes(const uint8_t *d_raw, uint64_t total, const uint64_t *d_start, uint32_t n_records, uint32_t n_tiles,
+                                        uint8_t *d_scratch, uint64_t *d_out_base, hipStream_t stream);
+hipError_t launch_fasta_translate_write(const uint8_t *d_raw, uint64_t total, const uint64_t *d_start, uint32_t n_records, uint32_t n_tiles,
+                                        uint8_t *d_scratch, const uint64_t *d_out_base, uint64_t out_bytes, uint8_t *d_out, uint64_t *d_tile_cnt,
+                                        hipStream_t stream);
+hipError_t launch_fasta_translate_segments(const uint8_t *d_out, uint64_t out_bytes, const uint64_t *d_tile_base, const uint64_t *d_out_base,
+                                           uint32_t n_records, uint64_t n_seg, uint64_t *d_seg_off, uint64_t *d_rec_seg, hipStream_t stream);
 
 struct FinalizeArgs {
     const uint8_t  *partials;

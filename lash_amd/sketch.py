@@ -258,6 +258,39 @@ class WindowIndex:
             pass
 
 
+class TranslatedIndex:
+    """Device-resident six-frame translation of the records of a RecordIndex, cut into segments at stops and ambiguous codons
+    (lash_tr_index*)."""
+
+    def __init__(self, ctx, handle, n_records):
+        self._ctx, self._h, self.n_records = ctx, handle, int(n_records)
+        self.n_segments = int(_lib.load().lash_tr_index_n_segments(handle))
+        self.nbytes = int(_lib.load().lash_tr_index_bytes(handle))
+
+    def arrays(self):
+        """(seg_off[n_segments + 1], rec_seg[n_records + 1]) u64, each one copy to the host"""
+        lib = _lib.load()
+        seg_off, rec_seg = np.zeros(self.n_segments + 1, np.uint64), np.zeros(self.n_records + 1, np.uint64)
+        self._ctx._check(lib.lash_tr_index_seg_off(self._ctx._h, self._h, seg_off.ctypes.data))
+        self._ctx._check(lib.lash_tr_index_rec_seg(self._ctx._h, self._h, rec_seg.ctypes.data))
+        return seg_off, rec_seg
+
+    @property
+    def device_ptr(self):
+        return _lib.load().lash_tr_index_buffer_device(self._h) or 0
+
+    def free(self):
+        if self._h:
+            _lib.load().lash_tr_index_free(self._ctx._h, self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
 class RecordIndex:
     """Device-resident record index of raw multi-FASTA bytes (lash_rec_index*)."""
 
@@ -515,6 +548,38 @@ class Context:
         out = np.zeros((max(int(w1) - int(w0), 0), self.image_bytes(prm.algo, prm.p)), dtype=np.uint8)
         self._check_einval(self._lib.lash_sketch_windows_raw(self._h, C.byref(prm), windows._h, int(w0), int(w1),
                                                              out.ctypes.data if out.size else None))
+        return out
+
+    def fasta_translate(self, raw, file_off, index, device=False, keep=False):
+        """lash_fasta_translate: the six reading frames of the records of `index` (a RecordIndex made from the same raw / file_off),
+        translated on the GPU and cut into segments at stops and ambiguous codons.  raw as for fasta_index.  Returns
+        (seg_off[n_segments + 1], rec_seg[n_records + 1]) u64; keep=True returns a TranslatedIndex (for sketch_translated) instead."""
+        off = np.ascontiguousarray(file_off, dtype=np.uint64)
+        if not device:
+            raw = np.frombuffer(raw, dtype=np.uint8) if isinstance(raw, (bytes, bytearray)) else np.ascontiguousarray(raw, dtype=np.uint8)
+            assert raw.size >= int(off[-1])
+        h = C.c_void_p()
+        fn = self._lib.lash_fasta_translate_device if device else self._lib.lash_fasta_translate
+        self._check_einval(fn(self._h, _ptr(raw) if int(off[-1]) else None, off.ctypes.data, len(off) - 1, index._h, C.byref(h)))
+        ti = TranslatedIndex(self, h, index.n_records)
+        if keep:
+            return ti
+        try:
+            return ti.arrays()
+        finally:
+            ti.free()
+
+    def sketch_translated(self, algo, k, p, seed, translated, group_rec_off=None, flags=0, out=None):
+        """lash_sketch_translated: one amino-acid image per group of records of a TranslatedIndex; group g = records
+        [group_rec_off[g], group_rec_off[g + 1]) (None: one group of all records).  out: images to union into (with F_ACCUMULATE).
+        Returns images[n_groups, image_bytes]."""
+        prm = self._params(algo, k, p, seed, flags)
+        goff = np.ascontiguousarray([0, translated.n_records] if group_rec_off is None else group_rec_off, dtype=np.uint64)
+        if out is None:
+            out = np.zeros((max(len(goff) - 1, 0), self.image_bytes(prm.algo, prm.p)), dtype=np.uint8)
+        assert out.dtype == np.uint8 and out.flags.c_contiguous
+        self._check_einval(self._lib.lash_sketch_translated(self._h, C.byref(prm), translated._h, goff.ctypes.data, max(len(goff) - 1, 0),
+                                                            out.ctypes.data if out.size else None))
         return out
 
     def sketch_records_raw(self, algo, k, p, seed, raw, file_off, index=None, r0=0, r1=None, flags=0):
