@@ -245,7 +245,7 @@ int      lash_sketch_records_raw(lash_ctx *ctx, const lash_params *prm, const ui
 
 /* One sketch per fixed-length WINDOW of every FASTA record (`lash sketch --window W`): which stretch of a chromosome is the prophage, which
  * part of a contig is the contaminant.  lash_fasta_windows cuts the records of an index (made from the same raw / file_off on the same
- * context) into windows on the device (fasta_windows.hip):
+ * context) into windows on the device (fasta_coords.hip, fasta_windows.hip):
  *   sequence bytes  of a record: the bytes after its header line's '\n' up to start[r + 1] that are neither '\n' nor '\r'; every other
  *                   byte counts (N, lower case, a stray '>').  Their 0-based rank in the record is the coordinate.
  *   windows         a record of L sequence bytes has ceil(L / window) of them, window j = coordinates [j * window, min(L, (j + 1) * window));
@@ -277,7 +277,7 @@ void     lash_win_index_free(lash_ctx *ctx, lash_win_index *windows);
 
 /* Six-frame PROTEIN sketches of nucleotide FASTA (`lash sketch --translate`): genomes too far apart for nucleotide k-mers are compared in protein
  * space, and a user with assemblies has no proteins.  lash_fasta_translate translates the records of an index (made from the same raw / file_off
- * on the same context) on the device (fasta_translate.hip) into one buffer the result owns until it is freed.  The rule does not depend on k:
+ * on the same context) on the device (fasta_coords.hip, fasta_translate.hip) into one buffer the result owns until it is freed.  The rule does not depend on k:
  *   sequence bytes  S[0..L) of a record: as for lash_fasta_windows (the bytes after the header line's LF that are neither LF nor CR)
  *   bases           ACGTacgt, case ignored (soft-masked sequence translates like any other); every other byte, N and U included, is no base
  *   frames          f = 0, 1, 2 read S from offset f; f = 3, 4, 5 read the reverse complement R[t] = comp(S[L - 1 - t]) from offset f - 3;

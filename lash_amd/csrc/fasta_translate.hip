@@ -1,9 +1,9 @@
 // fasta_translate.hip — six-frame translation of FASTA records, made on the device (`lash sketch --translate`; lash_fasta_translate[_device]).
-// fasta_index.hip finds the records and fasta_windows.hip's count passes give every sequence byte its coordinate; this stage writes the six
+// fasta_index.hip finds the records and fasta_coords.hip gives every sequence byte its coordinate; this stage writes the six
 // reading frames of every record as residues into one buffer, cut into segments at stops and ambiguous codons, so that the amino-acid
 // route (LASH_F_AMINO, aa_sketch_kernel) sketches them unchanged with the segments as its records.
 //
-// Rules (k-independent): the sequence bytes S[0..L) of a record are those of fasta_windows.hip.  A base is one of ACGTacgt, every other byte
+// Rules (k-independent): the sequence bytes S[0..L) of a record are those of fasta_coords.hip.  A base is one of ACGTacgt, every other byte
 // is no base.  Frames 0, 1, 2 read S from offset f; frames 3, 4, 5 read the reverse complement R[t] = comp(S[L - 1 - t]) from offset f - 3;
 // frame f has n_f = max(0, (L - o) / 3) codons, a trailing partial codon is dropped.  Three bases translate by NCBI table 1 ('*' for a stop),
 // a codon with a no-base gives 'X'; '*' and 'X' are break bytes.  Record r takes 6 + 2 * max(0, L - 2) bytes at out_base[r]: its frames in
@@ -11,7 +11,7 @@
 // s-th break; rec_seg[r] = the first segment of record r (out_base[r] is always a segment boundary: the byte before it ends a frame).
 //
 // Passes (no atomics, nothing depends on scheduling):
-//   1. launch_fasta_windows_count   lane words, tile bases and seq0[r] of fasta_windows.hip: the coordinate of every sequence byte
+//   1. launch_fasta_coords          lane words, tile bases and seq0[r]: the coordinate of every sequence byte
 //   2. tr_size_kernel + scan        the closed-form record sizes, scanned to out_base[r]; the host reads the total B and makes room
 //   3. tr_term_kernel               one thread per record: the six frame terminators
 //   4. tr_map_kernel                per 4 KiB tile of the INPUT, 16 bytes per lane: the sequence byte at coordinate i >= 2 completes the codon
@@ -24,10 +24,9 @@
 #include <hip/hip_runtime.h>
 
 #include "lash_kernels.h"
+#include "text_tiles.h"
 
 namespace lash {
-
-constexpr uint32_t TR_TILE = 4096;           // bytes per tile = 256 threads x 16, input (fasta_index.hip's) and output alike
 
 // base order T, C, A, G: the order of the codon table below; the complement of code x is x ^ 2
 __device__ const uint8_t TR_CODON[65] = "FFLLSSSSYY**CC*WLLLLPPPPHHQQRRRRIIIMTTTTNNKKSSRRVVVVAAAADDEEGGGG";
@@ -43,22 +42,6 @@ __device__ __forceinline__ uint32_t tr_base_code(uint32_t byte)
 __device__ __forceinline__ uint8_t tr_residue(const uint8_t *tab, uint32_t a, uint32_t b, uint32_t c)
 {
     return (a | b | c) & 4u ? (uint8_t)'X' : tab[(a << 4) | (b << 2) | c];
-}
-
-// number of j in [0, n) with a[j] <= x (a ascending)
-__device__ __forceinline__ uint32_t tr_count_le(const uint64_t *a, uint32_t n, uint64_t x)
-{
-    uint32_t lo = 0, hi = n;
-    while (lo < hi) { const uint32_t mid = lo + (hi - lo) / 2; if (a[mid] <= x) lo = mid + 1; else hi = mid; }
-    return lo;
-}
-
-// the record of byte `at` (start[0] == 0): one search per tile, the same for every lane, then one among the records that begin inside the tile
-__device__ __forceinline__ uint32_t tr_record_of(const uint64_t *start, uint32_t n, uint64_t tile0, uint64_t at)
-{
-    const uint32_t rt = tr_count_le(start, n, tile0) - 1u;
-    const uint32_t in_tile = tr_count_le(start + rt + 1u, n - rt - 1u, tile0 + TR_TILE - 1u);
-    return rt + tr_count_le(start + rt + 1u, in_tile, at);
 }
 
 // where the frames of a record of L sequence bytes start inside its 6 + 2 * max(0, L - 2) bytes, and how many codons each holds
@@ -100,25 +83,15 @@ __global__ void __launch_bounds__(256) tr_map_kernel(const uint8_t *__restrict__
     __shared__ uint8_t tab[64];
     if (threadIdx.x < 64u) tab[threadIdx.x] = TR_CODON[threadIdx.x];
     __syncthreads();
-    const uint64_t tile0 = (uint64_t)blockIdx.x * TR_TILE, at = tile0 + threadIdx.x * 16ull;
+    const uint64_t tile0 = (uint64_t)blockIdx.x * TEXT_TILE, at = tile0 + threadIdx.x * 16ull;
     const uint32_t word = lanes[(uint64_t)blockIdx.x * 256u + threadIdx.x];
     uint32_t m = word & 0xFFFFu;
     if (!m) return;                                                 // (a lane past the end of the buffer has no bit set)
-    uint64_t lo = 0, hi = 0;
-    if (total - at >= 16u) {
-        uint4 q;
-        __builtin_memcpy(&q, raw + at, 16);
-        lo = q.x | ((uint64_t)q.y << 32);
-        hi = q.z | ((uint64_t)q.w << 32);
-    } else {
-        for (uint32_t i = 0; i < (uint32_t)(total - at); ++i) {
-            const uint64_t b = raw[at + i];
-            if (i < 8) lo |= b << (8u * i); else hi |= b << (8u * (i - 8u));
-        }
-    }
+    uint64_t lo, hi;
+    (void)lane_load(raw, at, total, lo, hi);
     const uint64_t g = tile_base[blockIdx.x] + (word >> 16);        // rank of the lane's first sequence byte in the whole buffer
     const uint32_t first = (uint32_t)__builtin_ctz(m);
-    uint32_t r = tr_record_of(start, n, tile0, at + first);
+    uint32_t r = record_of(start, n, tile0, at + first);
     uint64_t i = g - seq0[r], L = seq0[r + 1u] - seq0[r], base = out_base[r];
     TrFrames fr(L);
     // the two sequence bytes before the lane's first: the same record's, behind nothing but line ends
@@ -162,44 +135,20 @@ __global__ void __launch_bounds__(256) tr_map_kernel(const uint8_t *__restrict__
     }
 }
 
-// bit i: byte i of the 8 in x equals c
-__device__ __forceinline__ uint32_t tr_eq_mask8(uint64_t x, uint8_t c)
-{
-    const uint64_t z = x ^ (0x0101010101010101ull * c);
-    const uint64_t nz = ((z & 0x7F7F7F7F7F7F7F7Full) + 0x7F7F7F7F7F7F7F7Full) | z;
-    return (uint32_t)((((~nz >> 7) & 0x0101010101010101ull) * 0x0102040810204080ull) >> 56);
-}
-
-// which of the lane's 16 output bytes are break bytes (the buffer is readable for 64 bytes past `bytes`)
+// which of the lane's 16 output bytes are break bytes
 __device__ __forceinline__ uint32_t tr_break_mask(const uint8_t *__restrict__ out, uint64_t bytes, uint64_t at)
 {
-    if (at >= bytes) return 0u;
-    const uint4 q = *reinterpret_cast<const uint4 *>(out + at);
-    const uint64_t lo = q.x | ((uint64_t)q.y << 32), hi = q.z | ((uint64_t)q.w << 32);
-    const uint32_t valid = bytes - at >= 16u ? 0xFFFFu : (1u << (uint32_t)(bytes - at)) - 1u;
-    return (tr_eq_mask8(lo, '*') | (tr_eq_mask8(hi, '*') << 8) | tr_eq_mask8(lo, 'X') | (tr_eq_mask8(hi, 'X') << 8)) & valid;
-}
-
-// exclusive prefix of `mine` over the 256 threads of the workgroup; *sum = their total
-__device__ __forceinline__ uint32_t tr_block_scan(uint32_t mine, uint32_t *wsum, uint32_t *sum)
-{
-    uint32_t incl = mine;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) { const uint32_t v = __shfl_up(incl, d, 64); if ((int)(threadIdx.x & 63u) >= d) incl += v; }
-    if ((threadIdx.x & 63u) == 63u) wsum[threadIdx.x >> 6] = incl;
-    __syncthreads();
-    uint32_t pre = incl - mine;
-    for (uint32_t w = 0; w < (threadIdx.x >> 6); ++w) pre += wsum[w];
-    *sum = wsum[0] + wsum[1] + wsum[2] + wsum[3];
-    return pre;
+    uint64_t lo, hi;
+    const uint32_t valid = lane_load(out, at, bytes, lo, hi);
+    return (eq_mask16(lo, hi, '*') | eq_mask16(lo, hi, 'X')) & valid;
 }
 
 __global__ void __launch_bounds__(256) tr_count_kernel(const uint8_t *__restrict__ out, uint64_t bytes, uint64_t *__restrict__ tile_cnt)
 {
     __shared__ uint32_t wsum[4];
-    const uint32_t m = tr_break_mask(out, bytes, (uint64_t)blockIdx.x * TR_TILE + threadIdx.x * 16ull);
+    const uint32_t m = tr_break_mask(out, bytes, (uint64_t)blockIdx.x * TEXT_TILE + threadIdx.x * 16ull);
     uint32_t sum;
-    (void)tr_block_scan((uint32_t)__builtin_popcount(m), wsum, &sum);
+    (void)block_scan_256((uint32_t)__builtin_popcount(m), wsum, &sum);
     if (threadIdx.x == 0u) tile_cnt[blockIdx.x] = sum;
 }
 
@@ -207,9 +156,9 @@ __global__ void __launch_bounds__(256) tr_segoff_kernel(const uint8_t *__restric
                                                         uint64_t *__restrict__ seg_off)
 {
     __shared__ uint32_t wsum[4];
-    const uint64_t at = (uint64_t)blockIdx.x * TR_TILE + threadIdx.x * 16ull;
+    const uint64_t at = (uint64_t)blockIdx.x * TEXT_TILE + threadIdx.x * 16ull;
     uint32_t m = tr_break_mask(out, bytes, at), sum;
-    uint64_t rank = tile_base[blockIdx.x] + tr_block_scan((uint32_t)__builtin_popcount(m), wsum, &sum);
+    uint64_t rank = tile_base[blockIdx.x] + block_scan_256((uint32_t)__builtin_popcount(m), wsum, &sum);
     while (m) {
         seg_off[++rank] = at + (uint32_t)__builtin_ctz(m) + 1u;     // the s-th break byte ends segment s: seg_off[s + 1]
         m &= m - 1u;
@@ -227,40 +176,34 @@ __global__ void __launch_bounds__(256) tr_recseg_kernel(const uint64_t *__restri
     rec_seg[r] = lo;
 }
 
-uint32_t fasta_translate_tile_bytes() { return TR_TILE; }
-
 hipError_t launch_fasta_translate_sizes(const uint8_t *d_raw, uint64_t total, const uint64_t *d_start, uint32_t n_records, uint32_t n_tiles,
                                         uint8_t *d_scratch, uint64_t *d_out_base, hipStream_t stream)
 {
-    const uint64_t *d_s = nullptr, *d_n = nullptr, *tile_base = nullptr, *seq0 = nullptr;
-    const uint32_t *lanes = nullptr;
-    // (one "window" per record with a sequence: only the coordinates are wanted)
-    hipError_t e = launch_fasta_windows_count(d_raw, total, d_start, n_records, n_tiles, ~0ull >> 1, d_scratch, &d_s, &d_n, stream);
+    const hipError_t e = launch_fasta_coords(d_raw, total, d_start, n_records, n_tiles, d_scratch, stream);
     if (e != hipSuccess) return e;
-    fasta_windows_rank_view(d_scratch, n_tiles, n_records, &lanes, &tile_base, &seq0);
-    hipLaunchKernelGGL(tr_size_kernel, dim3(n_records / 256u + 1u), dim3(256), 0, stream, seq0, n_records, d_out_base);
-    return launch_scan_u64(d_out_base, n_records, stream);
+    const FastaCoords c = fasta_coords_view(d_scratch, n_tiles, n_records);
+    hipLaunchKernelGGL(tr_size_kernel, dim3(n_records / 256u + 1u), dim3(256), 0, stream, c.seq0, n_records, d_out_base);
+    return launch_tile_scan(d_out_base, d_out_base, n_records, stream);
 }
 
 hipError_t launch_fasta_translate_write(const uint8_t *d_raw, uint64_t total, const uint64_t *d_start, uint32_t n_records, uint32_t n_tiles,
                                         uint8_t *d_scratch, const uint64_t *d_out_base, uint64_t out_bytes, uint8_t *d_out, uint64_t *d_tile_cnt,
                                         hipStream_t stream)
 {
-    const uint64_t *tile_base = nullptr, *seq0 = nullptr;
-    const uint32_t *lanes = nullptr;
-    fasta_windows_rank_view(d_scratch, n_tiles, n_records, &lanes, &tile_base, &seq0);
-    hipLaunchKernelGGL(tr_term_kernel, dim3(n_records / 256u + 1u), dim3(256), 0, stream, seq0, d_out_base, n_records, d_out);
+    const FastaCoords c = fasta_coords_view(d_scratch, n_tiles, n_records);
+    hipLaunchKernelGGL(tr_term_kernel, dim3(n_records / 256u + 1u), dim3(256), 0, stream, c.seq0, d_out_base, n_records, d_out);
     if (n_tiles && n_records)
-        hipLaunchKernelGGL(tr_map_kernel, dim3(n_tiles), dim3(256), 0, stream, d_raw, total, d_start, n_records, lanes, tile_base, seq0, d_out_base, d_out);
-    const uint32_t n_out_tiles = (uint32_t)((out_bytes + TR_TILE - 1u) / TR_TILE);
+        hipLaunchKernelGGL(tr_map_kernel, dim3(n_tiles), dim3(256), 0, stream, d_raw, total, d_start, n_records, c.lanes, c.tile_base, c.seq0, d_out_base,
+                           d_out);
+    const uint32_t n_out_tiles = (uint32_t)((out_bytes + TEXT_TILE - 1u) / TEXT_TILE);
     if (n_out_tiles) hipLaunchKernelGGL(tr_count_kernel, dim3(n_out_tiles), dim3(256), 0, stream, d_out, out_bytes, d_tile_cnt);
-    return launch_scan_u64(d_tile_cnt, n_out_tiles, stream);
+    return launch_tile_scan(d_tile_cnt, d_tile_cnt, n_out_tiles, stream);
 }
 
 hipError_t launch_fasta_translate_segments(const uint8_t *d_out, uint64_t out_bytes, const uint64_t *d_tile_base, const uint64_t *d_out_base,
                                            uint32_t n_records, uint64_t n_seg, uint64_t *d_seg_off, uint64_t *d_rec_seg, hipStream_t stream)
 {
-    const uint32_t n_out_tiles = (uint32_t)((out_bytes + TR_TILE - 1u) / TR_TILE);
+    const uint32_t n_out_tiles = (uint32_t)((out_bytes + TEXT_TILE - 1u) / TEXT_TILE);
     hipError_t e = hipMemsetAsync(d_seg_off, 0, 8, stream);         // seg_off[0] = 0
     if (e != hipSuccess) return e;
     if (n_out_tiles) hipLaunchKernelGGL(tr_segoff_kernel, dim3(n_out_tiles), dim3(256), 0, stream, d_out, out_bytes, d_tile_base, d_seg_off);

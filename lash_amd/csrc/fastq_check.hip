@@ -19,30 +19,18 @@
 #include <algorithm>
 
 #include "lash_kernels.h"
+#include "text_tiles.h"
 
 namespace lash {
 
-constexpr uint32_t FQ_BLOCK = 4096;          // bytes per block = 256 threads x 16
 constexpr uint32_t NONE = 0xFFFFFFFFu;
 
-__device__ __forceinline__ uint32_t nl_mask16(const uint8_t *p, uint64_t avail)
+// bit i: byte i of the 16 at file position `at` is '\n' (bytes at or beyond the file's end never are)
+__device__ __forceinline__ uint32_t nl_mask16(const uint8_t *file, uint64_t at, uint64_t len)
 {
-    // bit i: byte i of the 16 at p is '\n' (bytes at or beyond `avail` never are)
-    uint32_t m = 0;
-    if (avail >= 16) {
-        uint4 q;
-        __builtin_memcpy(&q, p, 16);
-        const uint32_t w[4] = {q.x, q.y, q.z, q.w};
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const uint32_t z = w[j] ^ 0x0A0A0A0Au;
-            const uint32_t nz = ((z & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | z;                 // high bit of a byte set <=> the byte is non-zero
-            m |= ((((~nz >> 7) & 0x01010101u) * 0x01020408u) >> 24 & 0xFu) << (4 * j);
-        }
-    } else {
-        for (uint32_t i = 0; i < (uint32_t)avail; ++i) m |= (p[i] == 0x0Au ? 1u : 0u) << i;
-    }
-    return m;
+    uint64_t lo, hi;
+    const uint32_t valid = lane_load(file, at, len, lo, hi);
+    return eq_mask16(lo, hi, '\n') & valid;
 }
 
 __device__ __forceinline__ uint32_t file_of_block(const FqFile *files, uint32_t n_files, uint32_t b)
@@ -55,12 +43,12 @@ __device__ __forceinline__ uint32_t file_of_block(const FqFile *files, uint32_t 
 __global__ void __launch_bounds__(256) fq_count_kernel(const uint8_t *__restrict__ raw, const FqFile *__restrict__ files, uint32_t n_files,
                                                        uint32_t *__restrict__ cnt, uint32_t *__restrict__ last3)
 {
-    __shared__ uint32_t bm[FQ_BLOCK / 32];
+    __shared__ uint32_t bm[TEXT_TILE / 32];
     __shared__ uint32_t n_sh;
     const uint32_t b = blockIdx.x, f = file_of_block(files, n_files, b);
     const FqFile ff = files[f];
-    const uint64_t boff = (uint64_t)(b - ff.block0) * FQ_BLOCK, at = boff + threadIdx.x * 16ull;
-    const uint32_t m = at < ff.len ? nl_mask16(raw + ff.off + at, ff.len - at) : 0u;
+    const uint64_t boff = (uint64_t)(b - ff.block0) * TEXT_TILE, at = boff + threadIdx.x * 16ull;
+    const uint32_t m = nl_mask16(raw + ff.off, at, ff.len);
     if ((threadIdx.x & 1u) == 0u) bm[threadIdx.x >> 1] = 0;
     if (threadIdx.x == 0) n_sh = 0;
     __syncthreads();
@@ -68,7 +56,7 @@ __global__ void __launch_bounds__(256) fq_count_kernel(const uint8_t *__restrict
     __syncthreads();
     if (threadIdx.x == 0) {
         uint32_t found = 0, pos[3] = {NONE, NONE, NONE};
-        for (int w = FQ_BLOCK / 32 - 1; w >= 0 && found < 3; --w) {
+        for (int w = TEXT_TILE / 32 - 1; w >= 0 && found < 3; --w) {
             uint32_t x = bm[w];
             while (x && found < 3) { const uint32_t i = 31u - (uint32_t)__builtin_clz(x); pos[found++] = (uint32_t)boff + 32u * (uint32_t)w + i; x &= ~(1u << i); }
         }
@@ -83,15 +71,7 @@ __global__ void __launch_bounds__(1024) fq_scan_kernel(const FqFile *__restrict_
 {
     __shared__ uint32_t part[1024];
     const FqFile ff = files[blockIdx.x];
-    const uint32_t n = ff.n_blocks, per = (n + 1023u) / 1024u, b0 = threadIdx.x * per, b1 = min(n, b0 + per);
-    uint32_t s = 0;
-    for (uint32_t b = b0; b < b1; ++b) s += cnt[ff.block0 + b];
-    part[threadIdx.x] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) { uint32_t acc = 0; for (uint32_t i = 0; i < 1024; ++i) { const uint32_t v = part[i]; part[i] = acc; acc += v; } total[blockIdx.x] = acc; }
-    __syncthreads();
-    uint32_t acc = part[threadIdx.x];
-    for (uint32_t b = b0; b < b1; ++b) { base[ff.block0 + b] = acc; acc += cnt[ff.block0 + b]; }
+    run_scan_1024(cnt + ff.block0, base + ff.block0, ff.n_blocks, part, total + blockIdx.x);
 }
 
 __global__ void __launch_bounds__(256) fq_check_kernel(const uint8_t *__restrict__ raw, const FqFile *__restrict__ files, uint32_t n_files,
@@ -99,14 +79,14 @@ __global__ void __launch_bounds__(256) fq_check_kernel(const uint8_t *__restrict
                                                        const uint32_t *__restrict__ base, const uint32_t *__restrict__ total,
                                                        uint32_t *__restrict__ file_err)
 {
-    __shared__ uint32_t bm[FQ_BLOCK / 32];
+    __shared__ uint32_t bm[TEXT_TILE / 32];
     __shared__ uint32_t wsum[4];
     const uint32_t b = blockIdx.x, f = file_of_block(files, n_files, b);
     const FqFile ff = files[f];
     const uint8_t *fp = raw + ff.off;
-    const uint32_t lb = b - ff.block0, boff = lb * FQ_BLOCK;
+    const uint32_t lb = b - ff.block0, boff = lb * TEXT_TILE;
     const uint64_t at = (uint64_t)boff + threadIdx.x * 16ull;
-    const uint32_t m = at < ff.len ? nl_mask16(fp + at, ff.len - at) : 0u;
+    const uint32_t m = nl_mask16(fp, at, ff.len);
     if ((threadIdx.x & 1u) == 0u) bm[threadIdx.x >> 1] = 0;
     __syncthreads();
     if (m) atomicOr(&bm[threadIdx.x >> 1], m << (16u * (threadIdx.x & 1u)));
@@ -116,7 +96,7 @@ __global__ void __launch_bounds__(256) fq_check_kernel(const uint8_t *__restrict
         uint32_t q = pos - boff;                                             // bits [0, q) of this block are before pos
         if (pos >= boff) {
             int w = (int)(q >> 5);
-            uint32_t x = w < (int)(FQ_BLOCK / 32) ? bm[w] & ((q & 31u) ? ((1u << (q & 31u)) - 1u) : 0u) : 0u;
+            uint32_t x = w < (int)(TEXT_TILE / 32) ? bm[w] & ((q & 31u) ? ((1u << (q & 31u)) - 1u) : 0u) : 0u;
             for (;;) {
                 if (x) return boff + 32u * (uint32_t)w + 31u - (uint32_t)__builtin_clz(x);
                 if (--w < 0) break;
@@ -125,12 +105,12 @@ __global__ void __launch_bounds__(256) fq_check_kernel(const uint8_t *__restrict
         }
         // earlier blocks: the nearest newline before pos in block j < lb is last3[j][0] — unless pos itself lies in an earlier block
         // (a walk that has already left this block), then the entries of that block that are below pos
-        for (int64_t j = (int64_t)min(lb, pos / FQ_BLOCK + 1u) - 1; j >= 0; --j) {
+        for (int64_t j = (int64_t)min(lb, pos / TEXT_TILE + 1u) - 1; j >= 0; --j) {
             const uint64_t t = 3ull * (ff.block0 + (uint32_t)j);
             for (int e = 0; e < 3; ++e) { const uint32_t v = last3[t + e]; if (v != NONE && v < pos) return v; }
-            if (cnt[ff.block0 + (uint32_t)j] > 3u && (uint32_t)j == pos / FQ_BLOCK) {
+            if (cnt[ff.block0 + (uint32_t)j] > 3u && (uint32_t)j == pos / TEXT_TILE) {
                 // more than three newlines in the block that holds pos, all three known ones at or after pos: scan its bytes (rare)
-                for (uint32_t i = pos; i > (uint32_t)j * FQ_BLOCK; --i) if (fp[i - 1] == 0x0Au) return i - 1;
+                for (uint32_t i = pos; i > (uint32_t)j * TEXT_TILE; --i) if (fp[i - 1] == 0x0Au) return i - 1;
             }
         }
         return NONE;
@@ -150,15 +130,10 @@ __global__ void __launch_bounds__(256) fq_check_kernel(const uint8_t *__restrict
         if (stripped_len(n0 + 1u, n1) != stripped_len(n2 + 1u, qend)) file_err[ff.index] = 1u;
     };
     // line number of a lane's first newline = newlines of the file before it: block base + waves before + lanes before
-    const uint32_t mine = (uint32_t)__builtin_popcount(m);
-    uint32_t incl = mine;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) { const uint32_t v = __shfl_up(incl, d, 64); if ((int)(threadIdx.x & 63u) >= d) incl += v; }
-    if ((threadIdx.x & 63u) == 63u) wsum[threadIdx.x >> 6] = incl;
-    __syncthreads();
+    uint32_t sum;
+    const uint32_t pre = block_scan_256((uint32_t)__builtin_popcount(m), wsum, &sum);
     if (m) {
-        uint32_t before = base[b] + incl - mine;
-        for (uint32_t w = 0; w < (threadIdx.x >> 6); ++w) before += wsum[w];
+        uint32_t before = base[b] + pre;
         const uint32_t q = threadIdx.x * 16u;
         uint32_t mm = m;
         while (mm) {
@@ -190,6 +165,5 @@ hipError_t launch_fastq_check(const uint8_t *d_raw, const FqFile *d_files, uint3
 }
 
 size_t fastq_check_scratch_words(uint32_t n_files, uint32_t n_blocks) { return (size_t)n_blocks * 5 + ((n_files + 3u) & ~3u) + 16; }
-uint32_t fastq_check_block_bytes() { return FQ_BLOCK; }
 
 }  // namespace lash

@@ -251,7 +251,7 @@ void lash_ctx_destroy(lash_ctx *ctx)
     release(ctx->sole_state);
     for (DevBuf *b : {&ctx->items, &ctx->item_begin, &ctx->item_kmers, &ctx->partials, &ctx->gregs, &ctx->counter, &ctx->st_seq, &ctx->st_rec,
                       &ctx->st_img, &ctx->hll_flags, &ctx->ec_ref, &ctx->ec_qry, &ctx->ec_x, &ctx->ec_card, &ctx->wf_scratch, &ctx->wf_out, &ctx->top_buf, &ctx->hll_bm_ref,
-                      &ctx->hll_bm_qry, &ctx->hll_lohi, &ctx->fa_off, &ctx->fa_scratch, &ctx->fw_scratch, &ctx->kf_keep})
+                      &ctx->hll_bm_qry, &ctx->hll_lohi, &ctx->fa_off, &ctx->fa_scratch, &ctx->fc_scratch, &ctx->kf_keep})
         release(*b);
     {
         lash_packed &sc = ctx->scratch;

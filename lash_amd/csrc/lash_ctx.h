@@ -172,8 +172,9 @@ struct lash_ctx {
     bool last_sole_only = false;         // the last sketch call ran on that kernel alone (lash_timing::bases_last comes from its census)
     DevBuf st_seq, st_rec, st_img;       // staging for the synchronous host-buffer entries (files_raw, merge, pair statistics)
     DevBuf kf_keep;                      // lash_sketch_files_raw_filtered: the batch's keep bits, laid out like the packed batch's brk
-    DevBuf fa_off, fa_scratch;           // lash_fasta_index[_device]: the file offsets; [masks | tile counts | tile bases] of fasta_index.hip
-    DevBuf fw_scratch;                   // lash_fasta_windows[_device]: [lane words | tile bases | seq_begin | seq0 | win_base] of fasta_windows.hip
+    DevBuf fa_off, fa_scratch;           // lash_fasta_index[_device]: the file offsets; [masks | tile counts | tile bases | flag] of fasta_index.hip
+    DevBuf fc_scratch;                   // lash_fasta_windows / _translate[_device]: the sequence coordinates [lane words | tile bases | seq_begin |
+                                         // seq0] of fasta_coords.hip and, behind them, the windows stage's own part [win_base] (fasta_windows.hip)
     // lash_sketch_batch[_async]: two staging slots and two copy streams, so that the H2D copy of batch n+1 and the D2H copy of
     // batch n-1 run while the kernels of batch n do (PCIe Gen5 moves 1 B/base: the host-buffer entry is link-bound)
     struct AsyncSlot { DevBuf seq, rec, img; hipEvent_t h2d = nullptr, kern = nullptr, d2h = nullptr; bool busy = false; };

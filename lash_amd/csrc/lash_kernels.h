@@ -231,7 +231,7 @@ hipError_t launch_brk_bytes(const GenomeDesc *genomes, const uint64_t *rec_off, 
 struct FqFile {
     uint64_t off;        // first byte of the file in the raw buffer
     uint64_t len;        // bytes (< 4 GiB)
-    uint32_t block0;     // index of the file's first 4 KiB block among all FASTQ blocks of the call
+    uint32_t block0;     // index of the file's first 4 KiB block (TEXT_TILE, text_tiles.h) among all FASTQ blocks of the call
     uint32_t n_blocks;
     uint32_t index;      // which file_err word to set
     uint32_t pad;
@@ -239,21 +239,33 @@ struct FqFile {
 hipError_t launch_fastq_check(const uint8_t *d_raw, const FqFile *d_files, uint32_t n_files, uint32_t n_blocks, uint32_t *d_scratch,
                               uint32_t *d_file_err, hipStream_t stream);
 size_t fastq_check_scratch_words(uint32_t n_files, uint32_t n_blocks);
-uint32_t fastq_check_block_bytes();
 // fasta_index.hip: the record index of raw multi-FASTA bytes (lash_fasta_index).  launch_fasta_mark queues the mark and scan kernels
 // and says where the record count and the "a file does not begin with '>'" flag will stand (two words, device); once the caller has
 // read the count and made room, launch_fasta_write queues the ordered write of start[n_records + 1] / file[] and the id_len[] walk.
-// d_file_off: n_files + 1 offsets, ascending from 0; d_scratch: fasta_index_scratch_bytes(n_tiles), n_tiles = tiles of `total` bytes.
-uint32_t fasta_index_tile_bytes();
+// d_file_off: n_files + 1 offsets, ascending from 0; d_scratch: fasta_index_scratch_bytes(n_tiles), n_tiles = tiles (TEXT_TILE, text_tiles.h) of `total` bytes.
 size_t fasta_index_scratch_bytes(uint32_t n_tiles);
 hipError_t launch_fasta_mark(const uint8_t *d_raw, uint64_t total, const uint64_t *d_file_off, uint32_t n_files, uint32_t n_tiles,
                              uint8_t *d_scratch, const uint32_t **d_n_records_and_bad, hipStream_t stream);
 hipError_t launch_fasta_write(const uint8_t *d_raw, uint64_t total, const uint64_t *d_file_off, uint32_t n_files, uint32_t n_tiles,
                               uint8_t *d_scratch, uint32_t n_records, uint64_t *d_start, uint32_t *d_file, uint32_t *d_id_len, hipStream_t stream);
+// fasta_coords.hip: the sequence coordinates of the records of such an index, the ground the two stages below stand on.  launch_fasta_coords
+// queues its passes and leaves in d_scratch (fasta_coords_scratch_bytes(n_tiles, n_records)) what fasta_coords_view hands out: the lane words
+// (bits 0..15: which of the lane's 16 bytes are sequence bytes; bits 16..: sequence bytes of the tile before the lane), the exclusive scan of
+// the tiles' counts (n_tiles + 1), seq_begin[r] (n_records: the first byte after record r's header line) and seq0[r] (n_records + 1): sequence
+// bytes before record r, so L_r = seq0[r + 1] - seq0[r] and seq0[n_records] is their number.  d_start: the index's start[n_records + 1].
+struct FastaCoords {
+    const uint32_t *lanes;
+    const uint64_t *tile_base, *seq_begin, *seq0;
+};
+size_t fasta_coords_scratch_bytes(uint32_t n_tiles, uint32_t n_records);
+FastaCoords fasta_coords_view(uint8_t *d_scratch, uint32_t n_tiles, uint32_t n_records);
+hipError_t launch_fasta_coords(const uint8_t *d_raw, uint64_t total, const uint64_t *d_start, uint32_t n_records, uint32_t n_tiles,
+                               uint8_t *d_scratch, hipStream_t stream);
 // fasta_windows.hip: fixed-length windows of the records of such an index, rewritten as one-record FASTA files (lash_fasta_windows).
-// launch_fasta_windows_count queues the passes up to the two totals (sequence bytes S, windows n: one u64 each, device); once the caller has
-// read them and made room (d_out: S + 3n bytes; d_record / d_begin / d_length: n u64; d_off: n + 1 u64), launch_fasta_windows_write queues
-// the window table and the scatter.  d_start: the index's start[n_records + 1]; d_scratch: fasta_windows_scratch_bytes(n_tiles, n_records).
+// launch_fasta_windows_count queues the coordinate passes and its own up to the two totals (sequence bytes S, windows n: one u64 each, device);
+// once the caller has read them and made room (d_out: S + 3n bytes; d_record / d_begin / d_length: n u64; d_off: n + 1 u64),
+// launch_fasta_windows_write queues the window table and the scatter.  d_scratch: fasta_windows_scratch_bytes(n_tiles, n_records), the
+// coordinate scratch with win_base[n_records + 1] behind it.
 size_t fasta_windows_scratch_bytes(uint32_t n_tiles, uint32_t n_records);
 hipError_t launch_fasta_windows_count(const uint8_t *d_raw, uint64_t total, const uint64_t *d_start, uint32_t n_records, uint32_t n_tiles,
                                       uint64_t window, uint8_t *d_scratch, const uint64_t **d_seq_bytes, const uint64_t **d_n_windows,
@@ -261,21 +273,13 @@ hipError_t launch_fasta_windows_count(const uint8_t *d_raw, uint64_t total, cons
 hipError_t launch_fasta_windows_write(const uint8_t *d_raw, uint64_t total, const uint64_t *d_start, uint32_t n_records, uint32_t n_tiles,
                                       uint64_t window, uint8_t *d_scratch, uint64_t n_windows, uint64_t *d_record, uint64_t *d_begin,
                                       uint64_t *d_length, uint64_t *d_off, uint8_t *d_out, hipStream_t stream);
-// what launch_fasta_windows_count left in d_scratch, for another stage that needs sequence coordinates (fasta_translate.hip): the lane words
-// (bits 0..15: which of the lane's 16 bytes are sequence bytes; bits 16..: sequence bytes of the tile before the lane), the exclusive scan
-// of the tiles' counts, and seq0[r] (n_records + 1): sequence bytes before record r, so L_r = seq0[r + 1] - seq0[r]
-void fasta_windows_rank_view(uint8_t *d_scratch, uint32_t n_tiles, uint32_t n_records, const uint32_t **d_lanes, const uint64_t **d_tile_base,
-                             const uint64_t **d_seq0);
-// one workgroup, in place: d_a[i] = d_a[0] + ... + d_a[i - 1] for i in [0, n], d_a[n] the total (n + 1 entries)
-hipError_t launch_scan_u64(uint64_t *d_a, uint32_t n, hipStream_t stream);
 // fasta_translate.hip: the six reading frames of every record of such an index, translated (NCBI table 1) into one buffer of residues
 // (`lash sketch --translate`; lash_fasta_translate).  Record r takes 6 + 2 * max(0, L_r - 2) bytes at out_base[r]: frames 0..5 in order, each
-// its residues and one '*'.  launch_fasta_translate_sizes queues the coordinate passes (it runs launch_fasta_windows_count on d_scratch,
-// fasta_windows_scratch_bytes) and the scan to d_out_base[n_records + 1]; once the caller has read the total B = out_base[n_records] and made
+// its residues and one '*'.  launch_fasta_translate_sizes queues the coordinate passes (d_scratch: fasta_coords_scratch_bytes) and the scan
+// of the record sizes to d_out_base[n_records + 1]; once the caller has read the total B = out_base[n_records] and made
 // room (d_out: B + 64 bytes; d_tile_cnt: B / 4096 + 2 u64), launch_fasta_translate_write fills the buffer and leaves the scanned number of
 // break bytes ('*', 'X') per 4 KiB output tile in d_tile_cnt, the total n_seg in its last entry; with that read and d_seg_off (n_seg + 1) there,
 // launch_fasta_translate_segments writes seg_off (the position after every break byte, in order) and rec_seg[n_records + 1].
-uint32_t fasta_translate_tile_bytes();
 hipError_t launch_fasta_translate_sizes(const uint8_t *d_raw, uint64_t total, const uint64_t *d_start, uint32_t n_records, uint32_t n_tiles,
                                         uint8_t *d_scratch, uint64_t *d_out_base, hipStream_t stream);
 hipError_t launch_fasta_translate_write(const uint8_t *d_raw, uint64_t total, const uint64_t *d_start, uint32_t n_records, uint32_t n_tiles,
@@ -283,7 +287,6 @@ hipError_t launch_fasta_translate_write(const uint8_t *d_raw, uint64_t total, co
                                         hipStream_t stream);
 hipError_t launch_fasta_translate_segments(const uint8_t *d_out, uint64_t out_bytes, const uint64_t *d_tile_base, const uint64_t *d_out_base,
                                            uint32_t n_records, uint64_t n_seg, uint64_t *d_seg_off, uint64_t *d_rec_seg, hipStream_t stream);
-
 struct FinalizeArgs {
     const uint8_t  *partials;
     const WorkItem *items;

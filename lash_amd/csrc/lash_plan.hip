@@ -5,6 +5,7 @@
 // (/root/reference/src/utils.rs:452-508).
 #include "lash_ctx.h"
 #include "lash_internal.h"
+#include "text_tiles.h"
 
 namespace lashi {
 
@@ -141,7 +142,7 @@ int pack_into(lash_ctx *ctx, lash_packed *pk, hipStream_t stream, EvSet *ev, con
             // FASTQ files: quality-line lengths and how the file ends, into the same flags (fastq_check.hip)
             std::vector<FqFile> fq;
             uint64_t blocks = 0;
-            const uint64_t bb = fastq_check_block_bytes();
+            const uint64_t bb = TEXT_TILE;
             for (uint32_t g = 0; g < n_genomes; ++g) {
                 if (formats[g] != LASH_FMT_FASTQ || descs[g].byte_len == 0) continue;
                 const uint64_t nb = (descs[g].byte_len + bb - 1) / bb;

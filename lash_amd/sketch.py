@@ -220,103 +220,85 @@ class Packed:
             pass
 
 
-class WindowIndex:
-    """Device-resident windows of the records of a RecordIndex, rewritten as one-record FASTA files (lash_win_index*)."""
+class _DeviceIndex:
+    """what the device-resident results of the fasta_* stages share: the context, the C handle, how a table is copied out and how it all is freed"""
+    _FREE = None                                                     # name of the C function that frees the handle
 
     def __init__(self, ctx, handle):
         self._ctx, self._h = ctx, handle
+
+    def _copy(self, fn, n, dtype):
+        out = np.zeros(n, dtype)
+        self._ctx._check(getattr(_lib.load(), fn)(self._ctx._h, self._h, out.ctypes.data))
+        return out
+
+    def free(self):
+        if self._h:
+            getattr(_lib.load(), self._FREE)(self._ctx._h, self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+class WindowIndex(_DeviceIndex):
+    """Device-resident windows of the records of a RecordIndex, rewritten as one-record FASTA files (lash_win_index*)."""
+    _FREE = "lash_win_index_free"
+
+    def __init__(self, ctx, handle):
+        super().__init__(ctx, handle)
         self.n_windows = int(_lib.load().lash_win_index_n_windows(handle))
         self.nbytes = int(_lib.load().lash_win_index_bytes(handle))
 
     def arrays(self):
         """(record[n], begin[n], length[n]) u64, each one copy to the host"""
-        lib, n = _lib.load(), self.n_windows
-        out = [np.zeros(n, np.uint64) for _ in range(3)]
-        for fn, a in zip((lib.lash_win_index_record, lib.lash_win_index_begin, lib.lash_win_index_length), out):
-            self._ctx._check(fn(self._ctx._h, self._h, a.ctypes.data))
-        return tuple(out)
+        return tuple(self._copy("lash_win_index_" + t, self.n_windows, np.uint64) for t in ("record", "begin", "length"))
 
     def offsets(self):
         """offset[n + 1] u64: where every window's file starts in the device buffer"""
-        off = np.zeros(self.n_windows + 1, np.uint64)
-        self._ctx._check(_lib.load().lash_win_index_offset(self._ctx._h, self._h, off.ctypes.data))
-        return off
+        return self._copy("lash_win_index_offset", self.n_windows + 1, np.uint64)
 
     @property
     def device_ptr(self):
         return _lib.load().lash_win_index_buffer_device(self._h) or 0
 
-    def free(self):
-        if self._h:
-            _lib.load().lash_win_index_free(self._ctx._h, self._h)
-            self._h = None
 
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
-
-
-class TranslatedIndex:
+class TranslatedIndex(_DeviceIndex):
     """Device-resident six-frame translation of the records of a RecordIndex, cut into segments at stops and ambiguous codons
     (lash_tr_index*)."""
+    _FREE = "lash_tr_index_free"
 
     def __init__(self, ctx, handle, n_records):
-        self._ctx, self._h, self.n_records = ctx, handle, int(n_records)
+        super().__init__(ctx, handle)
+        self.n_records = int(n_records)
         self.n_segments = int(_lib.load().lash_tr_index_n_segments(handle))
         self.nbytes = int(_lib.load().lash_tr_index_bytes(handle))
 
     def arrays(self):
         """(seg_off[n_segments + 1], rec_seg[n_records + 1]) u64, each one copy to the host"""
-        lib = _lib.load()
-        seg_off, rec_seg = np.zeros(self.n_segments + 1, np.uint64), np.zeros(self.n_records + 1, np.uint64)
-        self._ctx._check(lib.lash_tr_index_seg_off(self._ctx._h, self._h, seg_off.ctypes.data))
-        self._ctx._check(lib.lash_tr_index_rec_seg(self._ctx._h, self._h, rec_seg.ctypes.data))
-        return seg_off, rec_seg
+        return self._copy("lash_tr_index_seg_off", self.n_segments + 1, np.uint64), self._copy("lash_tr_index_rec_seg", self.n_records + 1, np.uint64)
 
     @property
     def device_ptr(self):
         return _lib.load().lash_tr_index_buffer_device(self._h) or 0
 
-    def free(self):
-        if self._h:
-            _lib.load().lash_tr_index_free(self._ctx._h, self._h)
-            self._h = None
 
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
-
-
-class RecordIndex:
+class RecordIndex(_DeviceIndex):
     """Device-resident record index of raw multi-FASTA bytes (lash_rec_index*)."""
+    _FREE = "lash_rec_index_free"
 
     def __init__(self, ctx, handle):
-        self._ctx, self._h = ctx, handle
+        super().__init__(ctx, handle)
         self.n_records = int(_lib.load().lash_rec_index_n_records(handle))
 
     def arrays(self):
         """(start[n + 1] u64, id_len[n] u32, file[n] u32), each one copy to the host"""
-        lib, n = _lib.load(), self.n_records
-        start, id_len, file = np.zeros(n + 1, np.uint64), np.zeros(n, np.uint32), np.zeros(n, np.uint32)
-        self._ctx._check(lib.lash_rec_index_start(self._ctx._h, self._h, start.ctypes.data))
-        self._ctx._check(lib.lash_rec_index_id_len(self._ctx._h, self._h, id_len.ctypes.data))
-        self._ctx._check(lib.lash_rec_index_file(self._ctx._h, self._h, file.ctypes.data))
-        return start, id_len, file
-
-    def free(self):
-        if self._h:
-            _lib.load().lash_rec_index_free(self._ctx._h, self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
+        n = self.n_records
+        return (self._copy("lash_rec_index_start", n + 1, np.uint64), self._copy("lash_rec_index_id_len", n, np.uint32),
+                self._copy("lash_rec_index_file", n, np.uint32))
 
 
 class KmerFilter:
@@ -498,46 +480,38 @@ class Context:
                                                                     int(min_count), out.ctypes.data if out.size else None))
         return out
 
-    def fasta_index(self, raw, file_off, device=False, keep=False):
-        """lash_fasta_index: the records of raw multi-FASTA bytes, found on the GPU.  raw: uint8 array (or bytes) of the files back to
-        back — device=True: a device pointer / torch tensor; file_off: n_files + 1 byte offsets.  Returns (start[n + 1] u64,
-        id_len[n] u32, file[n] u32); keep=True returns a RecordIndex (for sketch_records_raw) instead."""
+    def _fasta_stage(self, name, raw, file_off, device, *args):
+        """what the fasta_* methods share: lash_<name>[_device](ctx, raw, file_off, n_files, *args, &handle) -> handle.  raw: uint8 array (or
+        bytes) of the files back to back — device=True: a device pointer / torch tensor; file_off: n_files + 1 byte offsets."""
         off = np.ascontiguousarray(file_off, dtype=np.uint64)
         if not device:
             raw = np.frombuffer(raw, dtype=np.uint8) if isinstance(raw, (bytes, bytearray)) else np.ascontiguousarray(raw, dtype=np.uint8)
             assert raw.size >= int(off[-1])
         h = C.c_void_p()
-        fn = self._lib.lash_fasta_index_device if device else self._lib.lash_fasta_index
-        rc = fn(self._h, _ptr(raw) if int(off[-1]) else None, off.ctypes.data, len(off) - 1, C.byref(h))
-        if rc == _lib.EINVAL:
-            raise LashError(rc, self._lib.lash_ctx_last_error(self._h).decode() or self._lib.lash_strerror(rc).decode())
-        self._check(rc)
-        ix = RecordIndex(self, h)
+        fn = getattr(self._lib, name + ("_device" if device else ""))
+        self._check_einval(fn(self._h, _ptr(raw) if int(off[-1]) else None, off.ctypes.data, len(off) - 1, *args, C.byref(h)))
+        return h
+
+    @staticmethod
+    def _kept_or_arrays(index, keep):
         if keep:
-            return ix
+            return index
         try:
-            return ix.arrays()
+            return index.arrays()
         finally:
-            ix.free()
+            index.free()
+
+    def fasta_index(self, raw, file_off, device=False, keep=False):
+        """lash_fasta_index: the records of raw multi-FASTA bytes, found on the GPU.  raw: uint8 array (or bytes) of the files back to
+        back — device=True: a device pointer / torch tensor; file_off: n_files + 1 byte offsets.  Returns (start[n + 1] u64,
+        id_len[n] u32, file[n] u32); keep=True returns a RecordIndex (for sketch_records_raw) instead."""
+        return self._kept_or_arrays(RecordIndex(self, self._fasta_stage("lash_fasta_index", raw, file_off, device)), keep)
 
     def fasta_windows(self, raw, file_off, index, window, device=False, keep=False):
         """lash_fasta_windows: the records of `index` (a RecordIndex made from the same raw / file_off) cut into windows of `window` bases
         on the GPU.  raw as for fasta_index.  Returns (record[n], begin[n], length[n]) u64; keep=True returns a WindowIndex (for
         sketch_windows) instead."""
-        off = np.ascontiguousarray(file_off, dtype=np.uint64)
-        if not device:
-            raw = np.frombuffer(raw, dtype=np.uint8) if isinstance(raw, (bytes, bytearray)) else np.ascontiguousarray(raw, dtype=np.uint8)
-            assert raw.size >= int(off[-1])
-        h = C.c_void_p()
-        fn = self._lib.lash_fasta_windows_device if device else self._lib.lash_fasta_windows
-        self._check_einval(fn(self._h, _ptr(raw) if int(off[-1]) else None, off.ctypes.data, len(off) - 1, index._h, int(window), C.byref(h)))
-        wi = WindowIndex(self, h)
-        if keep:
-            return wi
-        try:
-            return wi.arrays()
-        finally:
-            wi.free()
+        return self._kept_or_arrays(WindowIndex(self, self._fasta_stage("lash_fasta_windows", raw, file_off, device, index._h, int(window))), keep)
 
     def sketch_windows(self, algo, k, p, seed, windows, w0=0, w1=None, flags=0):
         """lash_sketch_windows_raw: one image per window, windows [w0, w1) of a WindowIndex.  Returns images[w1 - w0, image_bytes]."""
@@ -554,20 +528,8 @@ class Context:
         """lash_fasta_translate: the six reading frames of the records of `index` (a RecordIndex made from the same raw / file_off),
         translated on the GPU and cut into segments at stops and ambiguous codons.  raw as for fasta_index.  Returns
         (seg_off[n_segments + 1], rec_seg[n_records + 1]) u64; keep=True returns a TranslatedIndex (for sketch_translated) instead."""
-        off = np.ascontiguousarray(file_off, dtype=np.uint64)
-        if not device:
-            raw = np.frombuffer(raw, dtype=np.uint8) if isinstance(raw, (bytes, bytearray)) else np.ascontiguousarray(raw, dtype=np.uint8)
-            assert raw.size >= int(off[-1])
-        h = C.c_void_p()
-        fn = self._lib.lash_fasta_translate_device if device else self._lib.lash_fasta_translate
-        self._check_einval(fn(self._h, _ptr(raw) if int(off[-1]) else None, off.ctypes.data, len(off) - 1, index._h, C.byref(h)))
-        ti = TranslatedIndex(self, h, index.n_records)
-        if keep:
-            return ti
-        try:
-            return ti.arrays()
-        finally:
-            ti.free()
+        h = self._fasta_stage("lash_fasta_translate", raw, file_off, device, index._h)
+        return self._kept_or_arrays(TranslatedIndex(self, h, index.n_records), keep)
 
     def sketch_translated(self, algo, k, p, seed, translated, group_rec_off=None, flags=0, out=None):
         """lash_sketch_translated: one amino-acid image per group of records of a TranslatedIndex; group g = records

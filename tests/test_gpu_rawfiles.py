@@ -283,3 +283,24 @@ def test_fastq_quality_length_check_on_the_device_is_exact(ctx):
         want_bad = {i for i, f in enumerate(data) if _host_says_bad(f)}
         flagged, img = _device_flags(ctx, data)
         assert flagged == want_bad, (it, sorted(flagged), sorted(want_bad))
+
+
+def test_fastq_quality_length_check_past_1024_blocks(ctx):
+    """one well-formed FASTQ file of more than 1024 blocks of the check (the per-file scan of the blocks' newline counts gives a thread more
+    than one block), and the same file with one quality line one byte short in its last block"""
+    rng = random.Random(78)
+    g = O.synth_genome(91, 400_000).tobytes()
+    recs = []
+    for i in range(13_000):
+        n = rng.randint(20, 300)
+        s = rng.randrange(0, len(g) - n)
+        recs.append([b"@r%d" % i, g[s:s + n], b"+", b"I" * n])
+    good = b"".join(b"\n".join(r) + b"\n" for r in recs)
+    assert 1024 < -(-len(good) // 4096) <= 1100
+    recs[-1][3] = recs[-1][3][:-1]
+    bad = b"".join(b"\n".join(r) + b"\n" for r in recs)
+    assert len(b"\n".join(recs[-1])) < len(bad) % 4096                                       # the whole record lies in the last block
+    assert not _host_says_bad(good) and _host_says_bad(bad)
+    flagged, img = _device_flags(ctx, [good, bad])
+    assert flagged == {1}
+    assert np.array_equal(img[0], O.sketch_files(O.HMH, 16, 0, 42, [good], threads=4)[0])

@@ -157,6 +157,23 @@ def test_stage_on_single_files_and_nothing(ctx):
     check_stage(ctx, [b"", b""], M.Model([b"", b""]))                # no record at all
 
 
+def test_stage_past_1024_input_tiles_and_2048_output_tiles(ctx):
+    """one file of more than 1024 input tiles, more than 1024 records and more than 2048 output tiles: the single-workgroup scans of the tile
+    counts, of the record sizes and of the output tiles' break counts give a thread two elements, two and three"""
+    rng = random.Random(31)
+    g = dna(23, 400_000)
+    recs = []
+    for i in range(1480):
+        n = rng.randint(1000, 4900)
+        s = rng.randrange(0, len(g) - n)
+        recs.append(b">q%d\n" % i + lines(g[s:s + n], 97))
+    raw = b"".join(recs)
+    assert 1024 < -(-len(raw) // TILE) <= 1100 and len(recs) > 1024
+    m = M.Model([raw])
+    assert -(-len(m.buffer) // TILE) > 2048 and len(set(m.lengths)) > 500                             # lengths that are multiples of nothing
+    check_stage(ctx, [raw], m)
+
+
 def test_refusals(ctx):
     fa = b">a\nACGTACGTACGTACGTACGTAAATTTGGGCCC\n>b\nACGT\n"
     raw, off = np.frombuffer(fa, np.uint8), offsets([fa])

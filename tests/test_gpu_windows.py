@@ -234,6 +234,22 @@ def test_single_files_and_refusals(ctx):
         other.close()
 
 
+def test_window_table_past_1024_tiles_and_1024_records(ctx):
+    """one file of more than 1024 input tiles and more than 1024 records: the single-workgroup scans of the tile counts and of the records'
+    window counts each give a thread more than one element"""
+    rng = random.Random(29)
+    g = dna(19, 400_000)
+    recs = []
+    for i in range(1480):
+        n = rng.randint(1000, 4900)
+        s = rng.randrange(0, len(g) - n)
+        recs.append(b">q%d\n" % i + lines(g[s:s + n], 97))
+    raw = b"".join(recs)
+    assert 1024 < -(-len(raw) // 4096) <= 1100 and len(recs) > 1024
+    rec, beg, ln, data, ids = check_table(ctx, [raw], 997)
+    assert len(data) > 4096 and int(rec[-1]) == len(recs) - 1 and len({int(x) for x in ln}) > 500      # lengths that are multiples of nothing
+
+
 # ---- 2. - 4. images ------------------------------------------------------------------------------------------------------------------
 def check_images(ctx, files, w, algo, k, p, step=1 << 30, oracle_every=1, cuts=()):
     raw = np.frombuffer(b"".join(files), np.uint8)
