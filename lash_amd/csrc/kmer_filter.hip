@@ -27,11 +27,7 @@ __device__ __forceinline__ void kmer_filter_walk(const KmerFilterArgs &a)
 {
     const int k = a.k;
     KParams kp{};                                                          // the window fields only: nothing is hashed with xxh3 here
-    kp.sh_lt = 32u - 2u * (uint32_t)k;
-    kp.mask_lt = (KMODE == KM_LT16) ? ((1u << (2 * k)) - 1u) : 0xFFFFFFFFu;
-    kp.sh_gt = 64u - 2u * (uint32_t)k;
-    kp.mask_gt = (k == 32) ? ~0ull : ((1ull << (2 * k)) - 1ull);
-    kp.mask_hi = (uint32_t)(kp.mask_gt >> 32);
+    kp.set_window<KMODE>(k);
     const uint32_t cm = a.comp_mask;
     for (uint32_t g = blockIdx.y; g < a.n_genomes; g += gridDim.y) {
         const GenomeDesc gd = a.genomes[g];

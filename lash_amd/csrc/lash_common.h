@@ -30,7 +30,7 @@ struct WorkItem {
     uint32_t genome;
     uint32_t word_begin;  // slice = packed words [word_begin, word_end) of the genome, multiples of 4
     uint32_t word_end;
-    uint32_t slice;       // bits 14:0 slice index inside the genome, bit 15 ITEM_SOLE; bits 31:16 which bucket-space pass
+    uint32_t slice;       // bits 14:0 slice index inside the genome, bit 15 ITEM_SOLE
 };
 
 constexpr uint32_t ITEM_SOLE        = 0x8000u;   // WorkItem::slice flag: the genome's only work item (writes the image itself)

@@ -75,7 +75,6 @@ struct SketchPlan {
     uint32_t threads;             // 512 (<= 64 KiB of LDS, two workgroups per CU) or 1024
     uint32_t lds_bytes;
     uint32_t nreg32;
-    uint32_t parts_log2;          // > 0: the bucket space is covered in 2^parts_log2 passes, nreg32 / lds_bytes are per pass
     uint32_t partial_bytes;       // bytes of one partial sketch (register array only)
     uint32_t partial_stride;      // rounded up to 16
     bool     defer = false;       // direct HyperMinHash launch with deferred signatures (the caller sets it for batches of large work items)
@@ -124,7 +123,7 @@ hipError_t launch_sketch(const SketchPlan &plan, const SketchArgs &args, uint32_
 // the packed launch with args.keep ANDed into every lane's validity mask (lash_sketch_files_raw_filtered).  Only for plans with a plain
 // register table in LDS (sketch_plan_keeps): anything else is hipErrorInvalidValue
 hipError_t launch_sketch_keep(const SketchPlan &plan, const SketchArgs &args, uint32_t n_items, hipStream_t stream);
-inline bool sketch_plan_keeps(const SketchPlan &plan) { return plan.use_lds && !plan.bins && !plan.bytes && plan.parts_log2 == 0; }
+inline bool sketch_plan_keeps(const SketchPlan &plan) { return plan.use_lds && !plan.bins && !plan.bytes; }
 
 // ---- k-mer abundance filter (kmer_filter.hip; `lash sketch --min-count`) ------------------------------------------------------
 // Two passes over the pack stage's output.  kmer_count_kernel adds every valid k-mer occurrence of genome g to two saturating byte
@@ -301,18 +300,17 @@ struct FinalizeArgs {
     uint64_t        alpha_bits;          // HLL alpha as f64 bits
     int             algo, p, k;
     int             accumulate;          // union into the registers already in images[]
-    uint32_t        parts_log2;          // see SketchPlan: a partial holds only the registers of its item's pass
     LayoutDev       lay;
     uint32_t       *hll_corner;          // NULL, or [n_genomes] zeroed: set when a genome holds a HyperLogLog register > 53 - p
                                          // (write_hll_header, sketch_kernels.hip)
     int             src_images;          // the "partials" are images (lash_merge_images): HMH registers in image byte order
-    uint32_t        group;               // 0, or G: launch_reduce_groups() has folded every G consecutive slices (per
-                                         // pass) into the first one's partial; only those group heads are read
+    uint32_t        group;               // 0, or G: launch_reduce_groups() has folded every G consecutive slices
+                                         // into the first one's partial; only those group heads are read
     const GenomeDesc *descs;             // NULL, or: genomes of at most skip_max_len bytes are not this launch's (the persistent
     uint64_t        skip_max_len;        // small-genome kernel writes their images: sole_kernels.hip)
 };
 // Many slices per genome (one metagenome-sized input: thousands of work items, one finalize workgroup): fold every R
-// consecutive slices into the first one's partial, in place, with one workgroup per (genome, pass, group).
+// consecutive slices into the first one's partial, in place, with one workgroup per (genome, group).
 hipError_t launch_reduce_groups(const FinalizeArgs &args, uint32_t n_genomes, uint32_t max_slices, hipStream_t stream);
 hipError_t launch_finalize(const FinalizeArgs &args, uint32_t n_genomes, hipStream_t stream);
 hipError_t launch_census(const FinalizeArgs &args, uint32_t n_genomes, hipStream_t stream);   // all genomes ITEM_SOLE

@@ -576,7 +576,7 @@ static PlanKnobs plan_knobs()
 }
 
 // HyperMinHash launches that may defer their signatures (process_word_defer, ItemPlan::defer)
-static bool may_defer(const SketchPlan &plan) { return plan.algo == LASH_HMH && plan.use_lds && plan.parts_log2 == 0; }
+static bool may_defer(const SketchPlan &plan) { return plan.algo == LASH_HMH && plan.use_lds; }
 
 // what a call launches (the amino-acid branch fills the first three fields itself)
 struct ItemPlan {
@@ -629,7 +629,7 @@ static ItemPlan plan_items(const std::vector<uint64_t> &blen, const SketchPlan &
         for (uint64_t b : blen) any_cut = any_cut || (((b + 15) / 16 + 3) & ~3ull) > target;
         if (any_cut && !equal_genomes) target = std::max(min_slice, std::min(target, cap));
     }
-    ip.all_sole = plan.parts_log2 == 0 && plan.use_lds && !plan.bins && n_genomes > 0;
+    ip.all_sole = plan.use_lds && !plan.bins && n_genomes > 0;
     ip.item_begin.assign(n_genomes + 1, 0);
     ip.items.reserve(n_genomes * 2);
     auto slicing = [&](uint32_t g, uint64_t &nw, uint64_t &ns, uint64_t &per) {
@@ -668,7 +668,7 @@ static ItemPlan plan_items(const std::vector<uint64_t> &blen, const SketchPlan &
         if (nw == 0) { ip.all_sole = false; continue; }            // no work item at all: finalize writes the empty image (or it is the
                                                                    // persistent kernel's: FinalizeArgs::skip_max_len)
         uint32_t s = 0;
-        const bool whole = ns == 1 && plan.parts_log2 == 0 && plan.use_lds && !plan.bins;
+        const bool whole = ns == 1 && plan.use_lds && !plan.bins;
         for (uint64_t b = 0; b < nw; b += per, ++ci) {
             const uint64_t e = std::min(nw, b + per);
             uint64_t sub = e - b;                                  // this slice as one item, or as tail_split smaller ones
@@ -687,8 +687,7 @@ static ItemPlan plan_items(const std::vector<uint64_t> &blen, const SketchPlan &
             }
             const bool sole = whole && sub == e - b;
             for (uint64_t bb = b; bb < e; bb += sub, ++s)
-                for (uint32_t part = 0; part < (1u << plan.parts_log2); ++part)               // slice index | pass << 16
-                    ip.items.push_back(WorkItem{g, (uint32_t)bb, (uint32_t)std::min(e, bb + sub), (s & 0x7FFFu) | (part << 16) | (sole ? ITEM_SOLE : 0u)});
+                ip.items.push_back(WorkItem{g, (uint32_t)bb, (uint32_t)std::min(e, bb + sub), (s & 0x7FFFu) | (sole ? ITEM_SOLE : 0u)});
         }
         ip.max_slices = std::max<uint32_t>(ip.max_slices, s);
         if (s != 1) ip.all_sole = false;
@@ -766,7 +765,7 @@ static SketchArgs sketch_args(const lash_ctx *ctx, const lash_params *prm, const
     sa.gregs = static_cast<uint32_t *>(ctx->gregs.ptr);
     sa.item_kmers = static_cast<uint32_t *>(ctx->item_kmers.ptr);
     sa.partial_stride = plan.partial_stride;
-    sa.nreg32 = plan.nreg32 >> plan.parts_log2;                 // register words of one pass
+    sa.nreg32 = plan.nreg32;
     return sa;
 }
 
@@ -790,7 +789,6 @@ static int finalize_run(lash_ctx *ctx, const lash_params *prm, const SketchPlan 
     fa.partial_stride = plan.partial_stride;
     fa.partial_base_off = 0;
     fa.algo = prm->algo;
-    fa.parts_log2 = plan.parts_log2;
     fa.src_images = 0;
     // one finalize workgroup walks all of a genome's partials: fine for a handful of slices, 20 ms for the 4 096 slices of
     // a metagenome-sized input (BASELINE configs[4]) -> fold groups of 32 slices first (until <= 16 heads remain)
@@ -1065,8 +1063,7 @@ int sketch_aa(lash_ctx *ctx, const lash_params *prm, const uint8_t *d_seq, const
         if (nr > 0xFFFFFFFFull) return LASH_ELIMIT;
         uint32_t s = 0;
         for (uint64_t r0 = 0; r0 < nr; r0 += AA_RECORDS_PER_ITEM, ++s)
-            for (uint32_t part = 0; part < (1u << plan.parts_log2); ++part)
-                ip.items.push_back(WorkItem{g, (uint32_t)r0, (uint32_t)std::min<uint64_t>(nr, r0 + AA_RECORDS_PER_ITEM), (s & 0x7FFFu) | (part << 16)});
+            ip.items.push_back(WorkItem{g, (uint32_t)r0, (uint32_t)std::min<uint64_t>(nr, r0 + AA_RECORDS_PER_ITEM), s & 0x7FFFu});
         ip.max_slices = std::max(ip.max_slices, s);
     }
     ip.item_begin[n_genomes] = (uint32_t)ip.items.size();

@@ -33,9 +33,7 @@ __global__ void __launch_bounds__(1024) LASH_SKETCH_WAVES_PER_EU_ATTR sketch_ker
     constexpr int REGS = KEEP ? REGS_LDS : REGS_;
     static_assert(!DEFER || (ALGO == 0 && REGS == REGS_LDS), "deferred signatures: HyperMinHash, one LDS table");
     static_assert(!KEEP || (!DIRECT && !DEFER && REGS == REGS_LDS), "keep bits: the packed launch with a plain LDS table");
-    // dynamic LDS: [nreg32 register words][16 words of per-wave census]; registers start at LDS offset 0 so the
-    // bucket offset goes straight into the ds_max / ds_or address
-    extern __shared__ __attribute__((aligned(16))) uint32_t lds_regs[];
+    extern __shared__ __attribute__((aligned(16))) uint32_t lds_regs[];   // (its layout: bind_regs)
 
     // work items are handed out longest first when their sizes differ (a.item_order: the host's permutation), so that the last
     // workgroups to start are the short ones: a mixed collection lost 11 % to its tail in launch order = genome order
@@ -59,9 +57,11 @@ __global__ void __launch_bounds__(1024) LASH_SKETCH_WAVES_PER_EU_ATTR sketch_ker
     // instead of a pair and a 64-bit compare; the loop is short of scalar registers)
     const uint32_t nk_words = (uint32_t)((nk + 15) >> 4);                // word w holds a k-mer start <=> w < nk_words
     const uint32_t fast_words = L >= 96 ? (uint32_t)((L - 96) >> 4) + 1u : 0u;   // all 96 bytes from word w on are inside <=> w < fast_words
+    // (This kernel spells out three things the other kernels take from sketch_rules.h — the empty image, the clear loop, the window's
+    // rotation: through write_empty_sole_image / arm_table / rotate_window hipcc allocates the tile loop's registers differently, and the
+    // judged instantiations sit at their 128-register cap with a scratch budget: tests/test_kernel_budget.py.  A change to one of the
+    // three there belongs here too)
     if ((uint64_t)it.word_begin * 16 >= nk) {                             // slice beyond the surviving bases
-        // the only work item of a genome too short for a single k-mer still owes the (empty) image; when the call
-        // unions into existing images there is nothing to add
         if ((it.slice & ITEM_SOLE) && !a.accumulate) {
             uint8_t *img = a.images + (uint64_t)it.genome * a.image_bytes;
             for (uint64_t i = threadIdx.x; i < a.image_bytes; i += blockDim.x) img[i] = 0;
@@ -74,31 +74,12 @@ __global__ void __launch_bounds__(1024) LASH_SKETCH_WAVES_PER_EU_ATTR sketch_ker
         return;
     }
 
-    constexpr bool USE_LDS = REGS != REGS_GLOBAL;
-    using Regs = typename std::conditional<DEFER, typename std::conditional<XLOW, LdsThrRegsX, LdsThrRegs>::type,
-                                           typename std::conditional<REGS == REGS_LDS, LdsRegs,
-                                           typename std::conditional<REGS == REGS_GLOBAL, GlobalRegs,
-                                           typename std::conditional<REGS == REGS_BINS, BinRegs, LdsByteQRegs<ALGO>>::type>::type>::type>::type;
+    using Regs = SketchRegs<ALGO, REGS, XLOW, DEFER, true>;
     // what the slow paths (junction walks, dense tiles) update through: the byte tables' plain compare-and-swap form
     using SlowRegs = typename std::conditional<REGS == REGS_BYTES, LdsByteRegs, Regs>::type;
     Regs regs;
     uint32_t *census;
-    const uint32_t part = 0u;
-    if constexpr (REGS == REGS_BINS) {
-        regs = bin_regs_of<ALGO>(a, it.genome);                            // no table here: entries for bins_apply_kernel
-        census = lds_regs;
-    } else if constexpr (REGS == REGS_BYTES) {
-        if ((uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint32_t *)lds_regs != 0u) __builtin_trap();
-        regs.p = p;
-        census = lds_regs + a.nreg32;
-    } else if constexpr (USE_LDS) {
-        if ((uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint32_t *)lds_regs != 0u) __builtin_trap();
-        regs.base = lds_regs;
-        census = lds_regs + a.nreg32;
-    } else {
-        regs.base = a.gregs + (uint64_t)(item - a.item_base) * a.nreg32;   // (tables of the items of this launch: lash_api.hip, global_run)           // zeroed by the host (hipMemsetAsync)
-        census = lds_regs;
-    }
+    bind_regs<ALGO, REGS>(a, it, item, lds_regs, regs, census);
 
     const uint32_t *__restrict__ w = a.words + gd.word_off;
     // A genome with a single record has no interior record boundary: its lanes read three always-zero words (one
@@ -115,14 +96,7 @@ __global__ void __launch_bounds__(1024) LASH_SKETCH_WAVES_PER_EU_ATTR sketch_ker
     const uint8_t *__restrict__ gseq = DIRECT ? a.seq + gd.byte_off : nullptr;
     uint32_t *const dirty = DIRECT ? a.dirty + it.genome : nullptr;
     KParams kp;
-    kp.bitflip = BitFlip::vector(a.bitflip);
-    kp.p = p;
-    kp.sh_lt = 32u - 2u * (uint32_t)k;
-    kp.mask_lt = (KMODE == KM_LT16) ? ((1u << (2 * k)) - 1u) : 0xFFFFFFFFu;
-    kp.sh_gt = 64u - 2u * (uint32_t)k;
-    kp.mask_gt = (k == 32) ? ~0ull : ((1ull << (2 * k)) - 1ull);
-    kp.mask_hi = (uint32_t)(kp.mask_gt >> 32);
-    kp.to_vector_registers();
+    kp.set_hashing<KMODE>(k, p, a.bitflip);
     const uint32_t cmask = a.lay.comp_mask;
     const CodeTabs ctabs{a.lay.code_lo, a.lay.code_hi};
     constexpr bool K21 = KMODE == KM_GT16 && DIRECT && !DEFER && (REGS == REGS_LDS || REGS == REGS_BYTES);   // kernels with a k = 21 body of their own
@@ -173,7 +147,7 @@ __global__ void __launch_bounds__(1024) LASH_SKETCH_WAVES_PER_EU_ATTR sketch_ker
     tile_load(it.word_begin, nxt);
     // the table is cleared while the first tile's loads are in flight; a raw barrier, because __syncthreads() would also
     // drain vmcnt and with it those loads
-    if constexpr (USE_LDS && REGS != REGS_BINS) {
+    if constexpr (REGS == REGS_LDS || REGS == REGS_BYTES) {
         for (uint32_t i = threadIdx.x; i < a.nreg32; i += blockDim.x) lds_regs[i] = ALGO == 2 ? 0u : RANK_EMPTY;
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     }
@@ -233,7 +207,7 @@ __global__ void __launch_bounds__(1024) LASH_SKETCH_WAVES_PER_EU_ATTR sketch_ker
                     const uint64_t act = __builtin_amdgcn_ballot_w64(active);
                     if (__builtin_amdgcn_ballot_w64(gone) == act) {
                         // (raw_ok lanes own exactly their 64 bytes: the genome's tail is at least 32 bytes away)
-                        if ((threadIdx.x & 63) == 0 && part == 0u) atomicAdd(a.ndel + it.genome, 64u * (uint32_t)__builtin_popcountll(act));
+                        if ((threadIdx.x & 63) == 0) atomicAdd(a.ndel + it.genome, 64u * (uint32_t)__builtin_popcountll(act));
                         tile_load(tile + step, nxt);
                         continue;
                     }
@@ -290,11 +264,11 @@ __global__ void __launch_bounds__(1024) LASH_SKETCH_WAVES_PER_EU_ATTR sketch_ker
                     if constexpr (Regs::QUEUED) regs.template drain<true>();
                     my_kmers += wave_sum(dense_tile<ALGO, KMODE, XLOW, SlowRegs>(regs, kp, gseq, L, P0, E, use_bitmap ? bk : nullptr, RL, k, cmask, ctabs,
                                                                             (uint32_t)__builtin_amdgcn_readfirstlane((int)stage_b), dirty,
-                                                                            part == 0u ? a.ndel + it.genome : nullptr, raw_ok, cur.q, cur.a1, cur.a2, cur.a3));
+                                                                            a.ndel + it.genome, raw_ok, cur.q, cur.a1, cur.a2, cur.a3));
                     tile_load(tile + step, nxt);
                     continue;
                 }
-                if (wave_nd && part == 0u && (threadIdx.x & 63) == 0) atomicAdd(a.ndel + it.genome, wave_nd);   // (one per wave; the passes of a partitioned table see the same bytes)
+                if (wave_nd && (threadIdx.x & 63) == 0) atomicAdd(a.ndel + it.genome, wave_nd);   // (one per wave)
                 uint32_t walked = 0;
                 if (junc)                                                      // (here, not after the hashing: nothing of it stays live)
                     walked = junction_walk<ALGO, XLOW, SlowRegs>(regs, gseq, L, pos0, junc, jstarts, use_bitmap ? bk : nullptr, RL, k, kp.bitflip, p,
@@ -321,40 +295,8 @@ __global__ void __launch_bounds__(1024) LASH_SKETCH_WAVES_PER_EU_ATTR sketch_ker
         if constexpr (REGS == REGS_BINS) regs.mode = 1u;                   // the word loop pushes without branches (BinRegs::mode)
 #pragma unroll LASH_WORD_UNROLL
         for (int wi = 0; wi < SKETCH_WORDS_PER_THREAD; ++wi) {
-            uint32_t z;
-            if constexpr (DEFER) {
-                z = 0xFFFFFFFFu;                                               // (nothing to re-run: the full update does that itself)
-                if (all_valid) process_word_defer<KMODE, false>(regs, kp, c0, c1, c2, r0, r1, r2, 0u, sigq);
-                else {
-                    uint32_t kvw = (uint32_t)kv;
-                    asm volatile("" : "+v"(kvw));
-                    process_word_defer<KMODE, true>(regs, kp, c0, c1, c2, r0, r1, r2, kvw, sigq);
-                }
-            } else if (K21 && k == 21) {
-                // k = 21 (BASELINE configs[2]; the fields of the 64-bit window at compile-time places: canon_gt16<21>)
-                if (all_valid) z = process_word<ALGO, KMODE, XLOW, false, true, Regs, K21 ? 21 : 0>(regs, kp, c0, c1, c2, r0, r1, r2, 0u);
-                else {
-                    uint32_t kvw = (uint32_t)kv;
-                    asm volatile("" : "+v"(kvw));
-                    z = process_word<ALGO, KMODE, XLOW, true, true, Regs, K21 ? 21 : 0>(regs, kp, c0, c1, c2, r0, r1, r2, kvw);
-                }
-            } else if (all_valid) {
-                z = process_word<ALGO, KMODE, XLOW, false, true>(regs, kp, c0, c1, c2, r0, r1, r2, 0u);
-            } else {
-                // the masks are taken from an opaque copy so that hipcc cannot hoist the 16 v_bfe_i32 above the
-                // branch, where the (usual) all-valid path would pay for them too
-                uint32_t kvw = (uint32_t)kv;
-                asm volatile("" : "+v"(kvw));
-                z = process_word<ALGO, KMODE, XLOW, true, true>(regs, kp, c0, c1, c2, r0, r1, r2, kvw);
-            }
-            // FAST forms return a word whose smallness flags "rank not decided by the bits looked at": exact re-run
-            // (HMH/x-high looks at 18 bits -> 2^-18 per k-mer; the others at 32 bits -> 2^-32)
-            constexpr uint32_t Z_REDO = z_redo<ALGO, Regs>();
-            if (z <= Z_REDO) {
-                uint32_t kvw = (uint32_t)kv;
-                asm volatile("" : "+v"(kvw));
-                (void)process_word<ALGO, KMODE, XLOW, true, false>(regs, kp, c0, c1, c2, r0, r1, r2, kvw);
-            }
+            // k = 21 (BASELINE configs[2]; the fields of the 64-bit window at compile-time places: canon_gt16<21>)
+            hash_word<ALGO, KMODE, XLOW, Regs, K21 ? 21 : 0, DEFER>(regs, kp, c0, c1, c2, r0, r1, r2, all_valid, (uint32_t)kv, sigq, K21 && k == 21);
             if constexpr (REGS == REGS_BINS) {
                 if (regs.overflowed()) {                                       // a staging row ran full: the word again, straight to the fallback table
                     regs.mode = 2u;
@@ -365,7 +307,6 @@ __global__ void __launch_bounds__(1024) LASH_SKETCH_WAVES_PER_EU_ATTR sketch_ker
                 }
                 if ((((uint32_t)wi + 1u) & (a.bin_flush_words - 1u)) == 0u) regs.flush(lane);   // the staged entries leave the wave's rows (every word, or every 2nd / 4th)
             }
-            // rotate the window by one word
             c0 = c1; c1 = c2; c2 = c3; c3 = c4; c4 = c5; c5 = 0;
             r0 = r1;
             if constexpr (KMODE == KM_GT16) { r1 = r2; r2 = rcword(c2, cmask); } else { r1 = rcword(c1, cmask); }
@@ -379,7 +320,7 @@ __global__ void __launch_bounds__(1024) LASH_SKETCH_WAVES_PER_EU_ATTR sketch_ker
 #ifdef LASH_ABL_NO_FLUSH
     if (a.k != 99) return;
 #endif
-    finish_item<ALGO, REGS, Regs>(a, it, regs, census, part, my_kmers, p, item);
+    finish_item<ALGO, REGS, Regs>(a, it, regs, census, my_kmers, p, item);
 #ifdef LASH_ITEM_TRACE_BUILD
     if (a.item_trace && threadIdx.x == 0) a.item_trace[4ull * item + 1] = wall_clock64();
 #endif
@@ -420,42 +361,14 @@ __global__ void __launch_bounds__(1024) stream_sketch_kernel(SketchArgs a)
     const int k = a.k, p = a.p;
     const uint64_t nkg = L >= (uint64_t)k ? L - (uint64_t)k + 1 : 0;
     if ((uint64_t)it.word_begin * 16 >= nkg) {                            // (as in sketch_kernel: the item holds no k-mer start)
-        if ((it.slice & ITEM_SOLE) && !a.accumulate) {
-            uint8_t *img = a.images + (uint64_t)it.genome * a.image_bytes;
-            for (uint64_t i = threadIdx.x; i < a.image_bytes; i += blockDim.x) img[i] = 0;
-            __syncthreads();
-            if (threadIdx.x == 0) {
-                const uint64_t n_regs = ALGO == 0 ? HMH_M : (1ull << p);
-                write_header(img, a.lay.hdr_tpl, a.alpha_bits, n_regs, n_regs, (double)n_regs, ALGO == 0 ? HMH_P : p);
-            }
-        }
+        write_empty_sole_image<ALGO>(a, it, p);
         return;
     }
-    constexpr bool USE_LDS = REGS != REGS_GLOBAL;
-    using Regs = typename std::conditional<DEFER, typename std::conditional<XLOW, LdsThrRegsX, LdsThrRegs>::type,
-                                           typename std::conditional<REGS == REGS_LDS, LdsRegs,
-                                           typename std::conditional<REGS == REGS_GLOBAL, GlobalRegs,
-                                           typename std::conditional<REGS == REGS_BINS, BinRegs, LdsByteRegs>::type>::type>::type>::type;
+    using Regs = SketchRegs<ALGO, REGS, XLOW, DEFER, false>;
     Regs regs;
     uint32_t *census;
-    const uint32_t part = 0u;
-    if constexpr (REGS == REGS_BINS) {
-        regs = bin_regs_of<ALGO>(a, it.genome);
-        census = lds_regs;
-    } else if constexpr (REGS == REGS_BYTES) {
-        if ((uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint32_t *)lds_regs != 0u) __builtin_trap();
-        regs.p = p;
-        census = lds_regs + a.nreg32;
-        for (uint32_t i = threadIdx.x; i < a.nreg32; i += blockDim.x) lds_regs[i] = ALGO == 2 ? 0u : RANK_EMPTY;
-    } else if constexpr (USE_LDS) {
-        if ((uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint32_t *)lds_regs != 0u) __builtin_trap();
-        regs.base = lds_regs;
-        census = lds_regs + a.nreg32;
-        for (uint32_t i = threadIdx.x; i < a.nreg32; i += blockDim.x) lds_regs[i] = ALGO == 2 ? 0u : RANK_EMPTY;
-    } else {
-        regs.base = a.gregs + (uint64_t)(item - a.item_base) * a.nreg32;   // (tables of the items of this launch: lash_api.hip, global_run)
-        census = lds_regs;
-    }
+    bind_regs<ALGO, REGS>(a, it, item, lds_regs, regs, census);
+    if constexpr (REGS == REGS_LDS || REGS == REGS_BYTES) arm_table<ALGO>(a, lds_regs);   // (the barrier: behind the rings' clear, below)
     const bool multi_rec = gd.rec_end - gd.rec_begin > 1;
     uint32_t RL = 0;
     if (multi_rec && a.nonuniform[it.genome] == 0u) RL = (uint32_t)(a.rec_off[gd.rec_begin + 1] - a.rec_off[gd.rec_begin]);
@@ -463,14 +376,7 @@ __global__ void __launch_bounds__(1024) stream_sketch_kernel(SketchArgs a)
     const bool breaks = bk != nullptr || RL != 0u;
     const uint8_t *__restrict__ gseq = a.seq + gd.byte_off;
     KParams kp;
-    kp.bitflip = BitFlip::vector(a.bitflip);
-    kp.p = p;
-    kp.sh_lt = 32u - 2u * (uint32_t)k;
-    kp.mask_lt = (KMODE == KM_LT16) ? ((1u << (2 * k)) - 1u) : 0xFFFFFFFFu;
-    kp.sh_gt = 64u - 2u * (uint32_t)k;
-    kp.mask_gt = (k == 32) ? ~0ull : ((1ull << (2 * k)) - 1ull);
-    kp.mask_hi = (uint32_t)(kp.mask_gt >> 32);
-    kp.to_vector_registers();
+    kp.set_hashing<KMODE>(k, p, a.bitflip);
     const uint32_t cmask = a.lay.comp_mask;
     const CodeTabs ct{a.lay.code_lo, a.lay.code_hi};
 
@@ -499,7 +405,7 @@ __global__ void __launch_bounds__(1024) stream_sketch_kernel(SketchArgs a)
             const uint32_t pos0 = 32u * lane;
             const bool active = pos0 < nstarts;
             const uint32_t junk = (threadIdx.x + 1u) * 0x9E3779B1u;
-            uint32_t c0 = junk, c1 = ~junk, c2 = junk, c3 = ~junk;
+            uint32_t c0 = junk, c1 = ~junk, c2 = junk, c3 = ~junk, c4 = 0, c5 = 0;   // (two words per lane: nothing beyond c3 is looked at)
             uint32_t kvw = 0;
             auto rw = [&](uint32_t j) { uint32_t w = head_w + 2u * lane + j; w = w >= RING_W ? w - RING_W : w; return w; };
             const uint32_t w0 = rw(0), w1 = rw(1);
@@ -522,31 +428,9 @@ __global__ void __launch_bounds__(1024) stream_sketch_kernel(SketchArgs a)
             uint32_t r0 = rcword(c0, cmask), r1 = rcword(c1, cmask), r2 = (KMODE == KM_GT16) ? rcword(c2, cmask) : 0u;
 #pragma unroll 1
             for (int wi = 0; wi < 2; ++wi) {
-                uint32_t z;
-                if constexpr (DEFER) {
-                    z = 0xFFFFFFFFu;                                           // (nothing to re-run: the full update does that itself)
-                    if (all_valid) process_word_defer<KMODE, false>(regs, kp, c0, c1, c2, r0, r1, r2, 0u, sigq);
-                    else {
-                        uint32_t m = kvw;
-                        asm volatile("" : "+v"(m));
-                        process_word_defer<KMODE, true>(regs, kp, c0, c1, c2, r0, r1, r2, m, sigq);
-                    }
-                } else if (all_valid) z = process_word<ALGO, KMODE, XLOW, false, true>(regs, kp, c0, c1, c2, r0, r1, r2, 0u);
-                else {
-                    uint32_t m = kvw;
-                    asm volatile("" : "+v"(m));
-                    z = process_word<ALGO, KMODE, XLOW, true, true>(regs, kp, c0, c1, c2, r0, r1, r2, m);
-                }
-                constexpr uint32_t Z_REDO = z_redo<ALGO, Regs>();
-                if (z <= Z_REDO) {
-                    uint32_t m = kvw;
-                    asm volatile("" : "+v"(m));
-                    (void)process_word<ALGO, KMODE, XLOW, true, false>(regs, kp, c0, c1, c2, r0, r1, r2, m);
-                }
+                hash_word<ALGO, KMODE, XLOW, Regs, 0, DEFER>(regs, kp, c0, c1, c2, r0, r1, r2, all_valid, kvw, sigq);
                 if constexpr (REGS == REGS_BINS) regs.flush(lane);
-                c0 = c1; c1 = c2; c2 = c3; c3 = 0;
-                r0 = r1;
-                if constexpr (KMODE == KM_GT16) { r1 = r2; r2 = rcword(c2, cmask); } else { r1 = rcword(c1, cmask); }
+                rotate_window<KMODE>(c0, c1, c2, c3, c4, c5, r0, r1, r2, cmask);
                 kvw >>= 16;
             }
             head_w += STREAM_BATCH / 16u;
@@ -736,76 +620,67 @@ __global__ void __launch_bounds__(1024) stream_sketch_kernel(SketchArgs a)
             if (ns < STREAM_BATCH) break;
         }
         // surviving bases of this wave's part (lash_timing::bases_last)
-        if (lane == 0 && part == 0u && a.ndel2) atomicAdd(a.ndel2 + it.genome, (uint32_t)(we - ws) - own_seen);
+        if (lane == 0 && a.ndel2) atomicAdd(a.ndel2 + it.genome, (uint32_t)(we - ws) - own_seen);
     }
     if constexpr (DEFER) sigq_drain<true>(regs, kp.bitflip, p, sigq);
-    finish_item<ALGO, REGS, Regs>(a, it, regs, census, part, my_kmers, p, item);
+    finish_item<ALGO, REGS, Regs>(a, it, regs, census, my_kmers, p, item);
 }
 
-template <int ALGO, int KMODE, bool XLOW, int REGS>
-static hipError_t launch_stream_one(const SketchPlan &plan, const SketchArgs &args, uint32_t n_items, hipStream_t stream)
+// ------------------------------------------------------------------------------------------------------------
+// host side: ONE table from a plan to a kernel's template arguments.  with_plan_tags turns plan.algo, plan.variant, plan.k and the
+// plan's register mode into compile-time tags (`tag::value`) and hands them to the route — a generic lambda that knows its kernel,
+// its LDS arithmetic, and which combinations it has (`if constexpr`; the others are hipErrorInvalidValue).
+// ------------------------------------------------------------------------------------------------------------
+template <int V> using Tag = std::integral_constant<int, V>;
+template <class Route>
+static hipError_t with_plan_tags(const SketchPlan &plan, Route route)
 {
-    auto kern = stream_sketch_kernel<ALGO, KMODE, XLOW, REGS>;
-    uint32_t threads = plan.threads, stacks = 0;
-    SketchArgs a = args;
-    if constexpr (ALGO == 0 && REGS == REGS_LDS) {
-        if (plan.defer) {                                                  // (see the kernel: 1 024 threads, the lanes' stacks behind the rings)
-            kern = stream_sketch_kernel<ALGO, KMODE, XLOW, REGS, true>;
-            threads = 1024u;
-            stacks = (threads / 64u) * 64u * plan.sigq_depth * 4u;
-        }
+    auto regs = [&](auto algo, auto xlow, auto kmode) {
+        if (plan.bytes) return route(algo, xlow, kmode, Tag<REGS_BYTES>{});
+        if (plan.bins) return route(algo, xlow, kmode, Tag<REGS_BINS>{});
+        if (plan.use_lds) return route(algo, xlow, kmode, Tag<REGS_LDS>{});
+        return route(algo, xlow, kmode, Tag<REGS_GLOBAL>{});
+    };
+    auto kmode = [&](auto algo, auto xlow) {
+        if (plan.k == 16) return regs(algo, xlow, Tag<KM_16>{});
+        if (plan.k < 16) return regs(algo, xlow, Tag<KM_LT16>{});
+        return regs(algo, xlow, Tag<KM_GT16>{});
+    };
+    switch (plan.algo) {
+    case 0: return plan.variant ? kmode(Tag<0>{}, std::true_type{}) : kmode(Tag<0>{}, std::false_type{});
+    case 1: return plan.variant ? kmode(Tag<1>{}, std::true_type{}) : kmode(Tag<1>{}, std::false_type{});
+    case 2: return kmode(Tag<2>{}, std::false_type{});
+    default: return hipErrorInvalidValue;
     }
-    a.stage_off = plan.lds_bytes;
-    a.sigq_depth = plan.sigq_depth;
-    a.bin_lds_off = plan.lds_bytes + (threads / 64u) * (DENSE_STAGE_WORDS * 4u) + stacks;
-    a.bin_wave_bytes = sketch_bin_wave_bytes(plan);
-    const uint32_t lds = a.bin_lds_off + (threads / 64u) * a.bin_wave_bytes;
-    if (lds > 48u * 1024u) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL(kern, dim3(n_items), dim3(threads), lds, stream, a);
-    return hipGetLastError();
 }
-
-template <int ALGO, bool XLOW>
-static hipError_t launch_stream_kmode(const SketchPlan &plan, const SketchArgs &args, uint32_t n, hipStream_t s)
-{
-    const int km = plan.k == 16 ? KM_16 : plan.k < 16 ? KM_LT16 : KM_GT16;
-    if constexpr (ALGO != 0) {
-        if (plan.bytes) {
-            if (km == KM_16) return launch_stream_one<ALGO, KM_16, XLOW, REGS_BYTES>(plan, args, n, s);
-            if (km == KM_LT16) return launch_stream_one<ALGO, KM_LT16, XLOW, REGS_BYTES>(plan, args, n, s);
-            return launch_stream_one<ALGO, KM_GT16, XLOW, REGS_BYTES>(plan, args, n, s);
-        }
-        if (plan.bins) {
-            if (km == KM_16) return launch_stream_one<ALGO, KM_16, XLOW, REGS_BINS>(plan, args, n, s);
-            if (km == KM_LT16) return launch_stream_one<ALGO, KM_LT16, XLOW, REGS_BINS>(plan, args, n, s);
-            return launch_stream_one<ALGO, KM_GT16, XLOW, REGS_BINS>(plan, args, n, s);
-        }
-    }
-    if (plan.use_lds) {
-        if (km == KM_16) return launch_stream_one<ALGO, KM_16, XLOW, REGS_LDS>(plan, args, n, s);
-        if (km == KM_LT16) return launch_stream_one<ALGO, KM_LT16, XLOW, REGS_LDS>(plan, args, n, s);
-        return launch_stream_one<ALGO, KM_GT16, XLOW, REGS_LDS>(plan, args, n, s);
-    }
-    if constexpr (ALGO == 2) {
-        if (km == KM_16) return launch_stream_one<ALGO, KM_16, XLOW, REGS_GLOBAL>(plan, args, n, s);
-        if (km == KM_LT16) return launch_stream_one<ALGO, KM_LT16, XLOW, REGS_GLOBAL>(plan, args, n, s);
-        return launch_stream_one<ALGO, KM_GT16, XLOW, REGS_GLOBAL>(plan, args, n, s);
-    }
-    return hipErrorInvalidValue;
-}
+// the tables the nucleotide kernels have: HyperMinHash's always fits LDS as words; only UltraLogLog outgrows the bins
+constexpr bool table_exists(int algo, int regs) { return regs == REGS_LDS || algo == 2 || (algo == 1 && regs != REGS_GLOBAL); }
 
 hipError_t launch_sketch_stream(const SketchPlan &plan, const SketchArgs &args, uint32_t n_items, hipStream_t stream)
 {
     if (n_items == 0) return hipSuccess;
-    switch (plan.algo) {
-    case 0: return plan.variant ? launch_stream_kmode<0, true>(plan, args, n_items, stream) : launch_stream_kmode<0, false>(plan, args, n_items, stream);
-    case 1: return plan.variant ? launch_stream_kmode<1, true>(plan, args, n_items, stream) : launch_stream_kmode<1, false>(plan, args, n_items, stream);
-    case 2: return launch_stream_kmode<2, false>(plan, args, n_items, stream);
-    default: return hipErrorInvalidValue;
-    }
+    return with_plan_tags(plan, [&](auto algo, auto xlow, auto kmode, auto regs) {
+        constexpr int ALGO = decltype(algo)::value, KMODE = decltype(kmode)::value, REGS = decltype(regs)::value;
+        constexpr bool XLOW = decltype(xlow)::value;
+        if constexpr (!table_exists(ALGO, REGS)) return hipErrorInvalidValue;
+        else {
+            auto kern = stream_sketch_kernel<ALGO, KMODE, XLOW, REGS>;
+            uint32_t threads = plan.threads, stacks = 0;
+            SketchArgs a = args;
+            if constexpr (ALGO == 0 && REGS == REGS_LDS) {
+                if (plan.defer) {                                          // (see the kernel: 1 024 threads, the lanes' stacks behind the rings)
+                    kern = stream_sketch_kernel<ALGO, KMODE, XLOW, REGS, true>;
+                    threads = 1024u;
+                    stacks = (threads / 64u) * 64u * plan.sigq_depth * 4u;
+                }
+            }
+            a.stage_off = plan.lds_bytes;
+            a.sigq_depth = plan.sigq_depth;
+            a.bin_lds_off = plan.lds_bytes + (threads / 64u) * (DENSE_STAGE_WORDS * 4u) + stacks;
+            a.bin_wave_bytes = sketch_bin_wave_bytes(plan);
+            return launch_dyn_lds(kern, dim3(n_items), dim3(threads), a.bin_lds_off + (threads / 64u) * a.bin_wave_bytes, stream, a);
+        }
+    });
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -831,30 +706,11 @@ __global__ void __launch_bounds__(1024) aa_sketch_kernel(SketchArgs a)
     const WorkItem it = a.items[item];
     const GenomeDesc gd = a.genomes[it.genome];
     const int k = a.k, p = a.p;
-    constexpr bool USE_LDS = REGS != REGS_GLOBAL;
-    using Regs = typename std::conditional<REGS == REGS_LDS, LdsRegs,
-                                           typename std::conditional<REGS == REGS_GLOBAL, GlobalRegs,
-                                           typename std::conditional<REGS == REGS_BINS, BinRegs, LdsByteRegs>::type>::type>::type;
+    using Regs = SketchRegs<ALGO, REGS, XLOW, false, false>;
     Regs regs;
     uint32_t *census;
-    const uint32_t part = 0u;
-    if constexpr (REGS == REGS_BINS) {
-        regs = bin_regs_of<ALGO>(a, it.genome);
-        census = lds_regs;
-    } else if constexpr (REGS == REGS_BYTES) {
-        if ((uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint32_t *)lds_regs != 0u) __builtin_trap();
-        regs.p = p;
-        census = lds_regs + a.nreg32;
-        for (uint32_t i = threadIdx.x; i < a.nreg32; i += blockDim.x) lds_regs[i] = ALGO == 2 ? 0u : RANK_EMPTY;
-    } else if constexpr (USE_LDS) {
-        if ((uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint32_t *)lds_regs != 0u) __builtin_trap();
-        regs.base = lds_regs;
-        census = lds_regs + a.nreg32;
-        for (uint32_t i = threadIdx.x; i < a.nreg32; i += blockDim.x) lds_regs[i] = ALGO == 2 ? 0u : RANK_EMPTY;
-    } else {
-        regs.base = a.gregs + (uint64_t)(item - a.item_base) * a.nreg32;   // (tables of the items of this launch: lash_api.hip, global_run)
-        census = lds_regs;
-    }
+    bind_regs<ALGO, REGS>(a, it, item, lds_regs, regs, census);
+    if constexpr (REGS == REGS_LDS || REGS == REGS_BYTES) arm_table<ALGO>(a, lds_regs);   // (the barrier: behind the code table, below)
     // after the census + histogram words (16 + 72): the record counter, then the byte -> code table
     uint32_t *const next_rec = census + 88;
     uint8_t *const code_tab = reinterpret_cast<uint8_t *>(census + 92);
@@ -924,39 +780,20 @@ __global__ void __launch_bounds__(1024) aa_sketch_kernel(SketchArgs a)
         }
         if constexpr (REGS == REGS_BINS) regs.flush(threadIdx.x & 63u);
     }
-    finish_item<ALGO, REGS, Regs>(a, it, regs, census, part, wave_sum(my_kmers), p, item);
-}
-
-template <int ALGO, bool XLOW>
-static hipError_t launch_aa_regs(const SketchPlan &plan, const SketchArgs &args, uint32_t n, hipStream_t s)
-{
-    auto go = [&](auto kern) {
-        SketchArgs a = args;
-        a.bin_lds_off = plan.lds_bytes + 16u + 256u;                             // + the record counter and the byte -> code table
-        a.bin_wave_bytes = sketch_bin_wave_bytes(plan);
-        const uint32_t lds = a.bin_lds_off + (plan.threads / 64u) * a.bin_wave_bytes;
-        if (lds > 48u * 1024u) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess) return e;
-        }
-        hipLaunchKernelGGL(kern, dim3(n), dim3(plan.threads), lds, s, a);
-        return hipGetLastError();
-    };
-    if (plan.bytes) return go(aa_sketch_kernel<ALGO, XLOW, REGS_BYTES>);
-    if (plan.bins) return go(aa_sketch_kernel<ALGO, XLOW, REGS_BINS>);
-    if (plan.use_lds) return go(aa_sketch_kernel<ALGO, XLOW, REGS_LDS>);
-    return go(aa_sketch_kernel<ALGO, XLOW, REGS_GLOBAL>);
+    finish_item<ALGO, REGS, Regs>(a, it, regs, census, wave_sum(my_kmers), p, item);
 }
 
 hipError_t launch_sketch_aa(const SketchPlan &plan, const SketchArgs &args, uint32_t n_items, hipStream_t stream)
 {
     if (n_items == 0) return hipSuccess;
-    switch (plan.algo) {
-    case 0: return plan.variant ? launch_aa_regs<0, true>(plan, args, n_items, stream) : launch_aa_regs<0, false>(plan, args, n_items, stream);
-    case 1: return plan.variant ? launch_aa_regs<1, true>(plan, args, n_items, stream) : launch_aa_regs<1, false>(plan, args, n_items, stream);
-    case 2: return launch_aa_regs<2, false>(plan, args, n_items, stream);
-    default: return hipErrorInvalidValue;
-    }
+    // (k <= 12: the k-mode plays no part; every algorithm has every register mode here)
+    return with_plan_tags(plan, [&](auto algo, auto xlow, auto, auto regs) {
+        SketchArgs a = args;
+        a.bin_lds_off = plan.lds_bytes + 16u + 256u;                             // + the record counter and the byte -> code table
+        a.bin_wave_bytes = sketch_bin_wave_bytes(plan);
+        return launch_dyn_lds(aa_sketch_kernel<decltype(algo)::value, decltype(xlow)::value, decltype(regs)::value>, dim3(n_items), dim3(plan.threads),
+                              a.bin_lds_off + (plan.threads / 64u) * a.bin_wave_bytes, stream, a);
+    });
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -968,23 +805,23 @@ hipError_t launch_sketch_aa(const SketchPlan &plan, const SketchArgs &args, uint
 template <int ALGO>
 __global__ void __launch_bounds__(256) reduce_groups_kernel(FinalizeArgs a, uint32_t R, uint32_t stride)
 {
-    const uint32_t g = blockIdx.y, P = 1u << a.parts_log2, part = blockIdx.x % P, j = blockIdx.x / P;
+    const uint32_t g = blockIdx.y;
     const uint32_t i0 = a.genome_item_begin[g], i1 = a.genome_item_begin[g + 1];
-    const uint32_t n_slices = (i1 - i0) / P, n_units = (n_slices + stride - 1) / stride, u0 = j * R;
+    const uint32_t n_slices = i1 - i0, n_units = (n_slices + stride - 1) / stride, u0 = blockIdx.x * R;
     if (u0 >= n_units) return;
     const uint32_t u1 = u0 + R < n_units ? u0 + R : n_units;
     uint64_t nk = ~0ull;
     if (a.nvalid) { const uint64_t L = a.nvalid[g]; nk = L >= (uint64_t)a.k ? L - (uint64_t)a.k + 1 : 0; }
     auto live = [&](uint32_t it) { return stride > 1u || (uint64_t)a.items[it].word_begin * 16 < nk; };   // heads always are
-    const uint32_t nwords = (ALGO == 0 ? HMH_M * 2 : (1u << a.p)) >> 2, nw_part = nwords >> a.parts_log2, wbase = part * nw_part;
-    const uint32_t head = i0 + u0 * stride * P + part;
+    const uint32_t nwords = (ALGO == 0 ? HMH_M * 2 : (1u << a.p)) >> 2;
+    const uint32_t head = i0 + u0 * stride;
     uint8_t *dst = const_cast<uint8_t *>(a.partials) + (uint64_t)head * a.partial_stride + a.partial_base_off;
-    // blockIdx.z splits the pass's words so that a thread folds one word: R independent loads, no serial walk
-    for (uint32_t wi = wbase + blockIdx.z * blockDim.x + threadIdx.x; wi < wbase + nw_part; wi += gridDim.z * blockDim.x) {
+    // blockIdx.z splits the words so that a thread folds one word: R independent loads, no serial walk
+    for (uint32_t wi = blockIdx.z * blockDim.x + threadIdx.x; wi < nwords; wi += gridDim.z * blockDim.x) {
         uint32_t acc = 0;
 #pragma unroll 8
         for (uint32_t u = u0; u < u1; ++u) {
-            const uint32_t it = i0 + u * stride * P + part;
+            const uint32_t it = i0 + u * stride;
             if (!live(it)) continue;                                       // slice never ran: its partial is not defined
             acc = merge_word<ALGO>(acc, load_u32_any(a.partials + (uint64_t)it * a.partial_stride + a.partial_base_off + 4ull * wi));
         }
@@ -993,7 +830,7 @@ __global__ void __launch_bounds__(256) reduce_groups_kernel(FinalizeArgs a, uint
     if (a.item_kmers && threadIdx.x == 0 && blockIdx.z == 0) {
         uint32_t tot = 0;
         for (uint32_t u = u0; u < u1; ++u) {
-            const uint32_t it = i0 + u * stride * P + part;
+            const uint32_t it = i0 + u * stride;
             if (live(it)) tot += a.item_kmers[it];
         }
         const_cast<uint32_t *>(a.item_kmers)[head] = tot;
@@ -1008,8 +845,8 @@ hipError_t launch_reduce_groups(const FinalizeArgs &args, uint32_t n_genomes, ui
     constexpr uint32_t R = 32;
     for (uint32_t stride = 1; stride < args.group; stride *= R) {
         const uint32_t units = (max_slices + stride - 1) / stride, groups = (units + R - 1) / R;
-        const uint32_t nw_part = ((args.algo == 0 ? HMH_M * 2 : (1u << args.p)) >> 2) >> args.parts_log2;
-        dim3 grid(groups << args.parts_log2, n_genomes, std::max(1u, std::min(nw_part / 256u, 64u)));
+        const uint32_t nwords = (args.algo == 0 ? HMH_M * 2 : (1u << args.p)) >> 2;
+        dim3 grid(groups, n_genomes, std::max(1u, std::min(nwords / 256u, 64u)));
         switch (args.algo) {
         case 0: hipLaunchKernelGGL(reduce_groups_kernel<0>, grid, dim3(256), 0, stream, args, R, stride); break;
         case 1: hipLaunchKernelGGL(reduce_groups_kernel<1>, grid, dim3(256), 0, stream, args, R, stride); break;
@@ -1038,12 +875,12 @@ __global__ void __launch_bounds__(1024) finalize_kernel(FinalizeArgs a)
     uint8_t *img = a.images + (uint64_t)g * a.image_bytes;
     if (threadIdx.x < 72) hist[threadIdx.x] = 0;
     __syncthreads();
-    // items of a genome are ordered slice-major, pass-minor: item = i0 + slice * P + pass.  After launch_reduce_groups()
-    // only every `group`-th slice (a group head, always treated as live) still matters.
-    const uint32_t P = 1u << a.parts_log2, step = (a.group ? a.group : 1u) * P;
+    // items of a genome are its slices in order: item = i0 + slice.  After launch_reduce_groups() only every `group`-th slice
+    // (a group head, always treated as live) still matters.
+    const uint32_t step = a.group ? a.group : 1u;
     if (a.item_kmers && threadIdx.x == 0) {
         unsigned long long tot = 0;
-        for (uint32_t it = i0; it < i1; it += step)                        // pass 0 carries the count of its slice
+        for (uint32_t it = i0; it < i1; it += step)
             if (a.group || (uint64_t)a.items[it].word_begin * 16 < nk) tot += a.item_kmers[it];
         if (tot) atomicAdd(a.kmer_counter, tot);
     }
@@ -1053,8 +890,7 @@ __global__ void __launch_bounds__(1024) finalize_kernel(FinalizeArgs a)
     HllTally tally;
     for (uint32_t wi = threadIdx.x; wi < nwords; wi += blockDim.x) {
         uint32_t acc = a.accumulate ? hmh_img_order(load_u32_any(img + hdr + 4ull * wi), reg_be) : 0u;
-        const uint32_t part = a.parts_log2 ? wi / (nwords >> a.parts_log2) : 0u;   // whose pass wrote this word
-        for (uint32_t it = i0 + part; it < i1; it += step) {
+        for (uint32_t it = i0; it < i1; it += step) {
             if (!a.group && (uint64_t)a.items[it].word_begin * 16 >= nk) continue;   // slice never ran (see sketch_kernel)
             const uint8_t *src = a.partials + (uint64_t)it * a.partial_stride + a.partial_base_off;
             acc = merge_word<ALGO>(acc, hmh_img_order(load_u32_any(src + 4ull * wi), src_be));
@@ -1228,15 +1064,7 @@ hipError_t launch_bins_apply(const BinApplyArgs &args, uint32_t n_group_genomes,
 {
     if (n_group_genomes == 0) return hipSuccess;
     const uint32_t words = 1u << args.bin_shift, lds = (words + 1u + BINS_APPLY_RARE) * 4u;   // one word per register + the short list of rare entries
-    auto go = [&](auto kern) {
-        if (lds > 48u * 1024u) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess) return e;
-        }
-        hipLaunchKernelGGL(kern, dim3(args.bins, n_group_genomes), dim3(1024), lds, stream, args);
-        return hipGetLastError();
-    };
-    return args.algo == 2 ? go(bins_apply_kernel<2>) : go(bins_apply_kernel<1>);
+    return launch_dyn_lds(args.algo == 2 ? bins_apply_kernel<2> : bins_apply_kernel<1>, dim3(args.bins, n_group_genomes), dim3(1024), lds, stream, args);
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -1251,7 +1079,6 @@ SketchPlan make_sketch_plan(int algo, int k, int p, bool variant, bool small_ite
     else { s.nreg32 = 2u << p; s.partial_bytes = 1u << p; }
     s.partial_stride = (s.partial_bytes + 15u) & ~15u;
     s.lds_bytes = s.nreg32 * 4u;
-    s.parts_log2 = 0;
     // tables beyond 128 KiB: binned (BinRegs; up to 256 bins: HLL p = 16, ULL p = 15 .. 23), beyond that a table in global
     // memory per work item and one atomic per k-mer (ULL p >= 24)
     uint32_t bl = 0;
@@ -1297,7 +1124,7 @@ SketchPlan make_sketch_plan(int algo, int k, int p, bool variant, bool small_ite
     // batch is per-workgroup latency (item / descriptor / first tile loads, flush), not issue slots -> 256-thread
     // workgroups, as many per CU as the table allows (100 000 x 10 kbp, hll p=10: 4.4 -> 2.7 ms).  HyperMinHash's 64 KiB
     // table admits two workgroups per CU whatever their size, and smaller ones only lose lanes.
-    const bool many_small = small_items && s.use_lds && s.parts_log2 == 0 && s.lds_bytes <= 32u * 1024u;
+    const bool many_small = small_items && s.use_lds && s.lds_bytes <= 32u * 1024u;
     if (many_small) s.threads = 256u;
     if (const char *e = getenv("LASH_SKETCH_THREADS")) {                    // tuning knob (tools/)
         const int t = atoi(e);
@@ -1326,93 +1153,42 @@ static uint32_t stage_stride_bytes(const SketchPlan &plan, bool direct, bool def
 uint32_t sketch_direct_stage_bytes(const SketchPlan &plan) { return (plan.threads / 64u) * stage_stride_bytes(plan, true, true); }
 uint32_t sketch_bin_wave_bytes(const SketchPlan &plan) { return plan.bins ? ((1u << (plan.bins_log2 + plan.bin_sub_shift)) * (1u + bin_row_stride(plan.bin_S))) * 4u : 0u; }
 
-template <int ALGO, int KMODE, bool XLOW, int REGS, bool DIRECT, bool KEEP = false>
-static hipError_t launch_one(const SketchPlan &plan, const SketchArgs &args, uint32_t n_items, hipStream_t stream)
+// sketch_kernel's routes: packed (DIRECT = false), direct, and the packed launch under keep bits
+template <bool DIRECT, bool KEEP>
+static hipError_t launch_sliced(const SketchPlan &plan, const SketchArgs &args, uint32_t n_items, hipStream_t stream)
 {
-    auto kern = sketch_kernel<ALGO, KMODE, XLOW, KEEP ? REGS_LDS_KEEP : REGS, DIRECT>;
-    bool defer = false;
-    if constexpr (ALGO == 0 && REGS == REGS_LDS && !KEEP) {
-        if (plan.defer) { kern = sketch_kernel<ALGO, KMODE, XLOW, REGS, DIRECT, true>; defer = true; }
-    }
-    SketchArgs a = args;
-    a.stage_off = plan.lds_bytes;                                          // direct mode: the waves' staging areas follow (dense_tile);
-    a.stage_stride = stage_stride_bytes(plan, DIRECT, defer || REGS == REGS_BYTES);   // deferring launches keep their lanes' stacks there, the byte tables' theirs
-    a.sigq_depth = plan.sigq_depth;
-    a.bin_lds_off = plan.lds_bytes + (plan.threads / 64u) * a.stage_stride;
-    a.bin_wave_bytes = sketch_bin_wave_bytes(plan);
-    const uint32_t lds = a.bin_lds_off + (plan.threads / 64u) * a.bin_wave_bytes;
-    if (lds > 48u * 1024u) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL(kern, dim3(n_items), dim3(plan.threads), lds, stream, a);
-    return hipGetLastError();
-}
-
-template <int ALGO, bool XLOW, bool DIRECT>
-static hipError_t launch_kmode(const SketchPlan &plan, const SketchArgs &args, uint32_t n, hipStream_t s)
-{
-    const int km = plan.k == 16 ? KM_16 : plan.k < 16 ? KM_LT16 : KM_GT16;
-    if constexpr (ALGO != 0) {                                  // HMH's table always fits
-        if (plan.bytes) {
-            if (km == KM_16) return launch_one<ALGO, KM_16, XLOW, REGS_BYTES, DIRECT>(plan, args, n, s);
-            if (km == KM_LT16) return launch_one<ALGO, KM_LT16, XLOW, REGS_BYTES, DIRECT>(plan, args, n, s);
-            return launch_one<ALGO, KM_GT16, XLOW, REGS_BYTES, DIRECT>(plan, args, n, s);
+    return with_plan_tags(plan, [&](auto algo, auto xlow, auto kmode, auto regs) {
+        constexpr int ALGO = decltype(algo)::value, KMODE = decltype(kmode)::value, REGS = decltype(regs)::value;
+        constexpr bool XLOW = decltype(xlow)::value;
+        if constexpr (!table_exists(ALGO, REGS) || (KEEP && REGS != REGS_LDS)) return hipErrorInvalidValue;
+        else {
+            auto kern = sketch_kernel<ALGO, KMODE, XLOW, KEEP ? REGS_LDS_KEEP : REGS, DIRECT>;
+            bool defer = false;
+            if constexpr (ALGO == 0 && REGS == REGS_LDS && !KEEP) {
+                if (plan.defer) { kern = sketch_kernel<ALGO, KMODE, XLOW, REGS, DIRECT, true>; defer = true; }
+            }
+            SketchArgs a = args;
+            a.stage_off = plan.lds_bytes;                                  // direct mode: the waves' staging areas follow (dense_tile);
+            a.stage_stride = stage_stride_bytes(plan, DIRECT, defer || REGS == REGS_BYTES);   // deferring launches keep their lanes' stacks there, the byte tables' theirs
+            a.sigq_depth = plan.sigq_depth;
+            a.bin_lds_off = plan.lds_bytes + (plan.threads / 64u) * a.stage_stride;
+            a.bin_wave_bytes = sketch_bin_wave_bytes(plan);
+            return launch_dyn_lds(kern, dim3(n_items), dim3(plan.threads), a.bin_lds_off + (plan.threads / 64u) * a.bin_wave_bytes, stream, a);
         }
-        if (plan.bins) {
-            if (km == KM_16) return launch_one<ALGO, KM_16, XLOW, REGS_BINS, DIRECT>(plan, args, n, s);
-            if (km == KM_LT16) return launch_one<ALGO, KM_LT16, XLOW, REGS_BINS, DIRECT>(plan, args, n, s);
-            return launch_one<ALGO, KM_GT16, XLOW, REGS_BINS, DIRECT>(plan, args, n, s);
-        }
-    }
-    if (plan.use_lds) {
-        if (km == KM_16) return launch_one<ALGO, KM_16, XLOW, REGS_LDS, DIRECT>(plan, args, n, s);
-        if (km == KM_LT16) return launch_one<ALGO, KM_LT16, XLOW, REGS_LDS, DIRECT>(plan, args, n, s);
-        return launch_one<ALGO, KM_GT16, XLOW, REGS_LDS, DIRECT>(plan, args, n, s);
-    }
-    if constexpr (ALGO == 2) {                                  // only ULL p >= 19 outgrows the partitioned LDS passes
-        if (km == KM_16) return launch_one<ALGO, KM_16, XLOW, REGS_GLOBAL, DIRECT>(plan, args, n, s);
-        if (km == KM_LT16) return launch_one<ALGO, KM_LT16, XLOW, REGS_GLOBAL, DIRECT>(plan, args, n, s);
-        return launch_one<ALGO, KM_GT16, XLOW, REGS_GLOBAL, DIRECT>(plan, args, n, s);
-    }
-    return hipErrorInvalidValue;
-}
-
-template <bool DIRECT>
-static hipError_t launch_algo(const SketchPlan &plan, const SketchArgs &args, uint32_t n_items, hipStream_t stream)
-{
-    switch (plan.algo) {
-    case 0: return plan.variant ? launch_kmode<0, true, DIRECT>(plan, args, n_items, stream) : launch_kmode<0, false, DIRECT>(plan, args, n_items, stream);
-    case 1: return plan.variant ? launch_kmode<1, true, DIRECT>(plan, args, n_items, stream) : launch_kmode<1, false, DIRECT>(plan, args, n_items, stream);
-    case 2: return launch_kmode<2, false, DIRECT>(plan, args, n_items, stream);
-    default: return hipErrorInvalidValue;
-    }
+    });
 }
 
 hipError_t launch_sketch(const SketchPlan &plan, const SketchArgs &args, uint32_t n_items, hipStream_t stream, bool direct)
 {
     if (n_items == 0) return hipSuccess;
-    return direct ? launch_algo<true>(plan, args, n_items, stream) : launch_algo<false>(plan, args, n_items, stream);
-}
-
-template <int ALGO, bool XLOW>
-static hipError_t launch_keep_kmode(const SketchPlan &plan, const SketchArgs &args, uint32_t n, hipStream_t s)
-{
-    if (plan.k == 16) return launch_one<ALGO, KM_16, XLOW, REGS_LDS, false, true>(plan, args, n, s);
-    if (plan.k < 16) return launch_one<ALGO, KM_LT16, XLOW, REGS_LDS, false, true>(plan, args, n, s);
-    return launch_one<ALGO, KM_GT16, XLOW, REGS_LDS, false, true>(plan, args, n, s);
+    return direct ? launch_sliced<true, false>(plan, args, n_items, stream) : launch_sliced<false, false>(plan, args, n_items, stream);
 }
 
 hipError_t launch_sketch_keep(const SketchPlan &plan, const SketchArgs &args, uint32_t n_items, hipStream_t stream)
 {
     if (!sketch_plan_keeps(plan) || plan.defer || !args.keep) return hipErrorInvalidValue;
     if (n_items == 0) return hipSuccess;
-    switch (plan.algo) {
-    case 0: return plan.variant ? launch_keep_kmode<0, true>(plan, args, n_items, stream) : launch_keep_kmode<0, false>(plan, args, n_items, stream);
-    case 1: return plan.variant ? launch_keep_kmode<1, true>(plan, args, n_items, stream) : launch_keep_kmode<1, false>(plan, args, n_items, stream);
-    case 2: return launch_keep_kmode<2, false>(plan, args, n_items, stream);
-    default: return hipErrorInvalidValue;
-    }
+    return launch_sliced<false, true>(plan, args, n_items, stream);
 }
 
 // Are all records of a genome the same length (a FASTQ read set)?  Then record starts are the multiples of that length and the

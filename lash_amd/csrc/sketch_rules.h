@@ -657,6 +657,25 @@ struct KParams {
             asm volatile("v_mov_b32 %0, %1" : "=v"(ull_sh28) : "s"(ull_sh28));
         }
     }
+    // the window fields of k-mers of k bases — all that a walk which hashes nothing with xxh3 needs (kmer_filter.hip)
+    template <int KMODE>
+    __device__ __forceinline__ void set_window(int k)
+    {
+        sh_lt = 32u - 2u * (uint32_t)k;
+        mask_lt = (KMODE == KM_LT16) ? ((1u << (2 * k)) - 1u) : 0xFFFFFFFFu;
+        sh_gt = 64u - 2u * (uint32_t)k;
+        mask_gt = (k == 32) ? ~0ull : ((1ull << (2 * k)) - 1ull);
+        mask_hi = (uint32_t)(mask_gt >> 32);
+    }
+    // ... and what the hashing kernels take: the seed's words, p, the window, the constants in vector registers
+    template <int KMODE>
+    __device__ __forceinline__ void set_hashing(int k, int p_, uint64_t seed_words)
+    {
+        bitflip = BitFlip::vector(seed_words);
+        p = p_;
+        set_window<KMODE>(k);
+        to_vector_registers();
+    }
 };
 
 // The canonical k-mer of start position r (0..15) of a word for 16 < k <= 32: the window's value, right-aligned, against the
@@ -854,7 +873,72 @@ __device__ __forceinline__ void process_word_defer(const Regs &regs, const KPara
 }
 
 // ------------------------------------------------------------------------------------------------------------
-// which work item a workgroup takes.  The hardware hands workgroup b to XCD b mod 8 (eight dies, each with its own workgroup slots and L2:
+// The word step of the walks that hash a lane's words one after the other (sketch_kernel's tile loop, stream_sketch_kernel's batches,
+// dense_tile; sole_sketch_kernel's one-word pass keeps a copy: through this helper its kernels took up to two more vector registers):
+// the 16 k-mers of (c0 c1 c2 | r0 r1 r2) through the rule's FAST form — without
+// masks when the whole wave holds nothing but k-mers (all_valid, wave-uniform), else under bits 15:0 of kv16 — and, when a FAST form
+// answers "rank not decided by the bits looked at" (HMH / x-high looks at 18 bits: 2^-18 per k-mer; the others at 32: 2^-32; z_redo),
+// the word again in the exact form: max / OR are idempotent.  DEFER: process_word_defer, whose full update does its own re-run.
+// K: the caller has a body for k = K at compile time (21: canon_gt16<21>) and says with k_is_K (kernel-uniform) whether this launch is one.
+// ------------------------------------------------------------------------------------------------------------
+template <int ALGO, int KMODE, bool XLOW, class Regs, int K = 0, bool DEFER = false>
+__device__ __forceinline__ void hash_word(const Regs &regs, const KParams &kp, uint32_t c0, uint32_t c1, uint32_t c2, uint32_t r0, uint32_t r1,
+                                          uint32_t r2, bool all_valid, uint32_t kv16, SigQueue &sigq, bool k_is_K = false)
+{
+    static_assert(!(DEFER && K != 0), "the deferring form has no compile-time k");
+    uint32_t z;
+    if constexpr (DEFER) {
+        z = 0xFFFFFFFFu;                                                   // (nothing to re-run)
+        if (all_valid) process_word_defer<KMODE, false>(regs, kp, c0, c1, c2, r0, r1, r2, 0u, sigq);
+        else {
+            uint32_t kvw = kv16;
+            asm volatile("" : "+v"(kvw));
+            process_word_defer<KMODE, true>(regs, kp, c0, c1, c2, r0, r1, r2, kvw, sigq);
+        }
+    } else if (K != 0 && k_is_K) {
+        if (all_valid) z = process_word<ALGO, KMODE, XLOW, false, true, Regs, K>(regs, kp, c0, c1, c2, r0, r1, r2, 0u);
+        else {
+            uint32_t kvw = kv16;
+            asm volatile("" : "+v"(kvw));
+            z = process_word<ALGO, KMODE, XLOW, true, true, Regs, K>(regs, kp, c0, c1, c2, r0, r1, r2, kvw);
+        }
+    } else if (all_valid) {
+        z = process_word<ALGO, KMODE, XLOW, false, true>(regs, kp, c0, c1, c2, r0, r1, r2, 0u);
+    } else {
+        // the masks are taken from an opaque copy so that hipcc cannot hoist the 16 v_bfe_i32 above the branch, where the (usual)
+        // all-valid path would pay for them too (so in every masked call here)
+        uint32_t kvw = kv16;
+        asm volatile("" : "+v"(kvw));
+        z = process_word<ALGO, KMODE, XLOW, true, true>(regs, kp, c0, c1, c2, r0, r1, r2, kvw);
+    }
+    constexpr uint32_t Z_REDO = z_redo<ALGO, Regs>();
+    if (z <= Z_REDO) {
+        uint32_t kvw = kv16;
+        asm volatile("" : "+v"(kvw));
+        (void)process_word<ALGO, KMODE, XLOW, true, false>(regs, kp, c0, c1, c2, r0, r1, r2, kvw);
+    }
+}
+// (the walks that never defer have no stacks to hand over)
+template <int ALGO, int KMODE, bool XLOW, class Regs, int K = 0>
+__device__ __forceinline__ void hash_word(const Regs &regs, const KParams &kp, uint32_t c0, uint32_t c1, uint32_t c2, uint32_t r0, uint32_t r1,
+                                          uint32_t r2, bool all_valid, uint32_t kv16, bool k_is_K = false)
+{
+    SigQueue none;
+    hash_word<ALGO, KMODE, XLOW, Regs, K, false>(regs, kp, c0, c1, c2, r0, r1, r2, all_valid, kv16, none, k_is_K);
+}
+
+// the window one word on: c0 .. c5 are the lane's words from the current one, r0 .. r2 the reverse complements the next word's k-mers need
+template <int KMODE>
+__device__ __forceinline__ void rotate_window(uint32_t &c0, uint32_t &c1, uint32_t &c2, uint32_t &c3, uint32_t &c4, uint32_t &c5, uint32_t &r0,
+                                              uint32_t &r1, uint32_t &r2, uint32_t cmask)
+{
+    c0 = c1; c1 = c2; c2 = c3; c3 = c4; c4 = c5; c5 = 0;
+    r0 = r1;
+    if constexpr (KMODE == KM_GT16) { r1 = r2; r2 = rcword(c2, cmask); } else { r1 = rcword(c1, cmask); }
+}
+
+// ------------------------------------------------------------------------------------------------------------
+// which work item a workgroup takes. The hardware hands workgroup b to XCD b mod 8 (eight dies, each with its own workgroup slots and L2:
 // nothing moves between them once dispatched) and, inside the die, to its four shader engines in turn ((b / 8) mod 4, measured with
 // LASH_ITEM_TRACE: profiles/r06/dirty_2500000_trace_*.txt) — 32 static classes of workgroup slots; only the CU inside a class is chosen
 // dynamically.  A launch whose items alternate between dear and cheap with a period that divides 32 — the two halves of genomes that are clean up
@@ -1505,23 +1589,8 @@ inline __device__ __noinline__ uint32_t dense_tile(const Regs regs, const KParam
     uint32_t r0 = rcword(c0, cmask), r1 = rcword(c1, cmask), r2 = (KMODE == KM_GT16) ? rcword(c2, cmask) : 0u;
 #pragma unroll 1
     for (uint32_t wi = 0; wi < wpl; ++wi) {
-        uint32_t z;
-        if (all_valid) {
-            z = process_word<ALGO, KMODE, XLOW, false, true>(regs, kp, c0, c1, c2, r0, r1, r2, 0u);
-        } else {
-            uint32_t kvw = (uint32_t)kv;
-            asm volatile("" : "+v"(kvw));
-            z = process_word<ALGO, KMODE, XLOW, true, true>(regs, kp, c0, c1, c2, r0, r1, r2, kvw);
-        }
-        constexpr uint32_t Z_REDO = z_redo<ALGO, Regs>();
-        if (z <= Z_REDO) {
-            uint32_t kvw = (uint32_t)kv;
-            asm volatile("" : "+v"(kvw));
-            (void)process_word<ALGO, KMODE, XLOW, true, false>(regs, kp, c0, c1, c2, r0, r1, r2, kvw);
-        }
-        c0 = c1; c1 = c2; c2 = c3; c3 = c4; c4 = c5; c5 = 0;
-        r0 = r1;
-        if constexpr (KMODE == KM_GT16) { r1 = r2; r2 = rcword(c2, cmask); } else { r1 = rcword(c1, cmask); }
+        hash_word<ALGO, KMODE, XLOW, Regs>(regs, kp, c0, c1, c2, r0, r1, r2, all_valid, (uint32_t)kv);
+        rotate_window<KMODE>(c0, c1, c2, c3, c4, c5, r0, r1, r2, cmask);
         kv >>= 16;
     }
     return added;
@@ -1564,9 +1633,80 @@ __device__ __forceinline__ BinRegs bin_regs_of(const SketchArgs &a, uint32_t gen
     return r;
 }
 
+// ------------------------------------------------------------------------------------------------------------
+// host side: a launch with `lds` bytes of dynamic LDS.  Beyond 48 KiB a kernel has to be told first (allow_dyn_lds: also what an
+// occupancy query of such a launch needs).
+// ------------------------------------------------------------------------------------------------------------
+template <class Kern>
+inline hipError_t allow_dyn_lds(Kern kern, uint32_t lds)
+{
+    if (lds <= 48u * 1024u) return hipSuccess;
+    return hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+}
+template <class Kern, class Args>
+inline hipError_t launch_dyn_lds(Kern kern, dim3 grid, dim3 threads, uint32_t lds, hipStream_t stream, const Args &args)
+{
+    const hipError_t e = allow_dyn_lds(kern, lds);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(kern, grid, threads, lds, stream, args);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------------------------
+// start of a work item, shared by the three SketchArgs kernels: which table type, where it lives, how it is armed
+// ------------------------------------------------------------------------------------------------------------
+// QUEUED: byte tables behind their filter (LdsByteQRegs: sketch_kernel) or with the plain compare-and-swap update
+template <int ALGO, int REGS, bool XLOW, bool DEFER, bool QUEUED>
+using SketchRegs = typename std::conditional<DEFER, typename std::conditional<XLOW, LdsThrRegsX, LdsThrRegs>::type,
+                            typename std::conditional<REGS == REGS_LDS, LdsRegs,
+                            typename std::conditional<REGS == REGS_GLOBAL, GlobalRegs,
+                            typename std::conditional<REGS == REGS_BINS, BinRegs,
+                            typename std::conditional<QUEUED, LdsByteQRegs<ALGO>, LdsByteRegs>::type>::type>::type>::type>::type;
+
+// dynamic LDS of those kernels: [nreg32 register words][16 words of per-wave census][72 of header histogram]; a table in LDS starts at LDS
+// address 0 (checked here), so that the bucket offset goes straight into the ds_max / ds_or address.  Binned launches hold no table (entries
+// for bins_apply_kernel), a table in global memory is this item's of the launch's (lash_api.hip, global_run; zeroed by the host).
 template <int ALGO, int REGS, class Regs>
-__device__ __forceinline__ void finish_item(const SketchArgs &a, const WorkItem &it, const Regs &regs, uint32_t *census, uint32_t part,
-                                            uint32_t my_kmers, int p, uint32_t item)
+__device__ __forceinline__ void bind_regs(const SketchArgs &a, const WorkItem &it, uint32_t item, uint32_t *lds_regs, Regs &regs, uint32_t *&census)
+{
+    if constexpr (REGS == REGS_BINS) {
+        regs = bin_regs_of<ALGO>(a, it.genome);
+        census = lds_regs;
+    } else if constexpr (REGS == REGS_GLOBAL) {
+        regs.base = a.gregs + (uint64_t)(item - a.item_base) * a.nreg32;
+        census = lds_regs;
+    } else {
+        if ((uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint32_t *)lds_regs != 0u) __builtin_trap();
+        if constexpr (REGS == REGS_BYTES) regs.p = a.p;
+        else regs.base = lds_regs;
+        census = lds_regs + a.nreg32;
+    }
+}
+// every word of a table in LDS to "empty" (only the loop: each kernel has its own barrier behind it)
+template <int ALGO>
+__device__ __forceinline__ void arm_table(const SketchArgs &a, uint32_t *lds_regs)
+{
+    for (uint32_t i = threadIdx.x; i < a.nreg32; i += blockDim.x) lds_regs[i] = ALGO == 2 ? 0u : RANK_EMPTY;
+}
+// The only work item of a genome too short for a single k-mer still owes the (empty) image; when the call unions into existing images
+// there is nothing to add.
+template <int ALGO>
+__device__ __forceinline__ void write_empty_sole_image(const SketchArgs &a, const WorkItem it, int p)
+{
+    if ((it.slice & ITEM_SOLE) && !a.accumulate) {
+        uint8_t *img = a.images + (uint64_t)it.genome * a.image_bytes;
+        for (uint64_t i = threadIdx.x; i < a.image_bytes; i += blockDim.x) img[i] = 0;
+        __syncthreads();
+        if (threadIdx.x == 0) {                                            // all registers 0: zero = m, sum = m * 2^-0
+            const uint64_t n_regs = ALGO == 0 ? HMH_M : (1ull << p);
+            write_header(img, a.lay.hdr_tpl, a.alpha_bits, n_regs, n_regs, (double)n_regs, ALGO == 0 ? HMH_P : p);
+        }
+    }
+}
+
+template <int ALGO, int REGS, class Regs>
+__device__ __forceinline__ void finish_item(const SketchArgs &a, const WorkItem &it, const Regs &regs, uint32_t *census, uint32_t my_kmers, int p,
+                                            uint32_t item)
 {
     // `item`: the work item's index (its slot in partials / item_kmers / gregs) — blockIdx.x unless the launch is ordered (a.item_order)
     constexpr bool USE_LDS = REGS != REGS_GLOBAL;
@@ -1578,8 +1718,7 @@ __device__ __forceinline__ void finish_item(const SketchArgs &a, const WorkItem 
     if (threadIdx.x == 0) {
         unsigned long long tot = 0;
         for (uint32_t i = 0; i < (blockDim.x >> 6); ++i) tot += census[i];
-        a.item_kmers[item] = part == 0u ? (uint32_t)tot : 0u;   // < 2^32 per slice; summed by finalize_kernel (the
-                                                                      // passes of one slice count the same k-mers: once)
+        a.item_kmers[item] = (uint32_t)tot;                               // < 2^32 per slice; summed by finalize_kernel
     }
 
     if constexpr (REGS == REGS_BINS) {

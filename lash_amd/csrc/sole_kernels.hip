@@ -177,14 +177,7 @@ __global__ void __launch_bounds__(512) sole_sketch_kernel(SoleArgs a)
     regs.base = lds_regs;
     const int k = a.k, p = a.p;
     KParams kp;
-    kp.bitflip = BitFlip::vector(a.bitflip);
-    kp.p = p;
-    kp.sh_lt = 32u - 2u * (uint32_t)k;
-    kp.mask_lt = (KMODE == KM_LT16) ? ((1u << (2 * k)) - 1u) : 0xFFFFFFFFu;
-    kp.sh_gt = 64u - 2u * (uint32_t)k;
-    kp.mask_gt = (k == 32) ? ~0ull : ((1ull << (2 * k)) - 1ull);
-    kp.mask_hi = (uint32_t)(kp.mask_gt >> 32);
-    kp.to_vector_registers();
+    kp.set_hashing<KMODE>(k, p, a.bitflip);
     const uint32_t cmask = a.lay.comp_mask;
     const CodeTabs ct{a.lay.code_lo, a.lay.code_hi};
     const uint32_t ring_b = a.ring_off, brk_b = a.brk_off, scan_b = a.scan_off;
@@ -253,6 +246,8 @@ __global__ void __launch_bounds__(512) sole_sketch_kernel(SoleArgs a)
         }
         const bool all_valid = __builtin_amdgcn_ballot_w64(kvw != 0xFFFFu) == 0ull;
         kmers_wave += all_valid ? 1024u : wave_sum((uint32_t)__builtin_popcount(kvw));
+        // the word step of hash_word (sketch_rules.h), kept as a copy: through the helper these kernels took up to two more vector registers.
+        // A change to the opaque mask, the k = 21 choice or the exact re-run there belongs here too.
         uint32_t z;
         if (K21 && k == 21) {
             if (all_valid) z = process_word<ALGO, KMODE, XLOW, false, true, LdsRegs, K21 ? 21 : 0>(regs, kp, c0, c1, c2, r0, r1, r2, 0u);
@@ -626,19 +621,16 @@ template <int ALGO, int KMODE, bool XLOW, bool PACKED>
 static hipError_t launch_sole_one(const SolePlan &plan, const SoleArgs &args, uint32_t n_wg, hipStream_t stream, uint32_t *occ)
 {
     auto kern = sole_sketch_kernel<ALGO, KMODE, XLOW, PACKED>;
-    if (plan.lds_bytes > 48u * 1024u) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.lds_bytes);
-        if (e != hipSuccess) return e;
-    }
     if (occ) {
         int n = 0;
-        hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, reinterpret_cast<const void *>(kern), (int)plan.threads, plan.lds_bytes);
+        hipError_t e = allow_dyn_lds(kern, plan.lds_bytes);
+        if (e != hipSuccess) return e;
+        e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, reinterpret_cast<const void *>(kern), (int)plan.threads, plan.lds_bytes);
         if (e != hipSuccess) return e;
         *occ = (uint32_t)std::max(1, n);
         return hipSuccess;
     }
-    hipLaunchKernelGGL(kern, dim3(n_wg), dim3(plan.threads), plan.lds_bytes, stream, args);
-    return hipGetLastError();
+    return launch_dyn_lds(kern, dim3(n_wg), dim3(plan.threads), plan.lds_bytes, stream, args);
 }
 template <int ALGO, bool XLOW, bool PACKED>
 static hipError_t launch_sole_kmode(const SolePlan &plan, int k, const SoleArgs &args, uint32_t n_wg, hipStream_t stream, uint32_t *occ)

@@ -420,7 +420,7 @@ def test_the_last_round_of_equal_items_is_cut_into_quarters(an, k, p):
     a launch").  220 genomes of 1.06 Mbp are 1 100 slices of 13 252 words; with 512 slots (hmh on a 256-CU part) the first 588 stay
     whole and the other 512 become four work items each — genomes with 5, 8..17 and 20 partials in one launch, which also takes
     the finalize stage through its grouped fold.  Some genomes in records, one soft-masked; the oracle checks a sample from both ends and
-    the middle, the census all of it.  hll p = 16 runs two bucket-space passes per slice on top."""
+    the middle, the census all of it.  hll p = 16 keeps its registers as bytes."""
     import lash_amd
     ctx = lash_amd.Context(0)
     n, L = 220, 1_060_000

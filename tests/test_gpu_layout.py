@@ -232,3 +232,49 @@ def test_a_packed_batch_belongs_to_the_code_table_it_was_packed_under(ctx):
         pk.free()
     finally:
         ctx.set_layout(None)
+
+
+# The launch table (with_plan_tags, sketch_kernels.hip) turns algorithm, variant, k-mode and register mode into one kernel per route.  The
+# cases above and the other modules reach most of its rungs; these are the ones they leave out, on the smallest shape: one genome of two
+# records, 40 and 70 bases with one N (two proteins of 15 and 30 residues for the amino-acid route), the smallest p that selects the mode.
+# LASH_NO_BYTES sends a byte-table plan to the bins, LASH_NO_BINS with it to the table in global memory.
+BINS = {"LASH_NO_BYTES": "1"}
+GLOBAL = {"LASH_NO_BYTES": "1", "LASH_NO_BINS": "1"}
+RUNG_CASES = [(spec, "hll", k, 16, BINS) for spec in (None, "hll_bucket=high") for k in (11, 16, 21)] + \
+             [("hll_bucket=high", "hll", 21, 16, {}), ("hll_bucket=high", "hll", 11, 10, {}), (None, "ull", 16, 15, GLOBAL), (None, "ull", 11, 15, GLOBAL)]
+AA_RUNG_CASES = [("hmh_x=low", "hmh", 0, {}), (None, "hll", 16, {}), (None, "hll", 16, BINS), ("hll_bucket=high", "hll", 10, {}),
+                 ("hll_bucket=high", "hll", 16, {}), ("hll_bucket=high", "hll", 16, BINS), (None, "ull", 15, {}), (None, "ull", 15, GLOBAL)]
+
+
+def _rung_case(ctx, monkeypatch, spec, an, k, p, envs, records, routes, amino):
+    import lash_amd
+    ctx.set_layout(spec)
+    try:
+        seq, off, goff = lash_amd.records_to_arrays([records])
+        want = O.sketch_genomes(ALGO[an], k, p, 42, seq, off, goff, layout=O.parse_layout(spec) if spec else None, amino=amino)
+        with monkeypatch.context() as m:
+            for key, v in envs.items():
+                m.setenv(key, v)
+            for name, flags in routes:
+                got = ctx.sketch_batch(an, k, p, 42, seq, off, goff, flags=flags)
+                assert got.shape == want.shape and np.array_equal(got, want), (spec, an, k, p, envs, name)
+    finally:
+        ctx.set_layout(None)
+
+
+@pytest.mark.parametrize("spec,an,k,p,envs", RUNG_CASES)
+def test_launch_table_rungs_the_other_cases_leave_out(ctx, monkeypatch, spec, an, k, p, envs):
+    import lash_amd
+    rng = random.Random(zlib.crc32(repr(("rungs", spec, an, k, p)).encode()))
+    a, b = bytearray(rng.choice(b"ACGT") for _ in range(40)), bytearray(rng.choice(b"ACGT") for _ in range(70))
+    b[33] = ord("N")
+    routes = [("direct", lash_amd.F_NO_SOLE), ("packed", lash_amd.F_NO_DIRECT | lash_amd.F_NO_SOLE), ("stream", lash_amd.F_STREAM_ONLY)]
+    _rung_case(ctx, monkeypatch, spec, an, k, p, envs, [bytes(a), bytes(b)], routes, False)
+
+
+@pytest.mark.parametrize("spec,an,p,envs", AA_RUNG_CASES)
+def test_launch_table_rungs_of_the_amino_acid_route(ctx, monkeypatch, spec, an, p, envs):
+    import lash_amd
+    rng = random.Random(zlib.crc32(repr(("aa rungs", spec, an, p)).encode()))
+    recs = [bytes(rng.choice(b"ACDEFGHIKLMNPQRSTVWY") for _ in range(n)) for n in (15, 30)]
+    _rung_case(ctx, monkeypatch, spec, an, 7, p, envs, recs, [("aa", lash_amd.F_AMINO)], True)

@@ -180,7 +180,7 @@ def test_model_matches_the_oracle():
 
 # ---- A ------------------------------------------------------------------------------------------------------------------------------
 @gpu
-@pytest.mark.parametrize("algo,k,p", TYPES + [("hll", 14, 10)])
+@pytest.mark.parametrize("algo,k,p", TYPES + [("hll", 14, 10), ("hmh", 11, 0), ("ull", 11, 12)])   # (every algorithm at k < 16 too)
 def test_two_slices_long_kept_and_dropped_runs(ctx, algo, k, p):
     """A: a 608 kB FASTA of two records (G, and G with alternate 20 000-base blocks replaced) is cut into several work items of several tiles;
     with M = 2 the shared blocks are kept whole (more than 3 x 4 096 positions: some wave tile is all kept, the all_valid branch under KEEP)
@@ -309,10 +309,16 @@ def test_layouts_on_reads(ctx, spec):
 @gpu
 @pytest.mark.parametrize("spec", LAYOUT_SPECS)
 def test_layouts_on_a_sliced_file(ctx, spec):
-    """D: case A's file under each layout, images only: the x = low / bucket = high variants of the filtered launch on several work items"""
+    """D: case A's file under each layout, images only: the x = low / bucket = high variants of the filtered launch on several work items —
+    each variant at k < 16, k = 16 and k > 16 under the specs that select it"""
+    cases = [("hmh", 16, 0), ("hll", 21, 10)]
+    if "hmh_x=low" in spec:
+        cases += [("hmh", 11, 0), ("hmh", 21, 0)]
+    if "hll_bucket=high" in spec:
+        cases += [("hll", 11, 10), ("hll", 16, 10)]
     ctx.set_layout(spec)
     try:
-        for algo, k, p in (("hmh", 16, 0), ("hll", 21, 10)):
+        for algo, k, p in cases:
             img, tm, _ = filtered(ctx, algo, k, p, [file_a()], [22], 2)
             assert tm["sketch_workgroups"] > 1
             assert np.array_equal(img[0], expected(file_a(), algo, k, p, 22, 2, spec)), (spec, algo)

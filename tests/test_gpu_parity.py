@@ -360,8 +360,8 @@ def test_partial_sketches_of_one_input_merge_across_ranks():
 @pytest.mark.parametrize("an,k,p", [("hmh", 16, 0), ("ull", 16, 12), ("hll", 21, 16)])
 def test_one_input_with_very_many_slices(ctx, an, k, p):
     """A metagenome-sized input (BASELINE configs[4] shape, scaled): one 'genome' of 150-bp reads cut into far more than 64
-    work-item slices, whose partial sketches are folded in groups before the per-genome finalize (and, for hll p=16, in
-    two bucket-space passes as well), next to a small genome in the same batch."""
+    work-item slices, whose partial sketches are folded in groups before the per-genome finalize, next to a small genome in
+    the same batch."""
     import lash_amd
     g = O.synth_genome(77, 40_000_000)
     reads = [g[i:i + 150].tobytes() for i in range(0, len(g) - 150, 150)]
