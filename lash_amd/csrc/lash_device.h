@@ -92,6 +92,27 @@ __device__ __forceinline__ void xxh3_mul128(uint32_t a0, uint32_t a1, uint64_t &
     lo = (uint64_t)(uint32_t)t | (v << 32);
 }
 
+// Bits 63:32 of {h1,h0} * M mod 2^64 — the word three partial products meet in: hi32(h0*M0) + h0*M1 + h1*M0.  As a chain of
+// multiply-adds that STARTS with the high product: Yh = v_mul_hi_u32(h0, M0) is born in the LOW half of an aligned pair {Yh, 0},
+// A = h1*M0 + {Yh, 0}, B = h0*M1 + A, and only lo32(B) is read.  Bits 63:32 of an addend never reach bits 31:0 of a sum, so the
+// pair's high half is free: one loop-invariant zero serves every chain, nothing is moved into place and no carry is rebuilt —
+// three instructions for v_mul_hi_u32 + 2 x v_mul_lo_u32 + v_add3_u32 (13.8 against 17.5 issue cycles, profiles/r04/isa_cost).
+// Inline asm because hipcc, knowing that 32 bits are read, canonicalises a plain-C chain back to the four-instruction form.
+// M0 / M1 stay scalar operands, one per instruction (the constant bus carries one).
+__device__ __forceinline__ uint32_t mul64_word1(uint32_t h0, uint32_t h1, uint64_t M)
+{
+    typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+    u32x2 y;
+    y.x = __umulhi(h0, (uint32_t)M);
+    y.y = 0u;
+    uint64_t b;                                          // (ONE statement: hipcc pads every asm boundary whose output the next VALU reads with an s_nop)
+    asm("v_mad_u64_u32 %0, vcc, %1, %2, %3\n\tv_mad_u64_u32 %0, vcc, %4, %5, %0"
+        : "=&v"(b)
+        : "v"(h1), "s"((uint32_t)M), "v"(__builtin_bit_cast(uint64_t, y)), "v"(h0), "s"((uint32_t)(M >> 32))
+        : "vcc");
+    return (uint32_t)b;
+}
+
 // XXH3-128 of the 4 little-endian bytes of w (XXH3_len_4to8_128b, len = 4), seed folded into `bitflip`.
 __device__ __forceinline__ void xxh3_128_4b(uint32_t w, BitFlip bitflip, uint64_t &lo, uint64_t &hi)
 {
@@ -132,9 +153,7 @@ __device__ __forceinline__ void xxh3_128_4b_hmh_fast(uint32_t w, BitFlip bitflip
     asm("v_mad_u32_u24 %0, %1, 37, %2" : "=v"(top) : "v"((uint32_t)l + (uint32_t)(l >> 32)), "v"((uint32_t)(pm >> 32)));
     sig10 = ((uint32_t)pm ^ alignbit(top, (uint32_t)pm, 28)) & 0x3FFu;
     h ^= h >> 37;
-    constexpr uint32_t m0 = (uint32_t)XXH_PRIME_MX1, m1 = (uint32_t)(XXH_PRIME_MX1 >> 32);
-    const uint32_t h0 = (uint32_t)h, h1 = (uint32_t)(h >> 32);
-    xh = __umulhi(h0, m0) + h0 * m1 + h1 * m0;
+    xh = mul64_word1((uint32_t)h, (uint32_t)(h >> 32), XXH_PRIME_MX1);
 }
 
 // ... and only the half that decides bucket and rank (the signature half — a third of the instructions — is left to the few
@@ -146,9 +165,7 @@ __device__ __forceinline__ uint32_t xxh3_128_4b_hmh_rank(uint32_t w, BitFlip bit
     asm("" : "+v"(l));                                   // (opaque: with nothing else using l, hipcc folds the doubling into the multiply chain — 8 instructions for one)
     asm("v_lshl_add_u64 %0, %1, 1, %0" : "+v"(h) : "v"(l));   // h += l << 1
     h ^= h >> 37;
-    constexpr uint32_t m0 = (uint32_t)XXH_PRIME_MX1, m1 = (uint32_t)(XXH_PRIME_MX1 >> 32);
-    const uint32_t h0 = (uint32_t)h, h1 = (uint32_t)(h >> 32);
-    return __umulhi(h0, m0) + h0 * m1 + h1 * m0;
+    return mul64_word1((uint32_t)h, (uint32_t)(h >> 32), XXH_PRIME_MX1);
 }
 
 // ---- the same three forms for x = LOW half (layout.hmh_x_low, SURVEY App. D switch U1; round 6) ---------------------------------
@@ -161,8 +178,7 @@ __device__ __forceinline__ uint32_t xxh3_l_chain_high(uint64_t l, uint64_t h)   
     asm("v_lshrrev_b64 %0, 3, %1" : "=v"(hs) : "v"(h));
     const uint32_t l1 = (uint32_t)(l >> 32) ^ (uint32_t)(hs >> 32);
     const uint32_t l0 = __builtin_amdgcn_bitop3_b32((uint32_t)l, (uint32_t)hs, l1 >> 3, 0x96);
-    constexpr uint32_t m0 = (uint32_t)XXH_PRIME_MX2, m1 = (uint32_t)(XXH_PRIME_MX2 >> 32);
-    return __umulhi(l0, m0) + l0 * m1 + l1 * m0;
+    return mul64_word1(l0, l1, XXH_PRIME_MX2);
 }
 // xh = bits 63:32 of the low half (bucket = xh >> 18, rank field = xh & 0x3FFFF), sig10 = bits 9:0 of the high half
 __device__ __forceinline__ void xxh3_128_4b_hmh_fast_xlow(uint32_t w, BitFlip bitflip, uint32_t &xh, uint32_t &sig10)
