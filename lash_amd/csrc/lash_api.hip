@@ -250,16 +250,16 @@ void lash_ctx_destroy(lash_ctx *ctx)
     release(ctx->sole_brk);
     release(ctx->sole_state);
     for (DevBuf *b : {&ctx->items, &ctx->item_begin, &ctx->item_kmers, &ctx->partials, &ctx->gregs, &ctx->counter, &ctx->st_seq, &ctx->st_rec,
-                      &ctx->st_img, &ctx->hll_flags, &ctx->ec_ref, &ctx->ec_qry, &ctx->ec_x, &ctx->ec_card, &ctx->wf_scratch, &ctx->wf_out, &ctx->top_buf, &ctx->hll_bm_ref,
-                      &ctx->hll_bm_qry, &ctx->hll_lohi, &ctx->fa_off, &ctx->fa_scratch, &ctx->fc_scratch, &ctx->kf_keep})
+                      &ctx->st_img, &ctx->hll_flags, &ctx->ec_ref, &ctx->ec_qry, &ctx->ec_x, &ctx->ec_card, &ctx->wf_scratch, &ctx->wf_out, &ctx->top_buf,
+                      &ctx->fa_off, &ctx->fa_scratch, &ctx->fc_scratch, &ctx->kf_keep})
         release(*b);
     {
         lash_packed &sc = ctx->scratch;
         for (DevBuf *b : {&sc.words, &sc.brk, &sc.tables, &sc.tiles, &sc.lookback, &sc.tile_begin_c, &sc.brk_bytes, &sc.fq})
             release(*b);
     }
-    for (lash_sketch_set *ps : {&ctx->pl_ref, &ctx->pl_qry})
-        for (DevBuf *b : {&ps->S, &ps->T, &ps->nzcount}) release(*b);
+    release(ctx->pair_ref);
+    release(ctx->pair_qry);
     for (auto &s : ctx->ev_pool)
         for (auto &e : s.e)
             if (e) (void)hipEventDestroy(e);

@@ -133,7 +133,12 @@ struct lash_sketch_set {
     DevBuf d_card, d_small;
 };
 
-int lash_set_build_planes(lash_ctx *ctx, lash_sketch_set *s, bool want_T);   // sketch_set.hip
+// sketch_set.hip.  lash_set_bind points a set at n images (d_images == nullptr: at members known by their cardinalities alone, for
+// lash_set_take_cardinalities) and forgets everything derived from what it held before; the grow-only buffers are kept.
+int lash_set_bind(lash_ctx *ctx, lash_sketch_set *s, int algo, int p, const uint8_t *d_images, uint32_t n);
+int lash_set_build_planes(lash_ctx *ctx, lash_sketch_set *s, bool want_T);
+int lash_set_take_cardinalities(lash_ctx *ctx, lash_sketch_set *s, const double *card);   // card, small_idx, d_card / d_small; synchronizes
+int lash_set_ec_vectors(lash_ctx *ctx, lash_sketch_set *qry);   // the small members' cell vectors, if they fit a third of the free memory
 
 // HyperMinHash: the 65 536-cell sums of the block's small pairs (rows [r0, r1) of ref x columns [0, n_cols) of qry, both sketches
 // <= 2^19 distinct k-mers) as f64 matrix products into ctx->ec_x, asynchronous on the context's stream (sketch_set.hip).  The small
@@ -145,6 +150,19 @@ struct EcBlock {
 };
 int lash_set_ec_block(lash_ctx *ctx, const lash_sketch_set *ref, uint32_t r0, uint32_t r1, const lash_sketch_set *qry, uint32_t n_cols,
                       EcBlock &eb);
+// fetches the block's products and writes hmh_ec_from_cell_sum of each to out_ec[(row - r0) * n_cols + column]; synchronizes
+int lash_set_ec_scatter(lash_ctx *ctx, const EcBlock &eb, const lash_sketch_set *ref, uint32_t r0, const lash_sketch_set *qry, uint32_t n_cols,
+                        double *out_ec);
+
+// Where the host-buffer pair entries keep a block's statistics on the device (ctx->st_img) and which of them an algorithm has:
+// HyperMinHash (C, N) in c / n; HyperLogLog (zero, sum) in c / u; UltraLogLog the union estimate in u.  (sketch_set.hip)
+struct PairOut {
+    uint32_t *c = nullptr, *n = nullptr;
+    double *u = nullptr;
+};
+int lash_pair_out_reserve(lash_ctx *ctx, size_t n_pairs, PairOut &d);
+int lash_pair_out_fetch(lash_ctx *ctx, int algo, size_t n_pairs, const PairOut &d, uint32_t *out_c_or_zero, uint32_t *out_n,
+                        double *out_sum_or_union);   // copies back and synchronizes
 
 struct lash_ctx {
     int device = 0;
@@ -182,10 +200,8 @@ struct lash_ctx {
     unsigned slot_next = 0;
     hipStream_t h2d_stream = nullptr, d2h_stream = nullptr;
     lash_packed scratch;                 // packed batch of lash_sketch_batch[_device]
-    lash_sketch_set pl_ref, pl_qry;      // lash_hmh_pair_counts[_device]: bit planes of the call's images (buffers reused across calls)
-    DevBuf hll_bm_ref, hll_bm_qry, hll_lohi;   // lash_hll_pair_union_stats*: threshold bitmaps [n][band][m/32], range of register values
-    DevBuf ec_ref, ec_qry, ec_x, ec_card;   // lash_hmh_pair_expected_collisions: cell vectors [n][65536] f64, products, cardinalities
-    std::vector<double> ec_qry_cards;    // the small query cardinalities whose vectors ec_qry holds (reused across row blocks)
+    lash_sketch_set pair_ref, pair_qry;  // the stand-alone pair entries (lash_dist_api.hip): bound to the call's images or cardinalities
+    DevBuf ec_ref, ec_qry, ec_x, ec_card;   // lash_set_ec_block: cell vectors [n][65536] f64, products, cardinalities
     DevBuf wf_scratch, wf_out;           // lash_sketch_set_pair_block_within: [offsets | masks | tile counts], the compacted candidates
     DevBuf top_buf;                      // lash_sketch_set_pair_block_top: [cutoff keys | interval keys | same_col] (dist_top.hip)
     DevBuf hll_flags;                    // [hll_flags_n] per genome of the last HyperLogLog sketch call: a register > 53 - p
@@ -252,6 +268,11 @@ void release(DevBuf &b)
     if (b.ptr) (void)hipFree(b.ptr);
     b.ptr = nullptr;
     b.cap = 0;
+}
+
+void release(lash_sketch_set &s)
+{
+    for (DevBuf *b : {&s.images, &s.S, &s.T, &s.nzcount, &s.lohi, &s.bm, &s.ec_vec, &s.d_card, &s.d_small}) release(*b);
 }
 
 // Small host tables go through a ring of pinned buffers, so the async copy never reads a dead std::vector and a

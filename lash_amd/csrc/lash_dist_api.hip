@@ -63,56 +63,60 @@ int lash_merge_images(lash_ctx *ctx, int algo, int p, uint8_t *dst, const uint8_
     return LASH_OK;
 }
 
+}  // extern "C"
+
+namespace {
+
+// The stand-alone pair entries run on the context's two call-scoped sets (sketch_set.hip holds all operand preparation): bind them
+// to the call's images, prepare, one block of all rows against all columns.  Binding always invalidates: the host entries stage
+// new contents at the address of the previous call.  One set serves both sides when the two image blocks are the same.
+int pair_stats_device(lash_ctx *ctx, int algo, int p, int ull_estimator, const uint8_t *d_ref, uint32_t n_ref, const uint8_t *d_qry,
+                      uint32_t n_qry, uint32_t *d_c_or_zero, uint32_t *d_n, double *d_sum_or_union)
+{
+    (void)hipSetDevice(ctx->device);
+    if (n_ref == 0 || n_qry == 0) return LASH_OK;
+    lash_sketch_set *ref = &ctx->pair_ref, *qry = d_ref == d_qry && n_ref == n_qry ? ref : &ctx->pair_qry;
+    int rc;
+    if ((rc = lash_set_bind(ctx, ref, algo, p, d_ref, n_ref))) return rc;
+    if (qry != ref && (rc = lash_set_bind(ctx, qry, algo, p, d_qry, n_qry))) return rc;
+    if ((rc = lash_sketch_set_prepare(ctx, ref, qry))) return rc;
+    return lash_sketch_set_pair_block_device(ctx, ref, 0, n_ref, qry, n_qry, 0, ull_estimator, d_c_or_zero, d_n, d_sum_or_union);
+}
+
+// host buffers: stage the reference and query images, run the device form, copy back what this algorithm outputs, synchronize
+int pair_stats_host(lash_ctx *ctx, int algo, int p, int ull_estimator, const uint8_t *ref_images, uint32_t n_ref, const uint8_t *qry_images,
+                    uint32_t n_qry, uint32_t *out_c_or_zero, uint32_t *out_n, double *out_sum_or_union)
+{
+    if (n_ref == 0 || n_qry == 0) return LASH_OK;
+    (void)hipSetDevice(ctx->device);
+    const size_t ib = image_bytes(ctx->layout, algo, p), rb = ib * n_ref, qb = ib * n_qry, np = (size_t)n_ref * n_qry;
+    int rc;
+    PairOut d;
+    if ((rc = reserve(ctx, ctx->st_seq, rb + qb + 64))) return rc;
+    if ((rc = lash_pair_out_reserve(ctx, np, d))) return rc;
+    uint8_t *d_r = static_cast<uint8_t *>(ctx->st_seq.ptr), *d_q = d_r + rb;
+    HIPCHK(ctx, hipMemcpyAsync(d_r, ref_images, rb, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(d_q, qry_images, qb, hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = pair_stats_device(ctx, algo, p, ull_estimator, d_r, n_ref, d_q, n_qry, d.c, d.n, d.u))) return rc;
+    return lash_pair_out_fetch(ctx, algo, np, d, out_c_or_zero, out_n, out_sum_or_union);
+}
+
+}  // namespace
+
+extern "C" {
+
 int lash_hmh_pair_counts_device(lash_ctx *ctx, const uint8_t *d_ref_images, uint32_t n_ref, const uint8_t *d_qry_images,
                                 uint32_t n_qry, uint32_t *d_out_c, uint32_t *d_out_n)
 {
     if (!ctx || ((n_ref && n_qry) && (!d_ref_images || !d_qry_images || !d_out_c || !d_out_n))) return LASH_EINVAL;
-    (void)hipSetDevice(ctx->device);
-    if (n_ref == 0 || n_qry == 0) return LASH_OK;
-    const uint32_t hdr = (uint32_t)header_bytes(ctx->layout, LASH_HMH);
-    const uint64_t stride = image_bytes(ctx->layout, LASH_HMH, 0);
-    static const bool words_kernel = getenv("LASH_HMH_PAIRS_WORDS") != nullptr;      // A/B knob: the u16-pair kernel on the images
-    if (words_kernel) {
-        HIPCHK(ctx, launch_hmh_pairs(d_ref_images, n_ref, d_qry_images, n_qry, hdr, stride, d_out_c, d_out_n, ctx->stream));
-        return LASH_OK;
-    }
-    // register bit planes of the call's images (pair_planes.hip; one read-back of the non-zero counts: synchronizes once)
-    const bool same = d_ref_images == d_qry_images && n_ref == n_qry;
-    lash_sketch_set *sets[2] = {&ctx->pl_ref, same ? &ctx->pl_ref : &ctx->pl_qry};
-    for (int i = 0; i < (same ? 1 : 2); ++i) {
-        lash_sketch_set *s = sets[i];
-        s->device = ctx->device; s->algo = LASH_HMH; s->p = 0; s->hdr = hdr; s->stride = stride;
-        s->n = i ? n_qry : n_ref;
-        s->d_images = i ? d_qry_images : d_ref_images;
-        s->have_S = s->have_T = false;                               // (the buffers are kept, their contents are this call's)
-    }
-    int rc;
-    if ((rc = lash_set_build_planes(ctx, sets[0], true))) return rc;                 // (row and column layout in one pass when the sets coincide)
-    if ((rc = lash_set_build_planes(ctx, sets[1], false))) return rc;
-    HIPCHK(ctx, launch_hmh_pairs_planes(static_cast<const uint32_t *>(sets[0]->T.ptr), sets[0]->ldT, 0, n_ref, static_cast<const uint32_t *>(sets[1]->S.ptr),
-                                        sets[1]->n_pad, n_qry, sets[0]->full && sets[1]->full, false, d_out_c, d_out_n, n_qry, ctx->stream));
-    return LASH_OK;
+    return pair_stats_device(ctx, LASH_HMH, 0, 0, d_ref_images, n_ref, d_qry_images, n_qry, d_out_c, d_out_n, nullptr);
 }
 
 int lash_hmh_pair_counts(lash_ctx *ctx, const uint8_t *ref_images, uint32_t n_ref, const uint8_t *qry_images,
                          uint32_t n_qry, uint32_t *out_c, uint32_t *out_n)
 {
     if (!ctx || ((n_ref && n_qry) && (!ref_images || !qry_images || !out_c || !out_n))) return LASH_EINVAL;
-    if (n_ref == 0 || n_qry == 0) return LASH_OK;
-    (void)hipSetDevice(ctx->device);
-    const size_t ib = image_bytes(ctx->layout, LASH_HMH, 0), rb = ib * n_ref, qb = ib * n_qry, pb = (size_t)n_ref * n_qry * 4;
-    int rc;
-    if ((rc = reserve(ctx, ctx->st_seq, rb + qb + 64))) return rc;
-    if ((rc = reserve(ctx, ctx->st_img, 2 * pb + 64))) return rc;
-    uint8_t *d_r = static_cast<uint8_t *>(ctx->st_seq.ptr), *d_q = d_r + rb;
-    uint32_t *d_c = static_cast<uint32_t *>(ctx->st_img.ptr), *d_n = d_c + (size_t)n_ref * n_qry;
-    HIPCHK(ctx, hipMemcpyAsync(d_r, ref_images, rb, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(d_q, qry_images, qb, hipMemcpyHostToDevice, ctx->stream));
-    if ((rc = lash_hmh_pair_counts_device(ctx, d_r, n_ref, d_q, n_qry, d_c, d_n))) return rc;
-    HIPCHK(ctx, hipMemcpyAsync(out_c, d_c, pb, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(out_n, d_n, pb, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    return LASH_OK;
+    return pair_stats_host(ctx, LASH_HMH, 0, 0, ref_images, n_ref, qry_images, n_qry, out_c, out_n, nullptr);
 }
 
 int lash_hmh_pair_expected_collisions(lash_ctx *ctx, const double *ref_card, uint32_t n_ref, const double *qry_card, uint32_t n_qry,
@@ -121,60 +125,36 @@ int lash_hmh_pair_expected_collisions(lash_ctx *ctx, const double *ref_card, uin
     if (!ctx || ((n_ref && n_qry) && (!ref_card || !qry_card || !out_ec))) return LASH_EINVAL;
     if (n_ref == 0 || n_qry == 0) return LASH_OK;
     (void)hipSetDevice(ctx->device);
-    // O(1) regimes on the host; what is left needs the cell sum: pairs whose LARGER sketch is at or below 2^(p+5), i.e. both are
-    std::vector<uint32_t> rs, qs;
-    std::vector<uint8_t> rsmall(n_ref), qsmall(n_qry);
-    double dummy;
-    for (uint32_t i = 0; i < n_ref; ++i) rsmall[i] = !hmh_ec_closed_form(ref_card[i], ref_card[i], &dummy);
-    for (uint32_t j = 0; j < n_qry; ++j) qsmall[j] = !hmh_ec_closed_form(qry_card[j], qry_card[j], &dummy);
-    for (uint32_t j = 0; j < n_qry; ++j) if (qsmall[j]) qs.push_back(j);
-    if (!qs.empty()) for (uint32_t i = 0; i < n_ref; ++i) if (rsmall[i]) rs.push_back(i);
+    // the call-scoped sets, bound to cardinalities alone.  The query set and its cell vectors are kept while the values repeat.
+    lash_sketch_set *ref = &ctx->pair_ref, *qry = &ctx->pair_qry;
+    int rc;
+    if ((rc = lash_set_bind(ctx, ref, LASH_HMH, 0, nullptr, n_ref))) return rc;
+    if ((rc = lash_set_take_cardinalities(ctx, ref, ref_card))) return rc;
+    if (!(qry->have_ec_vec && qry->card.size() == n_qry && std::equal(qry_card, qry_card + n_qry, qry->card.begin()))) {
+        if ((rc = lash_set_bind(ctx, qry, LASH_HMH, 0, nullptr, n_qry))) return rc;
+        if ((rc = lash_set_take_cardinalities(ctx, qry, qry_card))) return rc;
+    }
+    // O(1) regimes on the host: every pair with a large member (two small ones need the cell sum: below)
+    const std::vector<uint32_t> &rs = ref->small_idx;
+    std::vector<uint8_t> q_small(n_qry, 0);
+    for (uint32_t j : qry->small_idx) q_small[j] = 1;
+    auto r_next = rs.begin();
     for (uint32_t i = 0; i < n_ref; ++i) {
+        const bool r_small = r_next != rs.end() && *r_next == i;
+        if (r_small) ++r_next;
         double *row = out_ec + (size_t)i * n_qry;
         for (uint32_t j = 0; j < n_qry; ++j)
-            if (!(rsmall[i] && qsmall[j])) (void)hmh_ec_closed_form(qry_card[j], ref_card[i], &row[j]);
+            if (!(r_small && q_small[j])) (void)hmh_ec_closed_form(qry_card[j], ref_card[i], &row[j]);
     }
-    if (rs.empty()) return LASH_OK;
-    constexpr size_t VEC = 65536 * sizeof(double);
-    constexpr size_t Q_CHUNK = (24ull << 30) / VEC, R_CHUNK = (4ull << 30) / VEC;      // <= 24 + 4 GiB of vectors at a time
-    int rc;
-    std::vector<double> cards, x;
-    for (size_t q0 = 0; q0 < qs.size(); q0 += Q_CHUNK) {
-        const uint32_t nq = (uint32_t)std::min(Q_CHUNK, qs.size() - q0);
-        cards.resize(nq);
-        for (uint32_t j = 0; j < nq; ++j) cards[j] = qry_card[qs[q0 + j]];
-        if ((rc = reserve(ctx, ctx->ec_card, (size_t)(nq + R_CHUNK) * 8))) return rc;
-        double *d_card = static_cast<double *>(ctx->ec_card.ptr);
-        const bool cached = qs.size() <= Q_CHUNK && ctx->ec_qry.ptr && cards == ctx->ec_qry_cards;
-        if (!cached) {
-            ctx->ec_qry_cards.clear();
-            if ((rc = reserve(ctx, ctx->ec_qry, (size_t)nq * VEC))) return rc;
-            HIPCHK(ctx, hipMemcpyAsync(d_card, cards.data(), (size_t)nq * 8, hipMemcpyHostToDevice, ctx->stream));
-            HIPCHK(ctx, launch_collision_vectors(d_card, nq, static_cast<double *>(ctx->ec_qry.ptr), ctx->stream));
-            HIPCHK(ctx, hipStreamSynchronize(ctx->stream));    // (`cards` is reused below)
-            if (qs.size() <= Q_CHUNK) ctx->ec_qry_cards = cards;
-        }
-        for (size_t r0 = 0; r0 < rs.size(); r0 += R_CHUNK) {
-            const uint32_t nr = (uint32_t)std::min(R_CHUNK, rs.size() - r0);
-            std::vector<double> rcards(nr);
-            for (uint32_t i = 0; i < nr; ++i) rcards[i] = ref_card[rs[r0 + i]];
-            if ((rc = reserve(ctx, ctx->ec_ref, (size_t)nr * VEC))) return rc;
-            if ((rc = reserve(ctx, ctx->ec_x, (size_t)nr * nq * 8))) return rc;
-            HIPCHK(ctx, hipMemcpyAsync(d_card + nq, rcards.data(), (size_t)nr * 8, hipMemcpyHostToDevice, ctx->stream));
-            HIPCHK(ctx, launch_collision_vectors(d_card + nq, nr, static_cast<double *>(ctx->ec_ref.ptr), ctx->stream));
-            HIPCHK(ctx, launch_collision_gemm(static_cast<const double *>(ctx->ec_ref.ptr), nr, static_cast<const double *>(ctx->ec_qry.ptr), nq,
-                                              static_cast<double *>(ctx->ec_x.ptr), ctx->stream));
-            x.resize((size_t)nr * nq);
-            HIPCHK(ctx, hipMemcpyAsync(x.data(), ctx->ec_x.ptr, x.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
-            HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-            for (uint32_t i = 0; i < nr; ++i) {
-                const uint32_t ri = rs[r0 + i];
-                for (uint32_t j = 0; j < nq; ++j) {
-                    const uint32_t qj = qs[q0 + j];
-                    out_ec[(size_t)ri * n_qry + qj] = hmh_ec_from_cell_sum(x[(size_t)i * nq + j]);
-                }
-            }
-        }
+    if (rs.empty() || qry->small_idx.empty()) return LASH_OK;
+    if ((rc = lash_set_ec_vectors(ctx, qry))) return rc;
+    // row blocks of at most 8192 small rows: 4 GiB of reference vectors at a time
+    constexpr size_t R_BLOCK = 8192;
+    for (size_t b = 0; b < rs.size(); b += R_BLOCK) {
+        const uint32_t r0 = rs[b], r1 = b + R_BLOCK < rs.size() ? rs[b + R_BLOCK] : n_ref;
+        EcBlock eb;
+        if ((rc = lash_set_ec_block(ctx, ref, r0, r1, qry, n_qry, eb))) return rc;
+        if ((rc = lash_set_ec_scatter(ctx, eb, ref, r0, qry, n_qry, out_ec + (size_t)r0 * n_qry))) return rc;
     }
     return LASH_OK;
 }
@@ -184,62 +164,14 @@ int lash_hll_pair_union_stats_device(lash_ctx *ctx, int p, const uint8_t *d_ref_
 {
     if (!ctx || p < 4 || p > 16 || ((n_ref && n_qry) && (!d_ref_images || !d_qry_images || !d_out_zero || !d_out_sum)))
         return LASH_EINVAL;
-    (void)hipSetDevice(ctx->device);
-    const uint32_t hdr = (uint32_t)header_bytes(ctx->layout, LASH_HLL);
-    static const bool byte_kernel_only = getenv("LASH_HLL_PAIRS_BYTEWISE") != nullptr;
-    if (p >= 10 && n_ref && n_qry && !byte_kernel_only) {
-        // threshold-bitmap form (dist_kernels.hip): needs the range of register values first — one 8-byte read-back
-        int rc;
-        if ((rc = reserve(ctx, ctx->hll_lohi, 8))) return rc;
-        uint32_t *d_lohi = static_cast<uint32_t *>(ctx->hll_lohi.ptr);
-        HIPCHK(ctx, hipMemsetAsync(d_lohi, 0xFF, 4, ctx->stream));
-        HIPCHK(ctx, hipMemsetAsync(d_lohi + 1, 0, 4, ctx->stream));
-        HIPCHK(ctx, launch_hll_minmax(d_ref_images, n_ref, p, hdr, d_lohi, ctx->stream));
-        const bool same = d_ref_images == d_qry_images && n_ref == n_qry;
-        if (!same) HIPCHK(ctx, launch_hll_minmax(d_qry_images, n_qry, p, hdr, d_lohi, ctx->stream));
-        uint32_t lohi[2] = {0, 0};
-        HIPCHK(ctx, hipMemcpyAsync(lohi, d_lohi, 8, hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-        const uint32_t lo = lohi[0], hi = lohi[1];
-        if (hi > lo && hi <= 64u) {                              // (all registers equal, or values no sketch can hold: the byte-wise kernel)
-            const uint32_t band = hi - lo;
-            const size_t per = (size_t)band * ((size_t)1 << p) / 8;
-            if ((rc = reserve(ctx, ctx->hll_bm_qry, (size_t)n_qry * per))) return rc;
-            uint32_t *bq = static_cast<uint32_t *>(ctx->hll_bm_qry.ptr), *br = bq;
-            HIPCHK(ctx, launch_hll_bitmaps(d_qry_images, n_qry, p, hdr, lo, band, bq, ctx->stream));
-            if (!same) {
-                if ((rc = reserve(ctx, ctx->hll_bm_ref, (size_t)n_ref * per))) return rc;
-                br = static_cast<uint32_t *>(ctx->hll_bm_ref.ptr);
-                HIPCHK(ctx, launch_hll_bitmaps(d_ref_images, n_ref, p, hdr, lo, band, br, ctx->stream));
-            }
-            HIPCHK(ctx, launch_hll_pairs_bitmap(br, n_ref, bq, n_qry, p, lo, band, d_out_zero, d_out_sum, ctx->stream));
-            return LASH_OK;
-        }
-    }
-    HIPCHK(ctx, launch_hll_pairs(d_ref_images, n_ref, d_qry_images, n_qry, p, hdr, d_out_zero, d_out_sum, ctx->stream));
-    return LASH_OK;
+    return pair_stats_device(ctx, LASH_HLL, p, 0, d_ref_images, n_ref, d_qry_images, n_qry, d_out_zero, nullptr, d_out_sum);
 }
 
 int lash_hll_pair_union_stats(lash_ctx *ctx, int p, const uint8_t *ref_images, uint32_t n_ref, const uint8_t *qry_images,
                               uint32_t n_qry, uint32_t *out_zero, double *out_sum)
 {
     if (!ctx || p < 4 || p > 16 || ((n_ref && n_qry) && (!ref_images || !qry_images || !out_zero || !out_sum))) return LASH_EINVAL;
-    if (n_ref == 0 || n_qry == 0) return LASH_OK;
-    (void)hipSetDevice(ctx->device);
-    const size_t ib = image_bytes(ctx->layout, LASH_HLL, p), rb = ib * n_ref, qb = ib * n_qry, np = (size_t)n_ref * n_qry;
-    int rc;
-    if ((rc = reserve(ctx, ctx->st_seq, rb + qb + 64))) return rc;
-    if ((rc = reserve(ctx, ctx->st_img, np * 12 + 64))) return rc;
-    uint8_t *d_r = static_cast<uint8_t *>(ctx->st_seq.ptr), *d_q = d_r + rb;
-    double *d_s = static_cast<double *>(ctx->st_img.ptr);
-    uint32_t *d_z = reinterpret_cast<uint32_t *>(d_s + np);
-    HIPCHK(ctx, hipMemcpyAsync(d_r, ref_images, rb, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(d_q, qry_images, qb, hipMemcpyHostToDevice, ctx->stream));
-    if ((rc = lash_hll_pair_union_stats_device(ctx, p, d_r, n_ref, d_q, n_qry, d_z, d_s))) return rc;
-    HIPCHK(ctx, hipMemcpyAsync(out_zero, d_z, np * 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(out_sum, d_s, np * 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    return LASH_OK;
+    return pair_stats_host(ctx, LASH_HLL, p, 0, ref_images, n_ref, qry_images, n_qry, out_zero, nullptr, out_sum);
 }
 
 int lash_ull_pair_union_estimates_device(lash_ctx *ctx, int p, int estimator, const uint8_t *d_ref_images, uint32_t n_ref,
@@ -248,30 +180,14 @@ int lash_ull_pair_union_estimates_device(lash_ctx *ctx, int p, int estimator, co
     if (!ctx || p < 3 || p > 26 || (estimator != LASH_ULL_FGRA && estimator != LASH_ULL_ML) ||
         ((n_ref && n_qry) && (!d_ref_images || !d_qry_images || !d_out_est)))
         return LASH_EINVAL;
-    (void)hipSetDevice(ctx->device);
-    HIPCHK(ctx, launch_ull_pairs(d_ref_images, n_ref, d_qry_images, n_qry, p, (uint32_t)header_bytes(ctx->layout, LASH_ULL), estimator,
-                                 d_out_est, ctx->stream));
-    return LASH_OK;
+    return pair_stats_device(ctx, LASH_ULL, p, estimator, d_ref_images, n_ref, d_qry_images, n_qry, nullptr, nullptr, d_out_est);   // (no synchronization)
 }
 
 int lash_ull_pair_union_estimates(lash_ctx *ctx, int p, int estimator, const uint8_t *ref_images, uint32_t n_ref,
                                   const uint8_t *qry_images, uint32_t n_qry, double *out_est)
 {
     if (!ctx || p < 3 || p > 26 || ((n_ref && n_qry) && (!ref_images || !qry_images || !out_est))) return LASH_EINVAL;
-    if (n_ref == 0 || n_qry == 0) return LASH_OK;
-    (void)hipSetDevice(ctx->device);
-    const size_t ib = image_bytes(ctx->layout, LASH_ULL, p), rb = ib * n_ref, qb = ib * n_qry, np = (size_t)n_ref * n_qry;
-    int rc;
-    if ((rc = reserve(ctx, ctx->st_seq, rb + qb + 64))) return rc;
-    if ((rc = reserve(ctx, ctx->st_img, np * 8 + 64))) return rc;
-    uint8_t *d_r = static_cast<uint8_t *>(ctx->st_seq.ptr), *d_q = d_r + rb;
-    double *d_e = static_cast<double *>(ctx->st_img.ptr);
-    HIPCHK(ctx, hipMemcpyAsync(d_r, ref_images, rb, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(d_q, qry_images, qb, hipMemcpyHostToDevice, ctx->stream));
-    if ((rc = lash_ull_pair_union_estimates_device(ctx, p, estimator, d_r, n_ref, d_q, n_qry, d_e))) return rc;
-    HIPCHK(ctx, hipMemcpyAsync(out_est, d_e, np * 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    return LASH_OK;
+    return pair_stats_host(ctx, LASH_ULL, p, estimator, ref_images, n_ref, qry_images, n_qry, nullptr, nullptr, out_est);
 }
 
 double lash_ull_estimate(const uint8_t *registers, int p, int estimator)

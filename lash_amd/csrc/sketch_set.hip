@@ -59,7 +59,13 @@ hipError_t launch_gather_rows(const uint8_t *d_src, const uint32_t *d_order, uin
 
 namespace {
 
-int set_geometry(lash_ctx *ctx, lash_sketch_set *s, int algo, int p, uint32_t n)
+uint32_t set_regs(const lash_sketch_set *s) { return s->algo == LASH_HMH ? HMH_M : (1u << s->p); }
+
+}  // namespace
+
+// The one place that lists a set's derived state: the planes and `full`, the range, the bitmaps, the cardinalities with what
+// follows from them (small_idx, the cell vectors; d_card / d_small are read only while card.size() == n).
+int lash_set_bind(lash_ctx *ctx, lash_sketch_set *s, int algo, int p, const uint8_t *d_images, uint32_t n)
 {
     lash_params prm{algo, 16, p, 0, 0};
     const int rc = lash_params_check(&prm);
@@ -71,12 +77,16 @@ int set_geometry(lash_ctx *ctx, lash_sketch_set *s, int algo, int p, uint32_t n)
     s->hdr = (uint32_t)header_bytes(ctx->layout, algo);
     s->stride = image_bytes(ctx->layout, algo, p);
     s->hmh_be = ctx->layout.hmh_reg_be;
+    s->d_images = d_images;
+    s->have_S = s->have_T = s->full = false;
+    s->have_range = s->have_bm = false;
+    s->lo = 0xFFFFFFFFu;
+    s->hi = s->bm_lo = s->bm_band = 0;
+    s->card.clear();
+    s->small_idx.clear();
+    s->have_ec_vec = false;
     return LASH_OK;
 }
-
-uint32_t set_regs(const lash_sketch_set *s) { return s->algo == LASH_HMH ? HMH_M : (1u << s->p); }
-
-}  // namespace
 
 // HyperMinHash: column layout (+ non-zero counts -> `full`), optionally the row layout.  Synchronizes the stream.
 int lash_set_build_planes(lash_ctx *ctx, lash_sketch_set *s, bool want_T)
@@ -157,6 +167,93 @@ int lash_set_ec_block(lash_ctx *ctx, const lash_sketch_set *ref, uint32_t r0, ui
     return LASH_OK;
 }
 
+int lash_set_ec_scatter(lash_ctx *ctx, const EcBlock &eb, const lash_sketch_set *ref, uint32_t r0, const lash_sketch_set *qry, uint32_t n_cols,
+                        double *out_ec)
+{
+    std::vector<double> x((size_t)eb.nrs * eb.nqs);
+    HIPCHK(ctx, hipMemcpyAsync(x.data(), eb.X, x.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    for (uint32_t q0 = 0; q0 < eb.nqs; q0 += eb.q_step) {
+        const uint32_t nq = std::min(eb.q_step, eb.nqs - q0);
+        const double *chunk = x.data() + (size_t)eb.nrs * q0;
+        for (uint32_t i = 0; i < eb.nrs; ++i) {
+            double *row = out_ec + (size_t)(ref->small_idx[eb.rbase + i] - r0) * n_cols;
+            for (uint32_t j = 0; j < nq; ++j) row[qry->small_idx[q0 + j]] = hmh_ec_from_cell_sum(chunk[(size_t)i * nq + j]);
+        }
+    }
+    return LASH_OK;
+}
+
+int lash_set_take_cardinalities(lash_ctx *ctx, lash_sketch_set *s, const double *card)
+{
+    s->card.assign(card, card + s->n);
+    s->small_idx.clear();
+    s->have_ec_vec = false;
+    std::vector<int32_t> small_pos(s->n, -1);
+    if (s->algo == LASH_HMH) {
+        double dummy;
+        for (uint32_t i = 0; i < s->n; ++i)
+            if (!hmh_ec_closed_form(card[i], card[i], &dummy)) { small_pos[i] = (int32_t)s->small_idx.size(); s->small_idx.push_back(i); }
+    }
+    // (the device copies the --max-dist filter reads: lash_sketch_set_pair_block_within)
+    int rc;
+    if ((rc = reserve(ctx, s->d_card, (size_t)s->n * 8))) return rc;
+    if ((rc = reserve(ctx, s->d_small, (size_t)s->n * 4))) return rc;
+    HIPCHK(ctx, hipMemcpyAsync(s->d_card.ptr, card, (size_t)s->n * 8, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(s->d_small.ptr, small_pos.data(), (size_t)s->n * 4, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return LASH_OK;
+}
+
+// expected collisions of small pairs (lash_set_ec_block): the query side's cell vectors, once, when they fit a third of the
+// free memory (else they are made per block)
+int lash_set_ec_vectors(lash_ctx *ctx, lash_sketch_set *qry)
+{
+    if (qry->small_idx.empty() || qry->have_ec_vec) return LASH_OK;
+    size_t free_b = 0, total_b = 0;
+    const size_t need = qry->small_idx.size() * (size_t)65536 * 8;
+    if (need > qry->ec_vec.cap && (hipMemGetInfo(&free_b, &total_b) != hipSuccess || need > free_b / 3)) return LASH_OK;
+    int rc;
+    std::vector<double> cards(qry->small_idx.size());
+    for (size_t j = 0; j < cards.size(); ++j) cards[j] = qry->card[qry->small_idx[j]];
+    if ((rc = reserve(ctx, qry->ec_vec, need))) return rc;
+    if ((rc = reserve(ctx, ctx->ec_card, cards.size() * 8))) return rc;
+    HIPCHK(ctx, hipMemcpyAsync(ctx->ec_card.ptr, cards.data(), cards.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, launch_collision_vectors(static_cast<const double *>(ctx->ec_card.ptr), (uint32_t)cards.size(),
+                                         static_cast<double *>(qry->ec_vec.ptr), ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    qry->have_ec_vec = true;
+    return LASH_OK;
+}
+
+int lash_pair_out_reserve(lash_ctx *ctx, size_t n_pairs, PairOut &d)
+{
+    const int rc = reserve(ctx, ctx->st_img, n_pairs * 16 + 64);                      // [u f64 | c u32 | n u32]
+    if (rc) return rc;
+    d.u = static_cast<double *>(ctx->st_img.ptr);
+    d.c = reinterpret_cast<uint32_t *>(d.u + n_pairs);
+    d.n = d.c + n_pairs;
+    return LASH_OK;
+}
+
+int lash_pair_out_fetch(lash_ctx *ctx, int algo, size_t n_pairs, const PairOut &d, uint32_t *out_c_or_zero, uint32_t *out_n,
+                        double *out_sum_or_union)
+{
+    if (algo != LASH_ULL) {
+        if (!out_c_or_zero) return LASH_EINVAL;
+        HIPCHK(ctx, hipMemcpyAsync(out_c_or_zero, d.c, n_pairs * 4, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    if (algo == LASH_HMH) {
+        if (!out_n) return LASH_EINVAL;
+        HIPCHK(ctx, hipMemcpyAsync(out_n, d.n, n_pairs * 4, hipMemcpyDeviceToHost, ctx->stream));
+    } else {
+        if (!out_sum_or_union) return LASH_EINVAL;
+        HIPCHK(ctx, hipMemcpyAsync(out_sum_or_union, d.u, n_pairs * 8, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return LASH_OK;
+}
+
 namespace {
 
 int hll_range(lash_ctx *ctx, lash_sketch_set *s)
@@ -201,9 +298,8 @@ int lash_sketch_set_create_device(lash_ctx *ctx, int algo, int p, const uint8_t 
     *out = nullptr;
     lash_sketch_set *s = new (std::nothrow) lash_sketch_set();
     if (!s) return LASH_ENOMEM;
-    const int rc = set_geometry(ctx, s, algo, p, n);
+    const int rc = lash_set_bind(ctx, s, algo, p, d_images, n);
     if (rc) { delete s; return rc; }
-    s->d_images = d_images;
     *out = s;
     return LASH_OK;
 }
@@ -219,7 +315,7 @@ int lash_sketch_set_create(lash_ctx *ctx, int algo, int p, const uint8_t *images
     (void)hipSetDevice(ctx->device);
     lash_sketch_set *s = new (std::nothrow) lash_sketch_set();
     if (!s) return LASH_ENOMEM;
-    int rc = set_geometry(ctx, s, algo, p, n);
+    int rc = lash_set_bind(ctx, s, algo, p, nullptr, n);
     auto bail = [&](int code) { lash_sketch_set_free(ctx, s); return code; };
     if (rc) return bail(rc);
     if ((rc = reserve(ctx, s->images, (size_t)n * s->stride + 64))) return bail(rc);
@@ -257,7 +353,7 @@ void lash_sketch_set_free(lash_ctx *ctx, lash_sketch_set *s)
     if (!s) return;
     (void)hipSetDevice(s->device);
     if (ctx && ctx->stream) (void)hipStreamSynchronize(ctx->stream);
-    for (DevBuf *b : {&s->images, &s->S, &s->T, &s->nzcount, &s->lohi, &s->bm, &s->ec_vec, &s->d_card, &s->d_small}) release(*b);
+    release(*s);
     delete s;
 }
 
@@ -296,22 +392,7 @@ int lash_sketch_set_cardinalities(lash_ctx *ctx, lash_sketch_set *s, int ull_est
             out_card[i] = ull_estimator == LASH_ULL_ML ? lash::ull::ml(hh, s->p) : lash::ull::fgra(hh, s->p);
         }
     }
-    s->card.assign(out_card, out_card + s->n);
-    s->small_idx.clear();
-    s->have_ec_vec = false;
-    std::vector<int32_t> small_pos(s->n, -1);
-    if (s->algo == LASH_HMH) {
-        double dummy;
-        for (uint32_t i = 0; i < s->n; ++i)
-            if (!hmh_ec_closed_form(out_card[i], out_card[i], &dummy)) { small_pos[i] = (int32_t)s->small_idx.size(); s->small_idx.push_back(i); }
-    }
-    // (the device copies the --max-dist filter reads: lash_sketch_set_pair_block_within)
-    if ((rc = reserve(ctx, s->d_card, (size_t)s->n * 8))) return rc;
-    if ((rc = reserve(ctx, s->d_small, (size_t)s->n * 4))) return rc;
-    HIPCHK(ctx, hipMemcpyAsync(s->d_card.ptr, out_card, (size_t)s->n * 8, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(s->d_small.ptr, small_pos.data(), (size_t)s->n * 4, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    return LASH_OK;
+    return lash_set_take_cardinalities(ctx, s, out_card);
 }
 
 int lash_sketch_set_prepare(lash_ctx *ctx, lash_sketch_set *ref, lash_sketch_set *qry)
@@ -322,23 +403,7 @@ int lash_sketch_set_prepare(lash_ctx *ctx, lash_sketch_set *ref, lash_sketch_set
     int rc;
     if (ref->n == 0 || qry->n == 0) return LASH_OK;
     if (ref->algo == LASH_HMH) {
-        // expected collisions of small pairs (lash_sketch_set_hmh_expected_collisions): the query side's cell vectors, once, when
-        // both sides have small members and the vectors fit a third of the free memory (else they are made per block)
-        if (!ref->small_idx.empty() && !qry->small_idx.empty() && !qry->have_ec_vec) {
-            size_t free_b = 0, total_b = 0;
-            const size_t need = qry->small_idx.size() * (size_t)65536 * 8;
-            if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && need <= free_b / 3) {
-                std::vector<double> cards(qry->small_idx.size());
-                for (size_t j = 0; j < cards.size(); ++j) cards[j] = qry->card[qry->small_idx[j]];
-                if ((rc = reserve(ctx, qry->ec_vec, need))) return rc;
-                if ((rc = reserve(ctx, ctx->ec_card, cards.size() * 8))) return rc;
-                HIPCHK(ctx, hipMemcpyAsync(ctx->ec_card.ptr, cards.data(), cards.size() * 8, hipMemcpyHostToDevice, ctx->stream));
-                HIPCHK(ctx, launch_collision_vectors(static_cast<const double *>(ctx->ec_card.ptr), (uint32_t)cards.size(),
-                                                     static_cast<double *>(qry->ec_vec.ptr), ctx->stream));
-                HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-                qry->have_ec_vec = true;
-            }
-        }
+        if (!ref->small_idx.empty() && (rc = lash_set_ec_vectors(ctx, qry))) return rc;       // (no small row: no small pair)
         static const bool words_kernel = getenv("LASH_HMH_PAIRS_WORDS") != nullptr;      // A/B knob: the u16-pair kernel on the images
         if (words_kernel) return LASH_OK;
         if ((rc = lash_set_build_planes(ctx, ref, true))) return rc;                     // (both layouts in one pass when ref == qry)
@@ -406,24 +471,10 @@ int lash_sketch_set_pair_block(lash_ctx *ctx, const lash_sketch_set *ref, uint32
     if (np == 0) return LASH_OK;
     (void)hipSetDevice(ctx->device);
     int rc;
-    // [sum_or_union f64 | c_or_zero u32 | n u32]
-    if ((rc = reserve(ctx, ctx->st_img, np * 16 + 64))) return rc;
-    double *d_u = static_cast<double *>(ctx->st_img.ptr);
-    uint32_t *d_c = reinterpret_cast<uint32_t *>(d_u + np), *d_n = d_c + np;
-    if ((rc = lash_sketch_set_pair_block_device(ctx, ref, r0, r1, qry, n_cols, triangle, ull_estimator, d_c, d_n, d_u))) return rc;
-    if (ref->algo != LASH_ULL) {
-        if (!out_c_or_zero) return LASH_EINVAL;
-        HIPCHK(ctx, hipMemcpyAsync(out_c_or_zero, d_c, np * 4, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    if (ref->algo == LASH_HMH) {
-        if (!out_n) return LASH_EINVAL;
-        HIPCHK(ctx, hipMemcpyAsync(out_n, d_n, np * 4, hipMemcpyDeviceToHost, ctx->stream));
-    } else {
-        if (!out_sum_or_union) return LASH_EINVAL;
-        HIPCHK(ctx, hipMemcpyAsync(out_sum_or_union, d_u, np * 8, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    return LASH_OK;
+    PairOut d;
+    if ((rc = lash_pair_out_reserve(ctx, np, d))) return rc;
+    if ((rc = lash_sketch_set_pair_block_device(ctx, ref, r0, r1, qry, n_cols, triangle, ull_estimator, d.c, d.n, d.u))) return rc;
+    return lash_pair_out_fetch(ctx, ref->algo, np, d, out_c_or_zero, out_n, out_sum_or_union);
 }
 
 int lash_sketch_set_hmh_expected_collisions(lash_ctx *ctx, const lash_sketch_set *ref, uint32_t r0, uint32_t r1, const lash_sketch_set *qry,
@@ -437,17 +488,7 @@ int lash_sketch_set_hmh_expected_collisions(lash_ctx *ctx, const lash_sketch_set
     if (rc) return rc;
     if (eb.nrs == 0 || eb.nqs == 0) return LASH_OK;
     if (!out_ec) return LASH_EINVAL;
-    std::vector<double> x((size_t)eb.nrs * eb.nqs);
-    HIPCHK(ctx, hipMemcpyAsync(x.data(), eb.X, x.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    for (uint32_t q0 = 0; q0 < eb.nqs; q0 += eb.q_step) {
-        const uint32_t nq = std::min(eb.q_step, eb.nqs - q0);
-        const double *chunk = x.data() + (size_t)eb.nrs * q0;
-        for (uint32_t i = 0; i < eb.nrs; ++i) {
-            double *row = out_ec + (size_t)(ref->small_idx[eb.rbase + i] - r0) * n_cols;
-            for (uint32_t j = 0; j < nq; ++j) row[qry->small_idx[q0 + j]] = hmh_ec_from_cell_sum(chunk[(size_t)i * nq + j]);
-        }
-    }
+    if ((rc = lash_set_ec_scatter(ctx, eb, ref, r0, qry, n_cols, out_ec))) return rc;
     if (n_small_pairs) *n_small_pairs = (uint64_t)eb.nrs * eb.nqs;
     return LASH_OK;
 }

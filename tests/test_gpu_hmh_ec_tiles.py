@@ -80,7 +80,7 @@ def test_whole_matrix_every_tile_and_the_gaps(table):
     assert (rcard > 2.0 ** 19).sum() == 31 and (ccard > 2.0 ** 19).sum() == 40
     with lash_amd.Context(0) as ctx:
         got = ctx.hmh_pair_expected_collisions(rcard, ccard)
-        again = ctx.hmh_pair_expected_collisions(rcard, ccard)                       # same queries: the cached vectors (ec_qry_cards)
+        again = ctx.hmh_pair_expected_collisions(rcard, ccard)                       # same queries: the bound query set's cached vectors
         part = ctx.hmh_pair_expected_collisions(rcard[130:], ccard)                    # other rows against them: 2 x 4 tiles
     want, small = _check(got, table, ri, ci, rcard, ccard, "300 x 391", t0)
     assert (want[~small] > 0.5).all() and (want[150] == 1.8446744073709552e19).all() and (want[:, 200] == 1.8446744073709552e19).all()
@@ -98,6 +98,41 @@ def test_edges(table, m, n):
     with lash_amd.Context(0) as ctx:
         got = ctx.hmh_pair_expected_collisions(rcard, ccard)
     _check(got, table, ri, ci, rcard, ccard, "%d x %d" % (m, n), t0)
+
+
+def test_query_vectors_are_kept_only_for_the_same_cardinalities(table):
+    """lash_hmh_pair_expected_collisions keeps the bound query set and its cell vectors while the qry_card values repeat.  A call
+    whose queries differ in ONE small cardinality (same length, same smallness) must not be answered from them: bit for bit what a
+    fresh context returns, and another value than before in that column."""
+    import lash_amd
+    t0 = time.perf_counter()
+    ri, ci = E.row_rule(40), E.col_rule(30)
+    ci2 = ci.copy()
+    ci2[17] = 90                                                                     # (col_rule stays below 83)
+    r, q, q2 = table.cards[ri], table.cards[ci], table.cards[ci2]
+    with lash_amd.Context(0) as ctx:
+        first = ctx.hmh_pair_expected_collisions(r, q)
+        second = ctx.hmh_pair_expected_collisions(r, q2)
+    with lash_amd.Context(0) as ctx:
+        fresh = ctx.hmh_pair_expected_collisions(r, q2)
+    _check(first, table, ri, ci, r, q, "40 x 30", t0)
+    _check(second, table, ri, ci2, r, q2, "40 x 30, column 17 replaced", t0)
+    assert np.array_equal(second, fresh)
+    assert (second[:, 17] != first[:, 17]).all() and np.array_equal(np.delete(second, 17, axis=1), np.delete(first, 17, axis=1))
+
+
+def test_row_blocks_past_8192_small_rows(table):
+    """lash_hmh_pair_expected_collisions sends at most 8192 small rows (4 GiB of reference vectors) through lash_set_ec_block at a
+    time: 8200 small rows x 3 small columns is one full block and one of 8 rows, which are the point.  About 4.3 GB of vectors on
+    the device."""
+    import lash_amd
+    t0 = time.perf_counter()
+    ri, ci = E.row_rule(8200), E.col_rule(3)
+    r, q = table.cards[ri], table.cards[ci]
+    with lash_amd.Context(0) as ctx:
+        got = ctx.hmh_pair_expected_collisions(r, q)
+    want, small = _check(got, table, ri, ci, r, q, "8200 x 3", t0)
+    assert small.all() and len(np.unique(want[8192:], axis=0)) == 8
 
 
 def _set(ctx, n, rule, shift, large_at):

@@ -5,6 +5,7 @@ sketch types against the whole-matrix entries."""
 import os
 import subprocess
 import sys
+from fractions import Fraction
 
 import numpy as np
 import pytest
@@ -145,6 +146,27 @@ def test_hmh_set_cardinalities_with_leading_zero_counts_above_39():
     assert len(set(got)) > 15
 
 
+def _assert_yardstick(algo, p, est, ref, qry, got):
+    """The whole-matrix entries run the same code as the set blocks they are compared with below (at row offset 0), so their result
+    is held to a yardstick of its own here: numpy's register scan (hmh), the exact rational sum rounded once (hll), the host
+    estimator on the oracle-merged sketch within the bounds of tests/test_gpu_dist.py (ull)."""
+    import lash_amd
+    if algo == "hmh":
+        wc, wn = _numpy_counts(ref.view(np.uint16), qry.view(np.uint16))
+        assert np.array_equal(got["c_or_zero"], wc) and np.array_equal(got["n_counts"], wn)
+        return
+    tol = ((1 << p) + 1024) * 2.0 ** -52 if est == "fgra" else 2 * 0.001 * 0.7608621002725182 / (1 << p) ** 0.5
+    for i in range(len(ref)):
+        for j in range(len(qry)):
+            if algo == "hll":
+                mx = np.maximum(ref[i, 33:], qry[j, 33:])
+                assert got["c_or_zero"][i, j] == (mx == 0).sum()
+                assert got["sum_or_union"][i, j] == float(sum(Fraction(int(c), 1 << r) for r, c in enumerate(np.bincount(mx)) if c))
+            else:
+                want = lash_amd.ull_estimate(O.merge_images(O.ULL, p, ref[i], qry[j])[8:], p, est)
+                assert got["sum_or_union"][i, j] == pytest.approx(want, rel=tol, abs=0.0), (i, j)
+
+
 @pytest.mark.parametrize("algo,p,est", [("hmh", 0, "fgra"), ("hll", 12, "fgra"), ("hll", 8, "fgra"), ("ull", 11, "fgra"), ("ull", 11, "ml")])
 def test_row_blocks_triangle_and_order_equal_the_whole_matrix_entries(algo, p, est):
     import lash_amd
@@ -161,6 +183,7 @@ def test_row_blocks_triangle_and_order_equal_the_whole_matrix_entries(algo, p, e
             whole = dict(c_or_zero=z, sum_or_union=s_)
         else:
             whole = dict(sum_or_union=ctx.ull_pair_union_estimates(p, imgs[order], imgs[order], est))
+        _assert_yardstick(algo, p, est, imgs[order], imgs[order], whole)
         s = ctx.sketch_set(algo, p, imgs, order)
         for prepared in (False, True):
             if prepared:
@@ -186,5 +209,6 @@ def test_row_blocks_triangle_and_order_equal_the_whole_matrix_entries(algo, p, e
             assert np.array_equal(got["c_or_zero"], z) and np.array_equal(got["sum_or_union"], s_)
         else:
             assert np.array_equal(got["sum_or_union"], ctx.ull_pair_union_estimates(p, imgs[order][2:19], imgs[:7], est))
+        _assert_yardstick(algo, p, est, imgs[order][2:19], imgs[:7], got)
         q.free()
         s.free()
