@@ -656,6 +656,39 @@ int      lash_sketch_set_pair_block_derep(lash_ctx *ctx, const lash_sketch_set *
                                           double max_dist, lash_derep *acc, lash_derep_stats *stats, uint64_t *bad_pair);
 int      lash_derep_result(const lash_derep *d, uint32_t *out);
 
+/* lash_tree: `lash dist --tree` and `--cluster D --linkage average|complete`, agglomerative clustering of an n x n matrix of f64
+ * distances held in device memory (dist_tree.hip), n - 1 merges back.  The rule: slots 0..n-1 hold one leaf each (size 1, height 0);
+ * step s = 0..n-2 takes, among active slots i < j, the pair with the smallest key (D[i][j], i, j), records merge s = (node of i,
+ * node of j, D[i][j], size_i + size_j), lets the new node n + s live on in slot i and retires slot j; for every other active k,
+ * D[i][k] = D[k][i] becomes
+ *   LASH_LINKAGE_AVERAGE   (size_i * D[i][k] + size_j * D[j][k]) / (size_i + size_j), each operation a separately rounded f64 one
+ *   LASH_LINKAGE_SINGLE    min(D[i][k], D[j][k])
+ *   LASH_LINKAGE_COMPLETE  max(D[i][k], D[j][k])
+ * Node ids follow the scipy convention (leaves 0..n-1, the node of step s is n + s).  The result is a function of the input bits.
+ * lash_tree (every entry takes the context of the tree's device, else LASH_EINVAL):
+ *   create     allocates the n x n f64 matrix on ctx's device; LASH_ENOMEM with a last-error text that states the bytes needed
+ *   set_rows   d is host memory, row-major [r1 - r0][r1]; only columns <= row are read (the triangle) and each value lands at D[r][c]
+ *              and D[c][r].  Blocks may arrive in any order and any split; a cell set twice keeps the later value
+ *   get_rows   full rows [r1 - r0][n] as they stand, before build only (how tests see the mirror)
+ *   build      out holds n - 1 merges in step order; the whole merge loop is queued on ctx's stream (three plain launches per step,
+ *              no host round trip per step) and synchronized once.  It consumes the matrix.  LASH_EINVAL, with a last-error text: a
+ *              row that was never set, a NaN among the cells set_rows read (the text names row and col), a linkage other than the
+ *              three, a second build.  n < 2 has no merges and out may be NULL
+ *   free       the matrix and everything else
+ * stats (may be NULL): steps = n - 1; rescanned_rows = rows whose cached nearest slot had to be recomputed from the full row, the
+ * first fill of n rows included; bytes = the matrix, 8 n^2. */
+typedef struct lash_tree lash_tree;
+typedef struct lash_tree_merge { uint32_t a, b; double height; uint32_t size; } lash_tree_merge;
+typedef struct lash_tree_stats { uint64_t steps, rescanned_rows, bytes; } lash_tree_stats;
+#define LASH_LINKAGE_AVERAGE  0
+#define LASH_LINKAGE_SINGLE   1
+#define LASH_LINKAGE_COMPLETE 2
+int      lash_tree_create(lash_ctx *ctx, uint32_t n, lash_tree **out);
+int      lash_tree_set_rows(lash_ctx *ctx, lash_tree *t, uint32_t r0, uint32_t r1, const double *d);
+int      lash_tree_get_rows(lash_ctx *ctx, const lash_tree *t, uint32_t r0, uint32_t r1, double *out);
+int      lash_tree_build(lash_ctx *ctx, lash_tree *t, int linkage, lash_tree_merge *out, lash_tree_stats *stats);
+void     lash_tree_free(lash_ctx *ctx, lash_tree *t);
+
 /* HyperMinHash sets: hyperminhash's expected_collisions(n, m) for the pairs of a block in which BOTH sketches hold at most 2^19
  * distinct k-mers (the regime in which the crate walks 65 536 cells per pair; lash_hmh_pair_expected_collisions below):
  * out_ec[(r - r0) * n_cols + c] for exactly those pairs — the other entries are left untouched, lash_dist_rows derives theirs in

@@ -48,6 +48,18 @@ class DerepStats(C.Structure):
                 ("evaluated", C.c_uint64), ("representatives", C.c_uint64)]
 
 
+class TreeMerge(C.Structure):
+    """lash_tree_merge: one step of lash_tree_build (scipy node ids)"""
+    _fields_ = [("a", C.c_uint32), ("b", C.c_uint32), ("height", C.c_double), ("size", C.c_uint32)]
+
+
+class TreeStats(C.Structure):
+    """lash_tree_stats: what one lash_tree_build did"""
+    _fields_ = [("steps", C.c_uint64), ("rescanned_rows", C.c_uint64), ("bytes", C.c_uint64)]
+
+
+LINKAGE_AVERAGE, LINKAGE_SINGLE, LINKAGE_COMPLETE = 0, 1, 2
+
 _vp, _u64, _u32, _int = C.c_void_p, C.c_uint64, C.c_uint32, C.c_int
 _PP = C.POINTER(Params)
 _LP = C.POINTER(Layout)
@@ -178,6 +190,11 @@ PROTOTYPES = {
     "lash_sketch_set_pair_block_derep": (_int, [_vp, _vp, _u32, _u32, _vp, _u32, _int, _int, _int, _int, _vp, C.c_double, _vp,
                                                  C.POINTER(DerepStats), C.POINTER(_u64)]),
     "lash_derep_result": (_int, [_vp, _vp]),
+    "lash_tree_create": (_int, [_vp, _u32, C.POINTER(_vp)]),
+    "lash_tree_set_rows": (_int, [_vp, _vp, _u32, _u32, _vp]),
+    "lash_tree_get_rows": (_int, [_vp, _vp, _u32, _u32, _vp]),
+    "lash_tree_build": (_int, [_vp, _vp, _int, _vp, C.POINTER(TreeStats)]),
+    "lash_tree_free": (None, [_vp, _vp]),
     "lash_synth_genomes_device": (_int, [_vp, _u64, _u32, _u64, _vp]),
 }
 

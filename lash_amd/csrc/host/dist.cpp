@@ -33,6 +33,11 @@
 // --derep D (not upstream; same files only): greedy representatives in row order, "within D" meaning that --max-dist D prints the pair.
 // A row is decided from the representatives among the rows before it (lash_sketch_set_pair_block_derep, one lash_derep), so the blocks
 // run in row order on one worker; the N lines are written once, at the end.
+// --tree / --linkage L (not upstream; same files only): agglomerative clustering of the whole matrix of printed distances.  A block's pair
+// statistics come back as for the unfiltered run, -t threads turn them into the exact doubles (dist_block_values: the numbers the list
+// form prints, before rounding to six decimals) and the block's triangle rows go into the run's one N x N matrix on the first device
+// (lash_tree_set_rows; other devices' workers hand theirs over through the host).  After the last block lash_tree_build merges on the
+// device; --tree writes the Newick text, --cluster D --linkage average|complete the clusters of the cut at D (newick.hpp).
 #include "dist.hpp"
 
 #include <dirent.h>
@@ -57,6 +62,7 @@
 #include "dist_format.hpp"
 #include "json_out.hpp"
 #include "name_order.hpp"
+#include "newick.hpp"
 #include "zstd_dl.hpp"
 
 namespace lashhost {
@@ -176,6 +182,8 @@ std::string load_input(const DistOptions &opt, const Timing &timing, DistInput &
     in.same_sketches = rf["sketches"] == qf["sketches"];                                              // all-vs-all: one file, read once
     if (opt.has_cluster && !(in.same_files && in.same_sketches))
         return "--cluster needs an all-vs-all run: -q and -r must name the same sketch files";
+    if (opt.tree && !(in.same_files && in.same_sketches))
+        return "--tree needs an all-vs-all run: -q and -r must name the same sketch files";
     if (opt.has_derep && !(in.same_files && in.same_sketches))
         return "--derep needs an all-vs-all run: -q and -r must name the same sketch files";
     // utils.rs:111-127: the maps' key order (a repeated name is one entry carrying its last sketch)
@@ -312,7 +320,19 @@ struct Run {
     // --derep: the one worker's accumulator (created by it: rep[] lives on its device)
     lash_derep *derep = nullptr;
     lash_derep_stats dr{};                                       // (LASH_CLI_TIMING: summed over the blocks; representatives: the last block's)
-    ~Run() { for (lash_top *p : tops) lash_top_free(p); for (lash_cluster *p : clusters) lash_cluster_free(p); lash_derep_free(derep); if (out) fclose(out); }
+    // --tree / --linkage: the run's one matrix, on the first device, with a context of its own; workers take tree_mu to hand rows over
+    lash_ctx *tree_ctx = nullptr;
+    lash_tree *tree = nullptr;
+    std::mutex tree_mu;
+    ~Run()
+    {
+        for (lash_top *p : tops) lash_top_free(p);
+        for (lash_cluster *p : clusters) lash_cluster_free(p);
+        lash_derep_free(derep);
+        lash_tree_free(tree_ctx, tree);
+        if (tree_ctx) lash_ctx_destroy(tree_ctx);
+        if (out) fclose(out);
+    }
 };
 
 struct Block { uint32_t i0, i1, n_cols; };
@@ -333,6 +353,7 @@ struct Worker {
     std::vector<uint32_t> w_row, w_col;                          // --max-dist / --top: the block's survivors
     std::vector<double> w_dist;
     std::vector<lash_top_key> col_bound, row_bound;              // --top: this worker's K-th key per name, for the next block
+    std::vector<double> tree_rows;                               // --tree: the block's distances on their way into the matrix
     Worker(Run &r, size_t i) : run(r), opt(r.opt), in(r.in), wi(i), ds(r.dev.on(r.devices[i])) {}
     ~Worker() { lash_host_free_pinned(C); lash_host_free_pinned(N); lash_host_free_pinned(U); lash_host_free_pinned(EC); if (ctx) lash_ctx_destroy(ctx); }
 
@@ -417,8 +438,8 @@ struct Worker {
         return block_failure(b, rc, bad);
     }
 
-    // every pair: the pair tables come back and -t threads format them
-    std::string block_all(const Block &b)
+    // the unfiltered block's pair tables (and small pairs' expected collisions), copied back
+    std::string pair_tables(const Block &b, BlockTables &bt)
     {
         const bool hll = in.algo_id == LASH_HLL, ull = in.algo_id == LASH_ULL;
         const size_t np = (size_t)(b.i1 - b.i0) * b.n_cols;
@@ -442,10 +463,33 @@ struct Worker {
             have_ec = n_small != 0;
         }
         if (rc != LASH_OK) return block_failure(b, rc);
-        BlockTables bt;
         bt.c_or_zero = C; bt.n_counts = N; bt.sum_or_union = U; bt.hmh_ec = have_ec ? EC : nullptr; bt.ld = b.n_cols;
+        return "";
+    }
+
+    // every pair: the pair tables come back and -t threads format them
+    std::string block_all(const Block &b)
+    {
+        BlockTables bt;
+        const std::string f = pair_tables(b, bt);
+        if (!f.empty()) return f;
         return dist_block_rows(in.algo_id, in.prec, in.k, opt.model, opt.fp32, run.bias, b.i0, b.i1, in.same_files, in.nq, run.dev.rcard.data(), run.dev.qcard.data(),
                                bt, in.row_name, in.col_name, in.col_tab, in.row_id.data(), in.col_id.data(), opt.matrix, run.fmt_threads, row_text, opt.measure);
+    }
+
+    // --tree: the pair tables come back, -t threads make the exact distances of the block's triangle rows, and those go into the matrix
+    std::string block_tree(const Block &b)
+    {
+        BlockTables bt;
+        std::string f = pair_tables(b, bt);
+        if (!f.empty()) return f;
+        tree_rows.resize((size_t)(b.i1 - b.i0) * b.i1);
+        f = dist_block_values(in.algo_id, in.prec, in.k, opt.model, opt.fp32, run.bias, b.i0, b.i1, run.dev.rcard.data(), bt, in.row_name, in.row_id.data(),
+                              run.fmt_threads, tree_rows.data());
+        if (!f.empty()) return f;
+        std::lock_guard<std::mutex> lk(run.tree_mu);
+        const int rc = lash_tree_set_rows(run.tree_ctx, run.tree, b.i0, b.i1, tree_rows.data());
+        return rc == LASH_OK ? "" : std::string(lash_strerror(rc)) + " " + lash_ctx_last_error(run.tree_ctx);
     }
 
     // Blocks in turn, each through its mode's step, written in block order whatever order the workers finish in.
@@ -453,7 +497,7 @@ struct Worker {
     {
         int rc = lash_ctx_create(&ctx, run.devices[wi]);
         if (rc == LASH_OK) rc = lash_ctx_set_layout(ctx, &opt.layout);
-        if (rc == LASH_OK && opt.has_cluster) rc = lash_cluster_create(ctx, in.nr, &run.clusters[wi]);
+        if (rc == LASH_OK && opt.has_cluster && !opt.use_tree()) rc = lash_cluster_create(ctx, in.nr, &run.clusters[wi]);
         if (rc == LASH_OK && opt.has_derep) rc = lash_derep_create(ctx, in.nr, &run.derep);
         std::string my_fail = rc == LASH_OK ? "" : std::string(lash_strerror(rc));
         const uint32_t n_blocks = (uint32_t)run.block_begin.size() - 1;
@@ -466,7 +510,7 @@ struct Worker {
             { std::lock_guard<std::mutex> lk(run.wmu); skip = !run.fail.empty(); }
             row_text.off.clear(); row_text.len.clear();
             if (my_fail.empty() && !skip)
-                my_fail = opt.top ? block_top(b) : opt.has_cluster ? block_cluster(b) : opt.has_derep ? block_derep(b)
+                my_fail = opt.use_tree() ? block_tree(b) : opt.top ? block_top(b) : opt.has_cluster ? block_cluster(b) : opt.has_derep ? block_derep(b)
                           : opt.has_max_dist ? block_within(b) : block_all(b);
             std::unique_lock<std::mutex> lk(run.wmu);
             run.wcv.wait(lk, [&] { return run.next_to_write == blk; });
@@ -504,6 +548,24 @@ std::string finish_top(Run &run)
     return "";
 }
 
+// every name under label[name], the first name of its cluster in row order: the --cluster text after the header
+void write_clusters(Run &run, const std::vector<uint32_t> &label, uint64_t *n_clusters)
+{
+    const DistInput &in = run.in;
+    std::vector<uint32_t> by_rep(in.nr);
+    std::iota(by_rep.begin(), by_rep.end(), 0u);
+    std::stable_sort(by_rep.begin(), by_rep.end(), [&](uint32_t x, uint32_t y) { return label[x] < label[y]; });
+    std::string text;
+    *n_clusters = 0;
+    for (uint32_t i : by_rep) {
+        *n_clusters += label[i] == i;
+        text.append(in.row_name[label[i]]).push_back('\t');
+        text.append(in.row_name[i]).push_back('\n');
+        if (text.size() >= (1u << 20)) { fwrite(text.data(), 1, text.size(), run.out); text.clear(); }
+    }
+    fwrite(text.data(), 1, text.size(), run.out);
+}
+
 // --cluster: the workers' clusters merged; every name under its cluster's first name, in row order
 std::string finish_cluster(Run &run)
 {
@@ -513,21 +575,42 @@ std::string finish_cluster(Run &run)
         if (!cl[0] || !cl[w] || lash_cluster_merge(cl[0], cl[w]) != LASH_OK) return "cannot merge the --cluster labels";
     std::vector<uint32_t> label(in.nr);
     if (in.nr && (!cl[0] || lash_cluster_labels(cl[0], label.data()) != LASH_OK)) return "cannot read the --cluster labels";
-    std::vector<uint32_t> by_rep(in.nr);
-    std::iota(by_rep.begin(), by_rep.end(), 0u);
-    std::stable_sort(by_rep.begin(), by_rep.end(), [&](uint32_t x, uint32_t y) { return label[x] < label[y]; });
-    std::string text;
     uint64_t n_clusters = 0;
-    for (uint32_t i : by_rep) {
-        n_clusters += label[i] == i;
-        text.append(in.row_name[label[i]]).push_back('\t');
-        text.append(in.row_name[i]).push_back('\n');
-        if (text.size() >= (1u << 20)) { fwrite(text.data(), 1, text.size(), run.out); text.clear(); }
-    }
-    fwrite(text.data(), 1, text.size(), run.out);
+    write_clusters(run, label, &n_clusters);
     if (run.timing.on) fprintf(stderr, "[lash dist] --cluster: %llu pairs looked at, %llu pruned as already joined, %llu joined on the device, "
                                "%llu sent to the host, %llu clusters\n", (unsigned long long)run.cl_pairs.load(), (unsigned long long)run.cl_pruned.load(),
                                (unsigned long long)run.cl_joined.load(), (unsigned long long)run.cl_sent.load(), (unsigned long long)n_clusters);
+    run.timing.mark("--cluster: the clusters written");
+    return "";
+}
+
+// --tree / --linkage: the merges on the device, then the Newick text or the clusters of the cut
+std::string finish_tree(Run &run)
+{
+    const DistInput &in = run.in;
+    const DistOptions &opt = run.opt;
+    const int linkage = opt.linkage < 0 ? LASH_LINKAGE_AVERAGE : opt.linkage;
+    std::vector<lash_tree_merge> merges(in.nr > 1 ? in.nr - 1 : 0);
+    lash_tree_stats st{};
+    const auto t0 = std::chrono::steady_clock::now();
+    const int rc = lash_tree_build(run.tree_ctx, run.tree, linkage, merges.data(), &st);
+    const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    if (rc != LASH_OK) return std::string("--tree: ") + lash_strerror(rc) + " " + lash_ctx_last_error(run.tree_ctx);
+    if (run.timing.on) fprintf(stderr, "[lash dist] --tree: %u names, %llu steps, %llu rescanned rows, %llu matrix bytes, build %.3f ms\n", in.nr,
+                               (unsigned long long)st.steps, (unsigned long long)st.rescanned_rows, (unsigned long long)st.bytes, ms);
+    if (opt.tree) {
+        std::string err;
+        const std::string text = newick_text(in.row_name, merges.data(), err) + "\n";
+        if (!err.empty()) return "--tree: " + err;
+        fwrite(text.data(), 1, text.size(), run.out);
+        run.timing.mark("--tree: the tree written");
+        return "";
+    }
+    std::vector<uint32_t> label;
+    if (!tree_cut_labels(in.nr, merges.data(), opt.cluster_dist, label)) return "--linkage: the merge list is not a tree";
+    uint64_t n_clusters = 0;
+    write_clusters(run, label, &n_clusters);
+    if (run.timing.on) fprintf(stderr, "[lash dist] --cluster --linkage: %llu clusters\n", (unsigned long long)n_clusters);
     run.timing.mark("--cluster: the clusters written");
     return "";
 }
@@ -607,7 +690,8 @@ std::string run_dist(const DistOptions &opt)
     run.gpu_ec = small_ref && small_qry;
     run.out = fopen(opt.output_file.c_str(), "w");
     if (!run.out) return "cannot create " + opt.output_file;
-    if (opt.has_cluster || opt.has_derep) fprintf(run.out, "Representative\tMember\n");
+    if (opt.tree) {}                                                                                 // (the tree is the whole output)
+    else if (opt.has_cluster || opt.has_derep) fprintf(run.out, "Representative\tMember\n");
     else if (!opt.matrix) fprintf(run.out, "Reference\tQuery\tDistance\n");                          // main.rs:409-412
     else for (uint32_t j = 0; j < in.nq; ++j) fprintf(run.out, "\t%s", in.col_name[j].c_str());      // main.rs:439-441
     run.block_begin = plan_blocks(opt, in);
@@ -616,6 +700,12 @@ std::string run_dist(const DistOptions &opt)
     run.fmt_threads = std::max(1, opt.threads / (int)run.devices.size());
     run.tops.assign(run.devices.size(), nullptr);
     run.clusters.assign(run.devices.size(), nullptr);
+    if (opt.use_tree()) {
+        int rc = lash_ctx_create(&run.tree_ctx, run.devices[0]);
+        if (rc != LASH_OK) return std::string("--tree: ") + lash_strerror(rc);
+        if ((rc = lash_tree_create(run.tree_ctx, in.nr, &run.tree)) != LASH_OK)
+            return std::string("--tree: ") + lash_strerror(rc) + " " + lash_ctx_last_error(run.tree_ctx);
+    }
     if (opt.top)
         for (lash_top *&t : run.tops)
             if (lash_top_create(in.same_files ? in.nr : in.nq, opt.top, in.same_files ? 1 : 0, &t) != LASH_OK) return "cannot create the --top lists";
@@ -626,7 +716,8 @@ std::string run_dist(const DistOptions &opt)
         for (auto &t : pool) t.join();
     }
     if (run.fail.empty() && opt.top) run.fail = finish_top(run);
-    if (run.fail.empty() && opt.has_cluster) run.fail = finish_cluster(run);
+    if (run.fail.empty() && opt.use_tree()) run.fail = finish_tree(run);
+    else if (run.fail.empty() && opt.has_cluster) run.fail = finish_cluster(run);
     if (run.fail.empty() && opt.has_derep) run.fail = finish_derep(run);
     fclose(run.out);
     run.out = nullptr;

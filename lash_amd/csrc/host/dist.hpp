@@ -22,6 +22,10 @@ struct DistOptions {
     uint32_t top = 0;          // --top K (1..LASH_TOP_MAX): print only the rows in some name's K nearest (list form only); 0 = off
     bool has_cluster = false;  // --cluster D: single-linkage clusters of a triangle run instead of pairs; names are linked iff --max-dist D prints them
     double cluster_dist = 0.0;
+    bool tree = false;         // --tree: one Newick tree of all names of a triangle run instead of pairs (agglomerative, merged on the device)
+    int linkage = -1;          // --linkage average|single|complete: LASH_LINKAGE_*; -1 = not given (--tree: average; --cluster: single, the
+                               // union-find route, which an explicit single takes too; average / complete cut the tree at D)
+    bool use_tree() const { return tree || (has_cluster && (linkage == LASH_LINKAGE_AVERAGE || linkage == LASH_LINKAGE_COMPLETE)); }
     bool has_derep = false;    // --derep D: greedy representatives of a triangle run in row order; "within D" iff --max-dist D prints the pair
     double derep_dist = 0.0;
     int measure = LASH_MEASURE_JACCARD;   // --containment query|reference: LASH_MEASURE_CONTAIN_*; directional, so the run is a rectangle even

@@ -114,15 +114,54 @@ void append_row(std::string &out, const std::string &rname, const std::vector<st
     out.resize(at0 + format_row(&out[at0], rname, qtab, n_print, dist, row_id, col_id, matrix));
 }
 
+namespace {
+
+const char *const kBiasMsg = ": cardinality estimate <= 5 * 2^p needs the HLL++ bias tables of streaming_algorithms, which are "
+                             "not built in (pass --hll-bias-sim to simulate them, --hll-bias <file from lash hll-bias or tools/ref_probe/extract_hll_bias.py>, or sketch with a smaller -p)";
+
+// The numbers of ONE reference row i: dist[c] for its first n_print columns, before the "same name prints 0" rule.  Returns "" or the
+// message `lash dist` ends with.
+std::string row_distances(int algo, int p, int k, int model, bool fp32, const void *hll_bias, uint32_t i0, uint32_t i, uint32_t n_print,
+                          const double *row_card, const double *col_card, const BlockTables &t, const std::vector<std::string> &row_name,
+                          const std::vector<std::string> &col_name, int measure, double *dist)
+{
+    const bool hll = algo == LASH_HLL, ull = algo == LASH_ULL;
+    const size_t row = (size_t)(i - i0) * t.ld;
+    uint64_t bad_pair = 0;
+    const int drc = lash_dist_rows_measure(algo, p, k, model, fp32 ? 1 : 0, 1, n_print, &row_card[i], col_card, ull ? nullptr : t.c_or_zero + row,
+                                           (hll || ull) ? nullptr : t.n_counts + row, (hll || ull) ? t.sum_or_union + row : nullptr,
+                                           static_cast<const lash_hll_bias *>(hll_bias), t.hmh_ec ? t.hmh_ec + row : nullptr, measure, dist,
+                                           &bad_pair);
+    if (drc == LASH_ERANGE) return "union of " + row_name[i] + " and " + col_name[bad_pair] + kBiasMsg;
+    if (drc != LASH_OK) return lash_strerror(drc);
+    return "";
+}
+
+// rows [i0, i1) on up to `threads` host threads; the first failing row's message in row order, or ""
+template <class Row>
+std::string each_row(uint32_t i0, uint32_t i1, int threads, Row do_row)
+{
+    const uint32_t n_rows = i1 - i0;
+    std::vector<std::string> row_fail(n_rows);
+    const uint32_t nthreads = (uint32_t)std::max(1, std::min<int>(threads, (int)n_rows));
+    std::atomic<uint32_t> next{i0};
+    std::vector<std::thread> pool;
+    auto work = [&]() { std::vector<double> dist; for (uint32_t i = next.fetch_add(1); i < i1; i = next.fetch_add(1)) row_fail[i - i0] = do_row(i, dist); };
+    for (uint32_t th = 1; th < nthreads; ++th) pool.emplace_back(work);
+    work();
+    for (auto &th : pool) th.join();
+    for (const std::string &f : row_fail) if (!f.empty()) return f;
+    return "";
+}
+
+}  // namespace
+
 std::string dist_block_rows(int algo, int p, int k, int model, bool fp32, const void *hll_bias, uint32_t i0, uint32_t i1, bool triangle,
                             uint32_t n_cols_total, const double *row_card, const double *col_card, const BlockTables &t,
                             const std::vector<std::string> &row_name, const std::vector<std::string> &col_name,
                             const std::vector<std::string> &col_tab, const uint32_t *row_id, const uint32_t *col_id, bool matrix, int threads,
                             RowText &text, int measure)
 {
-    static const char *bias_msg = ": cardinality estimate <= 5 * 2^p needs the HLL++ bias tables of streaming_algorithms, which are "
-                                  "not built in (pass --hll-bias-sim to simulate them, --hll-bias <file from lash hll-bias or tools/ref_probe/extract_hll_bias.py>, or sketch with a smaller -p)";
-    const bool hll = algo == LASH_HLL, ull = algo == LASH_ULL;
     const uint32_t n_rows = i1 - i0;
     // slots: row r at off[r], room for its upper bound (list form: the column names' bytes come from a running sum)
     text.off.assign(n_rows, 0);
@@ -138,29 +177,31 @@ std::string dist_block_rows(int algo, int p, int k, int model, bool fp32, const 
         }
         if (text.buf.size() < at) text.buf.resize(at + at / 8);
     }
-    std::vector<std::string> row_fail(n_rows);
-    auto do_row = [&](uint32_t i, std::vector<double> &dist) {
-        const size_t row = (size_t)(i - i0) * t.ld;
+    return each_row(i0, i1, threads, [&](uint32_t i, std::vector<double> &dist) {
         const uint32_t n_print = triangle ? std::min(i + 1, n_cols_total) : n_cols_total;                  // utils.rs:158-160
         if (dist.size() < n_print) dist.resize(n_print);
-        uint64_t bad_pair = 0;
-        const int drc = lash_dist_rows_measure(algo, p, k, model, fp32 ? 1 : 0, 1, n_print, &row_card[i], col_card, ull ? nullptr : t.c_or_zero + row,
-                                               (hll || ull) ? nullptr : t.n_counts + row, (hll || ull) ? t.sum_or_union + row : nullptr,
-                                               static_cast<const lash_hll_bias *>(hll_bias), t.hmh_ec ? t.hmh_ec + row : nullptr, measure, dist.data(),
-                                               &bad_pair);
-        if (drc == LASH_ERANGE) { row_fail[i - i0] = "union of " + row_name[i] + " and " + col_name[bad_pair] + bias_msg; return; }
-        if (drc != LASH_OK) { row_fail[i - i0] = lash_strerror(drc); return; }
-        text.len[i - i0] = format_row(text.buf.data() + text.off[i - i0], row_name[i], col_tab, n_print, dist.data(), row_id[i], col_id, matrix);
-    };
-    const uint32_t nthreads = (uint32_t)std::max(1, std::min<int>(threads, (int)n_rows));
-    std::atomic<uint32_t> next{i0};
-    std::vector<std::thread> pool;
-    auto work = [&]() { std::vector<double> dist; for (uint32_t i = next.fetch_add(1); i < i1; i = next.fetch_add(1)) do_row(i, dist); };
-    for (uint32_t th = 1; th < nthreads; ++th) pool.emplace_back(work);
-    work();
-    for (auto &th : pool) th.join();
-    for (const std::string &f : row_fail) if (!f.empty()) return f;
-    return "";
+        std::string f = row_distances(algo, p, k, model, fp32, hll_bias, i0, i, n_print, row_card, col_card, t, row_name, col_name, measure, dist.data());
+        if (f.empty())
+            text.len[i - i0] = format_row(text.buf.data() + text.off[i - i0], row_name[i], col_tab, n_print, dist.data(), row_id[i], col_id, matrix);
+        return f;
+    });
+}
+
+std::string dist_block_values(int algo, int p, int k, int model, bool fp32, const void *hll_bias, uint32_t i0, uint32_t i1, const double *card,
+                              const BlockTables &t, const std::vector<std::string> &name, const uint32_t *name_id, int threads, double *out)
+{
+    return each_row(i0, i1, threads, [&](uint32_t i, std::vector<double> &) {
+        double *dist = out + (size_t)(i - i0) * i1;
+        std::string f = row_distances(algo, p, k, model, fp32, hll_bias, i0, i, i + 1, card, card, t, name, name, LASH_MEASURE_JACCARD, dist);
+        if (!f.empty()) return f;
+        for (uint32_t c = 0; c <= i; ++c) {
+            if (name_id[c] == name_id[i] || dist[c] == 0.0) dist[c] = 0.0;                                   // main.rs:452-453; -0 (identical
+                                                                                                             // sketches: -ln(1) / k) is the 0 the list form prints
+            else if (dist[c] != dist[c])
+                return "the distance of " + name[i] + " and " + name[c] + " is NaN: the linkage of a tree is undefined";
+        }
+        return f;
+    });
 }
 
 }  // namespace lashhost

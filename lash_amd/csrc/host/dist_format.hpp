@@ -61,5 +61,11 @@ std::string dist_block_rows(int algo, int p, int k, int model, bool fp32, const 
                             const std::vector<std::string> &row_name, const std::vector<std::string> &col_name,
                             const std::vector<std::string> &col_tab, const uint32_t *row_id, const uint32_t *col_id, bool matrix, int threads,
                             RowText &text, int measure = 0);
+// --tree: the same numbers as doubles instead of text, for the triangle rows [i0, i1) of an all-vs-all run (rows and columns are the
+// same names in the same order: one card / name / name_id array).  out is row-major [i1 - i0][i1], the layout lash_tree_set_rows
+// reads; row i gets columns [0, i], a column carrying the row's name 0, and -0 enters as 0.  Returns "" or the message the run ends with: the one of
+// dist_block_rows, or the two names of a NaN distance.
+std::string dist_block_values(int algo, int p, int k, int model, bool fp32, const void *hll_bias, uint32_t i0, uint32_t i1, const double *card,
+                              const BlockTables &t, const std::vector<std::string> &name, const uint32_t *name_id, int threads, double *out);
 
 }  // namespace lashhost

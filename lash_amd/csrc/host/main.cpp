@@ -10,7 +10,8 @@
 // --file-order (rows / columns in list-file order instead of the reference's seeded hash-map order), --max-dist D (print only
 // the pairs with distance <= D), --top K (only each name's K nearest), --cluster D (single-linkage clusters of an all-vs-all instead
 // of pairs), --derep D (greedy representatives of an all-vs-all in row order), --containment query|reference (the distance of the
-// containment fraction instead of the Jaccard-derived one; always a rectangle) (reference rows per GPU call); both: --layout SPEC (or $LASH_LAYOUT): the crate-internal rules as data, see `lash_layout`
+// containment fraction instead of the Jaccard-derived one; always a rectangle), --tree / --linkage average|single|complete (one Newick
+// tree of an all-vs-all, merged on the GPU; with --cluster D, that tree cut at D) (reference rows per GPU call); both: --layout SPEC (or $LASH_LAYOUT): the crate-internal rules as data, see `lash_layout`
 // in include/lash_gfx950.h.
 #include <chrono>
 #include <cmath>
@@ -88,6 +89,14 @@ void usage()
             "                     else a member of the first such representative.  Row order is the priority: pass --file-order to\n"
             "                     set it with the list file.  Output: Representative<TAB>Member, one line per name; not with --dm,\n"
             "                     --top, --max-dist, --cluster or more than one entry in --devices\n"
+            "      --tree         all-vs-all only: one Newick tree of all names instead of pairs, followed by a newline.  Agglomerative\n"
+            "                     clustering of the printed distances, merged on the GPU (8 x N^2 bytes of device memory); --linkage\n"
+            "                     says how [default: average, UPGMA].  Branch lengths are half the difference of the merge heights; a\n"
+            "                     name with any of ()[]':;, or white space is quoted.  Not with --dm, --top, --max-dist, --cluster,\n"
+            "                     --derep or --containment\n"
+            "      --linkage <average|single|complete>  with --tree or --cluster: the distance of two clusters is the mean, the\n"
+            "                     smallest or the largest distance of their members.  --cluster D --linkage average|complete cuts\n"
+            "                     that tree at height D (same output form); single [the default of --cluster] is --cluster as above\n"
             "      --containment <query|reference>  the distance of the containment fraction instead of the Jaccard-derived one, for sides\n"
             "                     of different size (a genome against a metagenome, a plasmid against its host): query = how much of the\n"
             "                     query is in the reference, reference = how much of the reference is in the query.  Directional, so\n"
@@ -261,13 +270,22 @@ int cmd_sketch(int argc, char **argv)
     return 0;
 }
 
+// what `dist` looks a prefix's three files up by (dist.cpp find_files): the part after the last '/', without a leading "./"
+std::string prefix_stem(const std::string &prefix)
+{
+    const size_t slash = prefix.find_last_of('/');
+    std::string stem = slash == std::string::npos ? prefix : prefix.substr(slash + 1);
+    if (stem.rfind("./", 0) == 0) stem = stem.substr(2);
+    return stem;
+}
+
 int cmd_dist(int argc, char **argv)
 {
     Args a;
     std::string err;
     const std::map<std::string, std::string> alias = {{"q", "query"}, {"r", "reference"}, {"o", "output_file"}, {"t", "threads"},
                                                       {"e", "estimator"}, {"m", "model"}};
-    if (!parse(argc, argv, 2, alias, {"fp32", "dm", "file-order", "hll-bias-sim", "help"}, a, err)) { fprintf(stderr, "error: %s\n", err.c_str()); return 2; }
+    if (!parse(argc, argv, 2, alias, {"fp32", "dm", "file-order", "hll-bias-sim", "tree", "help"}, a, err)) { fprintf(stderr, "error: %s\n", err.c_str()); return 2; }
     if (a.flags.count("help")) { usage(); return 0; }
     if (!a.kv.count("query") || !a.kv.count("reference")) {
         fprintf(stderr, "error: the following required arguments were not provided:\n  --query <query>\n  --reference <reference>\n");
@@ -364,6 +382,27 @@ int cmd_dist(int argc, char **argv)
         if (opt.matrix) { fprintf(stderr, "error: --containment cannot be used with --dm (list form only)\n"); return 2; }
         if (opt.has_cluster) { fprintf(stderr, "error: --containment cannot be used with --cluster (clusters need a symmetric distance)\n"); return 2; }
         if (opt.has_derep) { fprintf(stderr, "error: --containment cannot be used with --derep (representatives need a symmetric distance)\n"); return 2; }
+    }
+    if (a.flags.count("tree")) {
+        if (opt.matrix) { fprintf(stderr, "error: --tree cannot be used with --dm (a tree is not a matrix)\n"); return 2; }
+        if (opt.top) { fprintf(stderr, "error: --tree cannot be used with --top (a tree needs every pair)\n"); return 2; }
+        if (opt.has_max_dist) { fprintf(stderr, "error: --tree cannot be used with --max-dist (a tree needs every pair)\n"); return 2; }
+        if (opt.has_cluster) { fprintf(stderr, "error: --tree cannot be used with --cluster (the whole tree or its cut at D, not both)\n"); return 2; }
+        if (opt.has_derep) { fprintf(stderr, "error: --tree cannot be used with --derep (a tree or greedy representatives, not both)\n"); return 2; }
+        if (opt.measure != LASH_MEASURE_JACCARD) { fprintf(stderr, "error: --tree cannot be used with --containment (a tree needs a symmetric distance)\n"); return 2; }
+        if (prefix_stem(opt.query_prefix) != prefix_stem(opt.ref_prefix)) {
+            fprintf(stderr, "error: --tree needs an all-vs-all run: -q and -r must name the same sketch files\n");
+            return 2;
+        }
+        opt.tree = true;
+    }
+    if (a.kv.count("linkage")) {
+        const std::string &v = a.kv["linkage"];
+        if (v == "average") opt.linkage = LASH_LINKAGE_AVERAGE;
+        else if (v == "single") opt.linkage = LASH_LINKAGE_SINGLE;
+        else if (v == "complete") opt.linkage = LASH_LINKAGE_COMPLETE;
+        else { fprintf(stderr, "error: invalid value '%s' for --linkage: average, single or complete is required\n", v.c_str()); return 2; }
+        if (!opt.tree && !opt.has_cluster) { fprintf(stderr, "error: --linkage needs --tree or --cluster (it says how their clusters are merged)\n"); return 2; }
     }
     err = layout_from_option(a.kv.count("layout") ? a.kv["layout"] : "", opt.layout);
     if (!err.empty()) { fprintf(stderr, "error: %s\n", err.c_str()); return 2; }
