@@ -689,6 +689,25 @@ int      lash_tree_get_rows(lash_ctx *ctx, const lash_tree *t, uint32_t r0, uint
 int      lash_tree_build(lash_ctx *ctx, lash_tree *t, int linkage, lash_tree_merge *out, lash_tree_stats *stats);
 void     lash_tree_free(lash_ctx *ctx, lash_tree *t);
 
+/* lash_tree_build_nj: `lash dist --tree --nj`, a neighbour-joining tree of the same lash_tree matrix (dist_nj.hip; create / set_rows /
+ * get_rows / free as above).  The rule: slots 0..n-1 hold one leaf each, the slot index being the label that breaks ties.  R[i] starts
+ * from +0.0 and takes D[i][c] for c = 0, 1, .., n-1 in that order, c = i skipped, each add rounded.  Join step s = 0, 1, .. while r >= 3
+ * (r = active slots, w = (double)(r - 2)): for active i < j, Q = ((w * D[i][j]) - R[i]) - R[j], three separately rounded operations;
+ * the pair with the smallest key (Q, i, j) is joined with
+ *   len_i = D[i][j] * 0.5 + (R[i] - R[j]) / (2.0 * w)      len_j = D[i][j] - len_i      join s = (node of i, node of j, len_i, len_j)
+ * and for every other active k
+ *   v = ((D[i][k] + D[j][k]) - D[i][j]) * 0.5      R[k] = ((R[k] - D[i][k]) - D[j][k]) + v      D[i][k] = D[k][i] = v
+ * then R[i] = ((R[i] + R[j]) - (double)r * D[i][j]) * 0.5; node n + s lives on in slot i and slot j retires.  At r = 2 the closing
+ * record (node of i, node of j, D[i][j], 0) of the remaining slots i < j.  out holds n - 1 records for n >= 2 (n - 2 joins, then the
+ * closing record), none for n < 2 (out may be NULL).  Lengths may be negative and are reported as computed.  Row sums are carried,
+ * never re-summed: the result is a function of the input bits.
+ * The join loop is queued on ctx's stream (three plain launches per step, no host round trip per step) and synchronized once.  It
+ * consumes the matrix, as lash_tree_build does.  LASH_EINVAL, with a last-error text: a row that was never set, a second build (of
+ * either kind), a NaN or an infinite value among the cells set_rows read (the text names row and col; inf - inf would put a NaN into
+ * the arg-min).  stats (may be NULL): steps = records written, rescanned_rows = 0, bytes = 8 n^2. */
+typedef struct lash_nj_join { uint32_t a, b; double len_a, len_b; } lash_nj_join;
+int      lash_tree_build_nj(lash_ctx *ctx, lash_tree *t, lash_nj_join *out, lash_tree_stats *stats);
+
 /* HyperMinHash sets: hyperminhash's expected_collisions(n, m) for the pairs of a block in which BOTH sketches hold at most 2^19
  * distinct k-mers (the regime in which the crate walks 65 536 cells per pair; lash_hmh_pair_expected_collisions below):
  * out_ec[(r - r0) * n_cols + c] for exactly those pairs — the other entries are left untouched, lash_dist_rows derives theirs in

@@ -58,6 +58,11 @@ class TreeStats(C.Structure):
     _fields_ = [("steps", C.c_uint64), ("rescanned_rows", C.c_uint64), ("bytes", C.c_uint64)]
 
 
+class NjJoin(C.Structure):
+    """lash_nj_join: one record of lash_tree_build_nj (scipy node ids)"""
+    _fields_ = [("a", C.c_uint32), ("b", C.c_uint32), ("len_a", C.c_double), ("len_b", C.c_double)]
+
+
 LINKAGE_AVERAGE, LINKAGE_SINGLE, LINKAGE_COMPLETE = 0, 1, 2
 
 _vp, _u64, _u32, _int = C.c_void_p, C.c_uint64, C.c_uint32, C.c_int
@@ -194,6 +199,7 @@ PROTOTYPES = {
     "lash_tree_set_rows": (_int, [_vp, _vp, _u32, _u32, _vp]),
     "lash_tree_get_rows": (_int, [_vp, _vp, _u32, _u32, _vp]),
     "lash_tree_build": (_int, [_vp, _vp, _int, _vp, C.POINTER(TreeStats)]),
+    "lash_tree_build_nj": (_int, [_vp, _vp, _vp, C.POINTER(TreeStats)]),
     "lash_tree_free": (None, [_vp, _vp]),
     "lash_synth_genomes_device": (_int, [_vp, _u64, _u32, _u64, _vp]),
 }

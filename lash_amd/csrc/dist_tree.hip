@@ -32,23 +32,11 @@
 //
 // Later launches read what earlier ones left in device memory; the kernel boundary on one stream is the only ordering used.  There is
 // no host round trip per step, no graph capture and no grid-wide synchronization.
-#include "lash_ctx.h"
+#include "dist_tree.h"
 
 #include <new>
 
 #pragma clang fp contract(off)
-
-struct lash_tree {
-    int device = 0;
-    uint32_t n = 0;
-    bool built = false;
-    double *d_D = nullptr;                        // [n][n]
-    double *d_stage = nullptr;                    // set_rows: a piece of the caller's triangle on its way into d_D
-    size_t stage_cap = 0;                         // doubles
-    std::vector<uint8_t> row_set;                 // host: which rows set_rows has seen
-    bool has_nan = false;                         // host: the first NaN cell set_rows has seen, in (row, col) order of arrival
-    uint32_t nan_row = 0, nan_col = 0;
-};
 
 namespace lash {
 
@@ -56,7 +44,6 @@ constexpr uint32_t TREE_SELECT_THREADS = 1024;    // one workgroup; tests/test_g
 constexpr uint32_t TREE_UPDATE_THREADS = 256;     // one thread per slot
 constexpr uint32_t TREE_RESCAN_THREADS = 256;     // one workgroup per listed row
 constexpr uint32_t TREE_RESCAN_GRID = 512;        // workgroups of a rescan launch; each takes list entries b, b + grid, ...
-constexpr uint32_t TREE_NONE = 0xFFFFFFFFu;
 
 struct TreeStep { uint32_t i, j, size_i, size_j; };
 
@@ -74,42 +61,6 @@ struct TreeState {
     uint32_t n;
     int linkage;
 };
-
-namespace {
-
-// the smaller of two keys (d, a, b), lexicographic; no NaN ever gets here (lash_tree_build refuses it)
-__device__ inline bool key_less(double d0, uint32_t a0, uint32_t b0, double d1, uint32_t a1, uint32_t b1)
-{
-    if (d0 != d1) return d0 < d1;
-    if (a0 != a1) return a0 < a1;
-    return b0 < b1;
-}
-
-__device__ inline void wave_min_key(double &d, uint32_t &a, uint32_t &b)
-{
-    for (int off = 32; off > 0; off >>= 1) {
-        const double od = __shfl_xor(d, off, 64);
-        const uint32_t oa = __shfl_xor(a, off, 64), ob = __shfl_xor(b, off, 64);
-        if (key_less(od, oa, ob, d, a, b)) { d = od; a = oa; b = ob; }
-    }
-}
-
-// The workgroup's minimum key in every thread of wave 0 (the other waves return their own wave's).  WAVES = blockDim.x / 64.
-template <uint32_t WAVES>
-__device__ inline void block_min_key(double &d, uint32_t &a, uint32_t &b, double *s_d, uint32_t *s_a, uint32_t *s_b)
-{
-    wave_min_key(d, a, b);
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    if (lane == 0) { s_d[wave] = d; s_a[wave] = a; s_b[wave] = b; }
-    __syncthreads();
-    if (wave == 0) {
-        if (lane < WAVES) { d = s_d[lane]; a = s_a[lane]; b = s_b[lane]; }
-        else { d = HUGE_VAL; a = TREE_NONE; b = TREE_NONE; }
-        wave_min_key(d, a, b);
-    }
-}
-
-}  // namespace
 
 // D[r][c] = D[c][r] = v for the staged rows [r0, r1) x columns [0, r]; stage is row-major [r1 - r0][ld]
 __global__ void __launch_bounds__(256) tree_scatter_kernel(double *__restrict__ D, const double *__restrict__ stage, uint32_t n, uint32_t r0, uint32_t ld)
@@ -284,8 +235,11 @@ int lash_tree_set_rows(lash_ctx *ctx, lash_tree *t, uint32_t r0, uint32_t r1, co
     const uint32_t ld = r1;
     for (uint32_t r = r0; r < r1; ++r) {
         const double *row = d + (size_t)(r - r0) * ld;
-        for (uint32_t c = 0; c <= r && !t->has_nan; ++c)
-            if (row[c] != row[c]) { t->has_nan = true; t->nan_row = r; t->nan_col = c; }
+        for (uint32_t c = 0; c <= r && !(t->has_nan && t->has_inf); ++c) {
+            const double v = row[c];
+            if (v != v) { if (!t->has_nan) { t->has_nan = true; t->nan_row = r; t->nan_col = c; } }
+            else if (std::isinf(v) && !t->has_inf) { t->has_inf = true; t->inf_row = r; t->inf_col = c; }
+        }
         t->row_set[r] = 1;
     }
     // pieces of at most ~64 MB of rows (and 65 535 rows: the grid's y) go through one staging buffer

@@ -37,7 +37,8 @@
 // statistics come back as for the unfiltered run, -t threads turn them into the exact doubles (dist_block_values: the numbers the list
 // form prints, before rounding to six decimals) and the block's triangle rows go into the run's one N x N matrix on the first device
 // (lash_tree_set_rows; other devices' workers hand theirs over through the host).  After the last block lash_tree_build merges on the
-// device; --tree writes the Newick text, --cluster D --linkage average|complete the clusters of the cut at D (newick.hpp).
+// device; --tree writes the Newick text, --cluster D --linkage average|complete the clusters of the cut at D (newick.hpp).  --tree --nj
+// fills the same matrix and lets lash_tree_build_nj join it: the neighbour-joining tree, unrooted, no heights to cut.
 #include "dist.hpp"
 
 #include <dirent.h>
@@ -589,6 +590,22 @@ std::string finish_tree(Run &run)
 {
     const DistInput &in = run.in;
     const DistOptions &opt = run.opt;
+    if (opt.nj) {
+        std::vector<lash_nj_join> joins(in.nr > 1 ? in.nr - 1 : 0);
+        lash_tree_stats st{};
+        const auto t0 = std::chrono::steady_clock::now();
+        const int rc = lash_tree_build_nj(run.tree_ctx, run.tree, joins.data(), &st);
+        const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        if (rc != LASH_OK) return std::string("--tree --nj: ") + lash_strerror(rc) + " " + lash_ctx_last_error(run.tree_ctx);
+        if (run.timing.on) fprintf(stderr, "[lash dist] --tree --nj: %u names, %llu steps, %llu matrix bytes, build %.3f ms\n", in.nr,
+                                   (unsigned long long)st.steps, (unsigned long long)st.bytes, ms);
+        std::string err;
+        const std::string text = newick_text_nj(in.row_name, joins.data(), err) + "\n";
+        if (!err.empty()) return "--tree --nj: " + err;
+        fwrite(text.data(), 1, text.size(), run.out);
+        run.timing.mark("--tree --nj: the tree written");
+        return "";
+    }
     const int linkage = opt.linkage < 0 ? LASH_LINKAGE_AVERAGE : opt.linkage;
     std::vector<lash_tree_merge> merges(in.nr > 1 ? in.nr - 1 : 0);
     lash_tree_stats st{};

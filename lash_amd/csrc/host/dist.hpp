@@ -23,6 +23,7 @@ struct DistOptions {
     bool has_cluster = false;  // --cluster D: single-linkage clusters of a triangle run instead of pairs; names are linked iff --max-dist D prints them
     double cluster_dist = 0.0;
     bool tree = false;         // --tree: one Newick tree of all names of a triangle run instead of pairs (agglomerative, merged on the device)
+    bool nj = false;           // --nj (with --tree): the neighbour-joining tree instead of a linkage tree (lash_tree_build_nj)
     int linkage = -1;          // --linkage average|single|complete: LASH_LINKAGE_*; -1 = not given (--tree: average; --cluster: single, the
                                // union-find route, which an explicit single takes too; average / complete cut the tree at D)
     bool use_tree() const { return tree || (has_cluster && (linkage == LASH_LINKAGE_AVERAGE || linkage == LASH_LINKAGE_COMPLETE)); }

@@ -11,7 +11,7 @@
 // the pairs with distance <= D), --top K (only each name's K nearest), --cluster D (single-linkage clusters of an all-vs-all instead
 // of pairs), --derep D (greedy representatives of an all-vs-all in row order), --containment query|reference (the distance of the
 // containment fraction instead of the Jaccard-derived one; always a rectangle), --tree / --linkage average|single|complete (one Newick
-// tree of an all-vs-all, merged on the GPU; with --cluster D, that tree cut at D) (reference rows per GPU call); both: --layout SPEC (or $LASH_LAYOUT): the crate-internal rules as data, see `lash_layout`
+// tree of an all-vs-all, merged on the GPU; with --cluster D, that tree cut at D), --tree --nj (the neighbour-joining tree instead, joined on the GPU) (reference rows per GPU call); both: --layout SPEC (or $LASH_LAYOUT): the crate-internal rules as data, see `lash_layout`
 // in include/lash_gfx950.h.
 #include <chrono>
 #include <cmath>
@@ -97,6 +97,10 @@ void usage()
             "      --linkage <average|single|complete>  with --tree or --cluster: the distance of two clusters is the mean, the\n"
             "                     smallest or the largest distance of their members.  --cluster D --linkage average|complete cuts\n"
             "                     that tree at height D (same output form); single [the default of --cluster] is --cluster as above\n"
+            "      --nj           with --tree: the neighbour-joining tree (Saitou & Nei; the rule of PHYLIP neighbor, QuickTree, rapidNJ,\n"
+            "                     mashtree) instead of a linkage tree, joined on the GPU from the same matrix.  It assumes no clock, so\n"
+            "                     it is the one to read as a phylogeny; it is unrooted (the root prints as a trifurcation) and a branch\n"
+            "                     length may be negative.  Not with --linkage or --cluster: an NJ tree has no heights to cut\n"
             "      --containment <query|reference>  the distance of the containment fraction instead of the Jaccard-derived one, for sides\n"
             "                     of different size (a genome against a metagenome, a plasmid against its host): query = how much of the\n"
             "                     query is in the reference, reference = how much of the reference is in the query.  Directional, so\n"
@@ -285,7 +289,7 @@ int cmd_dist(int argc, char **argv)
     std::string err;
     const std::map<std::string, std::string> alias = {{"q", "query"}, {"r", "reference"}, {"o", "output_file"}, {"t", "threads"},
                                                       {"e", "estimator"}, {"m", "model"}};
-    if (!parse(argc, argv, 2, alias, {"fp32", "dm", "file-order", "hll-bias-sim", "tree", "help"}, a, err)) { fprintf(stderr, "error: %s\n", err.c_str()); return 2; }
+    if (!parse(argc, argv, 2, alias, {"fp32", "dm", "file-order", "hll-bias-sim", "tree", "nj", "help"}, a, err)) { fprintf(stderr, "error: %s\n", err.c_str()); return 2; }
     if (a.flags.count("help")) { usage(); return 0; }
     if (!a.kv.count("query") || !a.kv.count("reference")) {
         fprintf(stderr, "error: the following required arguments were not provided:\n  --query <query>\n  --reference <reference>\n");
@@ -403,6 +407,12 @@ int cmd_dist(int argc, char **argv)
         else if (v == "complete") opt.linkage = LASH_LINKAGE_COMPLETE;
         else { fprintf(stderr, "error: invalid value '%s' for --linkage: average, single or complete is required\n", v.c_str()); return 2; }
         if (!opt.tree && !opt.has_cluster) { fprintf(stderr, "error: --linkage needs --tree or --cluster (it says how their clusters are merged)\n"); return 2; }
+    }
+    if (a.flags.count("nj")) {
+        if (opt.has_cluster) { fprintf(stderr, "error: --nj cannot be used with --cluster (a neighbour-joining tree has no heights to cut)\n"); return 2; }
+        if (opt.linkage >= 0) { fprintf(stderr, "error: --nj cannot be used with --linkage (neighbour joining is a rule of its own, not a linkage)\n"); return 2; }
+        if (!opt.tree) { fprintf(stderr, "error: --nj needs --tree (it says which tree --tree writes)\n"); return 2; }
+        opt.nj = true;
     }
     err = layout_from_option(a.kv.count("layout") ? a.kv["layout"] : "", opt.layout);
     if (!err.empty()) { fprintf(stderr, "error: %s\n", err.c_str()); return 2; }

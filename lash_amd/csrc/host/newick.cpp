@@ -76,6 +76,65 @@ std::string newick_text(const std::vector<std::string> &names, const lash_tree_m
     return out;
 }
 
+std::string newick_text_nj(const std::vector<std::string> &names, const lash_nj_join *joins, std::string &err)
+{
+    const uint32_t n = (uint32_t)names.size();
+    err.clear();
+    if (n == 0) return ";";
+    if (n == 1) return newick_label(names[0]) + ";";
+    char buf[48];
+    const lash_nj_join &last = joins[n - 2];
+    if (n == 2) {
+        if (!((last.a == 0 && last.b == 1) || (last.a == 1 && last.b == 0))) { err = "the join list is not a tree"; return ""; }
+        snprintf(buf, sizeof buf, ":%.10g", last.len_a * 0.5);
+        return "(" + newick_label(names[last.a]) + buf + "," + newick_label(names[last.b]) + buf + ");";
+    }
+    // nodes 0 .. 2n - 3; every one a child exactly once, the closing record's two included
+    const uint32_t root = 2 * n - 3;
+    std::vector<uint8_t> used((size_t)2 * n - 2, 0);
+    std::vector<double> len((size_t)2 * n - 2, 0.0);                                 // the branch above every node
+    for (uint32_t s = 0; s + 2 < n; ++s) {
+        const uint32_t c[2] = {joins[s].a, joins[s].b};
+        const double l[2] = {joins[s].len_a, joins[s].len_b};
+        for (int e = 0; e < 2; ++e) {
+            if (c[e] >= n + s || used[c[e]]) { err = "the join list is not a tree"; return ""; }
+            used[c[e]] = 1;
+            len[c[e]] = l[e];
+        }
+    }
+    if (last.a > root || last.b > root || last.a == last.b || used[last.a] || used[last.b] || (last.a != root && last.b != root)) {
+        err = "the join list is not a tree: its closing record does not hold the last two nodes";
+        return "";
+    }
+    const uint32_t other = last.a == root ? last.b : last.a;
+    len[other] = last.len_a;
+    std::string out;
+    // depth first without recursion, as newick_text; the root has a third child
+    struct Frame { uint32_t node, done; };
+    std::vector<Frame> stack{{root, 0}};
+    while (!stack.empty()) {
+        Frame &f = stack.back();
+        const bool leaf = f.node < n;
+        const uint32_t n_children = leaf ? 0 : f.node == root ? 3 : 2;
+        if (f.done < n_children) {
+            out += f.done == 0 ? '(' : ',';
+            const uint32_t child = f.done == 0 ? joins[f.node - n].a : f.done == 1 ? joins[f.node - n].b : other;
+            ++f.done;
+            stack.push_back({child, 0});                                             // (f is dead from here on)
+            continue;
+        }
+        if (leaf) out += newick_label(names[f.node]);
+        else out += ')';
+        if (f.node == root) out += ';';
+        else {
+            snprintf(buf, sizeof buf, ":%.10g", len[f.node]);
+            out += buf;
+        }
+        stack.pop_back();
+    }
+    return out;
+}
+
 bool tree_cut_labels(uint32_t n, const lash_tree_merge *merges, double max_height, std::vector<uint32_t> &label)
 {
     label.resize(n);
@@ -103,13 +162,25 @@ bool tree_cut_labels(uint32_t n, const lash_tree_merge *merges, double max_heigh
 
 extern "C" {
 
-// The two functions above for callers outside C++ (tests through liblash_host.so).  newick: n NUL-terminated names; returns the
+// The functions above for callers outside C++ (tests through liblash_host.so).  newick: n NUL-terminated names; returns the
 // malloc'd text (free with lash_host_free) or NULL when the merge list is not a tree.  cut: 0, or -1 for such a list.
 char *lash_host_newick(const char *const *names, uint32_t n, const lash_tree_merge *merges)
 {
     std::vector<std::string> v(names, names + n);
     std::string err;
     const std::string text = lashhost::newick_text(v, merges, err);
+    if (!err.empty()) return nullptr;
+    char *p = static_cast<char *>(malloc(text.size() + 1));
+    if (p) memcpy(p, text.c_str(), text.size() + 1);
+    return p;
+}
+
+// newick_text_nj likewise: n - 1 records; NULL when the list is not such a tree
+char *lash_host_newick_nj(const char *const *names, uint32_t n, const lash_nj_join *joins)
+{
+    std::vector<std::string> v(names, names + n);
+    std::string err;
+    const std::string text = lashhost::newick_text_nj(v, joins, err);
     if (!err.empty()) return nullptr;
     char *p = static_cast<char *>(malloc(text.size() + 1));
     if (p) memcpy(p, text.c_str(), text.size() + 1);

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""tools/tree_rate.py [N[,N...]] [RUNS] [CLI_N] [L] — what `lash dist --tree` costs, and what the route it replaces costs.
+"""tools/tree_rate.py [--nj] [N[,N...]] [RUNS] [CLI_N] [L] — what `lash dist --tree` costs, and what the route it replaces costs.
 
 Part 1, per N (default 4096,16384): lash_tree_build (average linkage) on a random uniform N x N matrix through the ABI: one warm-up build,
 then RUNS (default 3) timed ones, each on a freshly uploaded matrix (a build consumes it).  Prints every wall time, the median, the
@@ -8,7 +8,11 @@ spread (max - min) and the rescanned rows the build reports.
 Part 2, for CLI_N (default: the largest N; 0 = skip): CLI_N hmh k=16 sketches of L-base genomes (default 1 000 000: above 2^19 distinct
 k-mers, so no expected-collision matrix product on either route) made on the device as families of 64, written as a sketch-file set
 under /dev/shm; then, after one warm-up run of each, RUNS times each, with -t 16 and --file-order: `lash dist --dm` (the matrix as text, the route to an external
-clustering tool) and `lash dist --tree` (with its LASH_CLI_TIMING line).  Prints every wall time, medians and spreads."""
+clustering tool) and `lash dist --tree` (with its LASH_CLI_TIMING line).  Prints every wall time, medians and spreads.
+
+--nj: part 1 also times lash_tree_build_nj the same way, after the average-linkage lines of the same N, and prints beside its median the
+traffic model of the scan (8 bytes x the sum over r = N .. 3 of r x N / 2 cells, about 2 N^3 bytes: retired columns are still fetched) and
+the GB/s that implies; part 2 also runs `lash dist --tree --nj`."""
 import os
 import statistics
 import subprocess
@@ -24,7 +28,10 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import lash_amd  # noqa: E402
 import host_lib as H  # noqa: E402
 import tree_model as T  # noqa: E402
+import nj_model as NJ  # noqa: E402
 
+WITH_NJ = "--nj" in sys.argv
+sys.argv = [a for a in sys.argv if a != "--nj"]
 NS = [int(x) for x in (sys.argv[1] if len(sys.argv) > 1 else "4096,16384").split(",")]
 RUNS = int(sys.argv[2]) if len(sys.argv) > 2 else 3
 CLI_N = int(sys.argv[3]) if len(sys.argv) > 3 else max(NS)
@@ -55,6 +62,24 @@ for n in NS:
             walls.append(t2 - t1)
             rescanned.append(st["rescanned_rows"])
     summary("N %d lash_tree_build average (rescanned rows %s)" % (n, sorted(set(rescanned))), walls)
+    walls = []
+    for run in range(RUNS + 1 if WITH_NJ else 0):
+        t = T.Tree(ctx, n)
+        t0 = time.perf_counter()
+        t.set_rows(0, n, d)
+        t1 = time.perf_counter()
+        jn, st = NJ.njbuild(t)
+        t2 = time.perf_counter()
+        t.free()
+        print("N %d %s: set_rows %.3f s, lash_tree_build_nj %.3f s, %d steps, %d matrix bytes"
+              % (n, "warm-up" if run == 0 else "run %d" % run, t1 - t0, t2 - t1, st["steps"], st["bytes"]), flush=True)
+        if run:
+            walls.append(t2 - t1)
+    if WITH_NJ:
+        summary("N %d lash_tree_build_nj" % n, walls)
+        scan_bytes = 8 * sum(r * n // 2 for r in range(3, n + 1))
+        print("N %d lash_tree_build_nj: scan traffic model %.3f TB (2 N^3 = %.3f TB), %.0f GB/s at the median"
+              % (n, scan_bytes / 1e12, 2 * n ** 3 / 1e12, scan_bytes / 1e9 / statistics.median(walls)), flush=True)
     del d
 
 if CLI_N:
@@ -101,12 +126,14 @@ if CLI_N:
     ctx.close()
     env = dict(os.environ, LASH_CLI_TIMING="1")
     walls = {"--dm": [], "--tree": []}
+    if WITH_NJ:
+        walls["--tree --nj"] = []
     try:
         for run in range(RUNS + 1):                           # run 0 warms up: not counted
             for key in walls:
-                path = os.path.join(work, "out" + key.replace("--", "_"))
+                path = os.path.join(work, "out" + key.replace("--", "_").replace(" ", ""))
                 t0 = time.perf_counter()
-                r = subprocess.run([H.CLI, "dist", "-q", "w", "-r", "w", "-o", path, "-t", "16", "--file-order", key], cwd=work, capture_output=True,
+                r = subprocess.run([H.CLI, "dist", "-q", "w", "-r", "w", "-o", path, "-t", "16", "--file-order"] + key.split(), cwd=work, capture_output=True,
                                    text=True, env=env)
                 wall = time.perf_counter() - t0
                 print("run %d: N %d %s: rc %d, %.2f s wall, %d output bytes" % (run, CLI_N, key, r.returncode, wall, os.path.getsize(path)), flush=True)
@@ -115,8 +142,8 @@ if CLI_N:
                     sys.exit(1)
                 if run:
                     walls[key].append(wall)
-                if key == "--tree":
-                    print("".join(ln + "\n" for ln in r.stderr.split("\n") if "--tree:" in ln or (run == 0 and "[lash dist]" in ln)), end="", flush=True)
+                if key != "--dm":
+                    print("".join(ln + "\n" for ln in r.stderr.split("\n") if key + ":" in ln or (run == 0 and "[lash dist]" in ln)), end="", flush=True)
                 os.remove(path)
         for key, w in walls.items():
             summary("N %d lash dist %s" % (CLI_N, key), w)
