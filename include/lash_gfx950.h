@@ -724,6 +724,35 @@ int      lash_sketch_set_hmh_expected_collisions(lash_ctx *ctx, const lash_sketc
 int    lash_hmh_pair_expected_collisions(lash_ctx *ctx, const double *ref_card, uint32_t n_ref, const double *qry_card, uint32_t n_qry,
                                          double *out_ec);
 
+/* ---- growth: the cardinality of the running union along orderings of a set (`lash growth`, prefix_union.hip) ----
+ * orders holds n_orders index lists of `len` members each, every entry < the set's size; a list need not be a permutation (repeats
+ * are legal and change nothing).  out_card[o * len + t] is the distinct-count estimate of U(o, t) = member orders[o][0] U ... U member
+ * orders[o][t], bit for bit what lash_hmh_cardinality / lash_hll_cardinality / lash_ull_estimate give for the image of that union (the
+ * number lash_sketch_set_cardinalities returns for a single image): one workgroup per (order, slice of the register table) folds the
+ * images in LDS and keeps the register histogram up to date, the O(histogram) finish runs on the host.  A HyperMinHash step whose
+ * union holds a register with more than 39 leading zeros is re-folded with lash_merge_images_device and summed in register order.
+ *   opts (may be NULL; a zero field = the library chooses)
+ *     slices             the table is cut into that many contiguous runs of whole 32-bit words, sizes differing by at most one word
+ *                        (clamped to the word count); one workgroup per (order, slice)
+ *     hist_budget_bytes  bound on the device histogram buffer, orders in flight x len x 1 KiB: the orders go in chunks under it, at
+ *                        least one order per chunk [256 MiB]
+ *   The numbers do not depend on opts: the histograms are sums of integers.
+ *   LASH_EINVAL  NULL arguments, len == 0 with n_orders > 0, an index >= the set's size (*bad_index = its position in orders), a bad
+ *                ull_estimator for an UltraLogLog set, a table that does not fit on chip: supported are hmh, hll (p 4-16) and ull p 3-16
+ *                (lash_ctx_last_error says so for ull p >= 17)
+ *   LASH_ERANGE  an HLL union fell into the bias-table regime and `tables` does not cover it; *bad_index = o * len + t of the first
+ *                such entry in (order, step) order
+ * The set's own state (the cardinalities it has taken, what prepare built) is left untouched.  Synchronous.
+ * _plan: what a call with these arguments would run with — out_plan->slices, and out_plan->hist_budget_bytes = the bytes of the
+ * histogram buffer it allocates.  Same LASH_EINVAL for an unsupported table. */
+typedef struct { uint32_t slices; uint64_t hist_budget_bytes; } lash_prefix_union_opts;   /* 0 = the library chooses */
+int lash_sketch_set_prefix_union_cardinalities(lash_ctx *ctx, lash_sketch_set *set, const uint32_t *orders, uint32_t n_orders,
+                                               uint32_t len, int ull_estimator, const lash_hll_bias *tables,
+                                               const lash_prefix_union_opts *opts /* may be NULL */,
+                                               double *out_card /* [n_orders][len] */, uint64_t *bad_index);
+int lash_sketch_set_prefix_union_plan(lash_ctx *ctx, const lash_sketch_set *set, uint32_t n_orders, uint32_t len,
+                                      const lash_prefix_union_opts *opts, lash_prefix_union_opts *out_plan);
+
 /* Synthetic genomes of SURVEY.md §8(d) generated in HBM (bench / tests): genome ids first..first+n-1,
  * n_bases ASCII bytes each, written back to back at d_out. */
 int lash_synth_genomes_device(lash_ctx *ctx, uint64_t first_genome, uint32_t n_genomes, uint64_t n_bases, uint8_t *d_out);

@@ -63,6 +63,11 @@ class NjJoin(C.Structure):
     _fields_ = [("a", C.c_uint32), ("b", C.c_uint32), ("len_a", C.c_double), ("len_b", C.c_double)]
 
 
+class PrefixUnionOpts(C.Structure):
+    """lash_prefix_union_opts: how lash_sketch_set_prefix_union_cardinalities cuts its work (0 = the library chooses)"""
+    _fields_ = [("slices", C.c_uint32), ("hist_budget_bytes", C.c_uint64)]
+
+
 LINKAGE_AVERAGE, LINKAGE_SINGLE, LINKAGE_COMPLETE = 0, 1, 2
 
 _vp, _u64, _u32, _int = C.c_void_p, C.c_uint64, C.c_uint32, C.c_int
@@ -201,6 +206,8 @@ PROTOTYPES = {
     "lash_tree_build": (_int, [_vp, _vp, _int, _vp, C.POINTER(TreeStats)]),
     "lash_tree_build_nj": (_int, [_vp, _vp, _vp, C.POINTER(TreeStats)]),
     "lash_tree_free": (None, [_vp, _vp]),
+    "lash_sketch_set_prefix_union_cardinalities": (_int, [_vp, _vp, _vp, _u32, _u32, _int, _vp, C.POINTER(PrefixUnionOpts), _vp, C.POINTER(_u64)]),
+    "lash_sketch_set_prefix_union_plan": (_int, [_vp, _vp, _u32, _u32, C.POINTER(PrefixUnionOpts), C.POINTER(PrefixUnionOpts)]),
     "lash_synth_genomes_device": (_int, [_vp, _u64, _u32, _u64, _vp]),
 }
 

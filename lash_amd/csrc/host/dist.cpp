@@ -772,4 +772,46 @@ std::string run_hll_bias(const HllBiasOptions &opt)
     return "";
 }
 
+std::string load_dist_side(const DistOptions &opt, DistSide &out)
+{
+    DistOptions one = opt;
+    one.query_prefix = opt.ref_prefix;
+    one.matrix = true;                                               // (no tabbed column names: nothing is printed from here)
+    const Timing timing{false};                                      // (the caller reports its own times)
+    DistInput in;
+    const std::string err = load_input(one, timing, in);
+    if (!err.empty()) return err;
+    out.algo_id = in.algo_id;
+    out.prec = in.prec;
+    out.ull_est = in.ull_est;
+    out.k = in.k;
+    out.names = std::move(in.rnames);
+    out.order = std::move(in.rorder);
+    out.images = std::move(in.rimg_store);
+    return "";
+}
+
+std::string load_hll_bias(const DistOptions &opt, int algo_id, int prec, const char *tag, lash_hll_bias **out)
+{
+    *out = nullptr;
+    if (algo_id != LASH_HLL) return "";
+    if (!opt.hll_bias_file.empty()) {
+        const int brc = lash_hll_bias_load(opt.hll_bias_file.c_str(), out);
+        if (brc != LASH_OK) return "cannot read HLL++ bias tables from " + opt.hll_bias_file + ": " + lash_strerror(brc);
+    }
+    if (opt.hll_bias_sim) {
+        lash_ctx *ctx = nullptr;
+        const int rc = lash_ctx_create(&ctx, opt.device);
+        if (rc != LASH_OK) return std::string("--hll-bias-sim: ") + lash_strerror(rc);
+        std::vector<double> raw, b;
+        std::string line;
+        const std::string err = simulate_bias(ctx, prec, 0, 0, 42, raw, b, line);
+        lash_ctx_destroy(ctx);
+        if (!err.empty()) return err;
+        if (lash_hll_bias_from_arrays(out, prec, raw.data(), b.data(), (uint32_t)raw.size()) != LASH_OK) return "--hll-bias-sim: bad table";
+        fprintf(stderr, "[%s] --hll-bias-sim: %s, %s\n", tag, SIM_NOTE, line.c_str());
+    }
+    return "";
+}
+
 }  // namespace lashhost

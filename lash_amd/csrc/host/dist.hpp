@@ -50,4 +50,17 @@ struct HllBiasOptions {
 };
 std::string run_hll_bias(const HllBiasOptions &opt);
 
+// One collection as `dist` reads a side of a run ({prefix}_sketches.bin, {prefix}_files.json, {prefix}_parameters.json), for the
+// commands that take a single collection (growth.cpp): opt.ref_prefix names it; estimator, file_order and layout are honoured.
+struct DistSide {
+    int algo_id = 0, prec = 0, ull_est = 0, k = 0;
+    std::vector<std::string> names;      // the name file
+    std::vector<uint32_t> order;         // the rows, as indices into names: the reference's key order, or list order under file_order
+    std::vector<uint8_t> images;         // the sketch file, inflated: one image per name
+};
+std::string load_dist_side(const DistOptions &opt, DistSide &out);
+// The HLL++ tables of a run, as `dist` gets them (--hll-bias FILE / --hll-bias-sim on opt.device): *out stays NULL for hmh / ull sketches
+// and when no tables were asked for.  tag names the command in the provenance line.  The caller frees *out (lash_hll_bias_free).
+std::string load_hll_bias(const DistOptions &opt, int algo_id, int prec, const char *tag, lash_hll_bias **out);
+
 }  // namespace lashhost

@@ -2,6 +2,7 @@
 // (/root/reference/src/main.rs:26-177) on top of liblash_gfx950.so.
 //   lash sketch -f LIST [-o sketch] [-k 16] [-t N] [-a hmh|hll|ull] [-p 10] [-s 42]        (main.rs:30-96, 180-279)
 //   lash dist   -q PREFIX -r PREFIX [-o dist] [-t N] [-e fgra|ml] [-m 1|0] [--fp32] [--dm]   (main.rs:107-176, 280-617)
+//   lash growth -r PREFIX [-o growth] [--orders P] [--seed S] [--file-order] [-e fgra|ml] [-t N]   (not upstream: union cardinality along orderings)
 //   lash hll-bias -o FILE [-p P[,P...]] [--points N] [--trials T] [--seed S] [--device D]    (not upstream: HLL++ bias tables, simulated)
 // Extras that do not exist upstream: --gpus N / --device D / --devices LIST (which GPUs to use, one worker each), --batch-mb M, --stream-mb M (files
 // larger than M MiB are streamed in chunks with on-device accumulation), --hmh-x-low, --min-count M [--count-cells-log2 L] (drop the k-mers a
@@ -13,6 +14,7 @@
 // containment fraction instead of the Jaccard-derived one; always a rectangle), --tree / --linkage average|single|complete (one Newick
 // tree of an all-vs-all, merged on the GPU; with --cluster D, that tree cut at D), --tree --nj (the neighbour-joining tree instead, joined on the GPU) (reference rows per GPU call); both: --layout SPEC (or $LASH_LAYOUT): the crate-internal rules as data, see `lash_layout`
 // in include/lash_gfx950.h.
+#include <algorithm>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -25,6 +27,7 @@
 
 #include "../../../include/lash_gfx950.h"
 #include "dist.hpp"
+#include "growth.hpp"
 #include "sketch_files.hpp"
 
 using namespace lashhost;
@@ -45,6 +48,7 @@ void usage()
             "Usage: lash <COMMAND>\n\nCommands:\n"
             "  sketch  Sketches genomes and serializes them, sketches are compressed\n"
             "  dist    Computes distance between sketches\n"
+            "  growth  Union cardinality of a collection along orderings: how much each further genome adds\n"
             "  hll-bias  Simulates the HLL++ bias tables on the GPU and writes the file dist --hll-bias reads\n\n"
             "sketch options:\n"
             "  -f, --file <file>            One file containing list of FASTA/FASTQ files (.gz/.zstd supported), one per line\n"
@@ -111,6 +115,20 @@ void usage()
             "      --hll-bias-sim hll sketches only: simulate the bias table of their precision on the GPU at start-up (as lash hll-bias\n"
             "                     does with its defaults) and use it; regenerated measurements, not the reference crate's numbers.\n"
             "                     Not with --hll-bias; $LASH_HLL_BIAS is ignored\n"
+            "growth options:\n"
+            "  -r, --reference <prefix>     The collection: {prefix}_sketches.bin, _files.json and _parameters.json, read as dist reads a side\n"
+            "  -o, --output_file <name>     Where the table goes [default: growth]: Order<TAB>Step<TAB>Name<TAB>Union<TAB>New, one line per\n"
+            "                               (order, step), steps from 1.  Union = the estimated distinct k-mers of the order's first Step names\n"
+            "                               (the number dist's cardinalities give for the merged sketch), New = Union minus the line before\n"
+            "                               (an estimate can go down by a hair: New may be negative); both with three decimals\n"
+            "      --orders <P>             Orderings to walk [default: 1].  Order 0 is the row order: the reference's hash-map key order, or\n"
+            "                               list-file order with --file-order.  Orders 1 .. P-1 are Fisher-Yates shuffles of it, drawn from\n"
+            "                               splitmix64 seeded with --seed: the same options give the same file\n"
+            "      --seed <S>               Seed of the shuffles [default: 42]\n"
+            "      --file-order             order 0 in list-file order\n"
+            "  -e, --estimator <fgra|ml>  -t, --threads <n> (formatting only; the bytes do not depend on it)  --device <D>\n"
+            "      --hll-bias <file> | --hll-bias-sim   as for dist: without tables an hll union with an estimate <= 5 * 2^p is refused\n"
+            "                               All orders are folded on the GPU in one pass per chunk of orders; hmh, hll, and ull up to -p 16\n"
             "hll-bias options:\n"
             "  -o, --output <file>          Where the tables go (text: \"p <p> <n>\" then n lines \"<raw estimate> <bias>\")\n"
             "  -p, --precision <p[,p...]>   Precisions to simulate, each 4-18 [default: 4,5,...,18]\n"
@@ -422,6 +440,59 @@ int cmd_dist(int argc, char **argv)
     return 0;
 }
 
+// lash growth -r PREFIX [-o growth] [--orders P] [--seed S] [--file-order] [-e fgra|ml] [-t N] [--hll-bias FILE | --hll-bias-sim] [--device D]
+int cmd_growth(int argc, char **argv)
+{
+    Args a;
+    std::string err;
+    const std::map<std::string, std::string> alias = {{"r", "reference"}, {"o", "output_file"}, {"t", "threads"}, {"e", "estimator"}};
+    // one collection, one table: whatever else `dist` takes (-q, --dm, --top, ...) is not an option of this command
+    const std::vector<std::string> known = {"reference", "output_file", "threads", "estimator", "orders", "seed", "file-order", "hll-bias",
+                                            "hll-bias-sim", "device", "layout", "help"};
+    for (int i = 2; i < argc; ++i) {
+        const std::string s = argv[i];
+        if (s.rfind("--", 0) != 0) continue;
+        const std::string key = s.substr(2, s.find('=') == std::string::npos ? std::string::npos : s.find('=') - 2);
+        if (std::find(known.begin(), known.end(), key) == known.end()) { fprintf(stderr, "error: unexpected argument '--%s'\n", key.c_str()); return 2; }
+    }
+    if (!parse(argc, argv, 2, alias, {"file-order", "hll-bias-sim", "help"}, a, err)) { fprintf(stderr, "error: %s\n", err.c_str()); return 2; }
+    if (a.flags.count("help")) { usage(); return 0; }
+    if (!a.kv.count("reference")) { fprintf(stderr, "error: the following required arguments were not provided:\n  --reference <reference>\n"); return 2; }
+    GrowthOptions opt;
+    opt.side.ref_prefix = opt.side.query_prefix = a.kv["reference"];
+    opt.output_file = a.kv.count("output_file") ? a.kv["output_file"] : "growth";
+    opt.side.estimator = a.kv.count("estimator") ? a.kv["estimator"] : "fgra";
+    if (opt.side.estimator != "fgra" && opt.side.estimator != "ml") {
+        fprintf(stderr, "error: invalid value '%s' for --estimator: fgra or ml is required\n", opt.side.estimator.c_str());
+        return 2;
+    }
+    uint64_t orders = 1, threads = std::thread::hardware_concurrency(), dev = 0;
+    if (a.kv.count("orders") && (!to_u64(a.kv["orders"], orders) || orders < 1 || orders > 0xFFFFFFFFull)) {
+        fprintf(stderr, "error: invalid value '%s' for --orders: a positive integer is required\n", a.kv["orders"].c_str());
+        return 2;
+    }
+    if (a.kv.count("seed") && !to_u64(a.kv["seed"], opt.seed)) { fprintf(stderr, "error: invalid value for --seed\n"); return 2; }
+    if (a.kv.count("threads") && !to_u64(a.kv["threads"], threads)) { fprintf(stderr, "error: invalid value for --threads\n"); return 2; }
+    if (a.kv.count("device") && !to_u64(a.kv["device"], dev)) { fprintf(stderr, "error: invalid value for --device\n"); return 2; }
+    opt.orders = (uint32_t)orders;
+    opt.side.threads = (int)std::max<uint64_t>(1, threads);
+    opt.side.device = (int)dev;
+    opt.side.file_order = a.flags.count("file-order") != 0;
+    opt.side.hll_bias_sim = a.flags.count("hll-bias-sim") != 0;
+    if (opt.side.hll_bias_sim && a.kv.count("hll-bias")) {
+        fprintf(stderr, "error: --hll-bias-sim cannot be used with --hll-bias (simulate the tables or read them from a file, not both)\n");
+        return 2;
+    }
+    if (a.kv.count("hll-bias")) opt.side.hll_bias_file = a.kv["hll-bias"];
+    else if (const char *e = opt.side.hll_bias_sim ? nullptr : getenv("LASH_HLL_BIAS")) opt.side.hll_bias_file = e;
+    err = layout_from_option(a.kv.count("layout") ? a.kv["layout"] : "", opt.side.layout);
+    if (!err.empty()) { fprintf(stderr, "error: %s\n", err.c_str()); return 2; }
+    err = run_growth(opt);
+    if (!err.empty()) { fprintf(stderr, "Error: %s\n", err.c_str()); return 1; }
+    printf("Growth table written.\n");
+    return 0;
+}
+
 int cmd_hll_bias(int argc, char **argv)
 {
     Args a;
@@ -489,6 +560,7 @@ int main(int argc, char **argv)
     if (cmd == "sketch") { const int rc = cmd_sketch(argc, argv); epoch_mark("main returning"); return rc; }
     if (cmd == "dist") return cmd_dist(argc, argv);
     if (cmd == "hll-bias") return cmd_hll_bias(argc, argv);
+    if (cmd == "growth") return cmd_growth(argc, argv);
     if (cmd == "--version" || cmd == "-V") { printf("Genome Sketching via HyperLogLog, HyperMinhash and UltraLogLog %s\n", VERSION); return 0; }
     usage();
     return cmd == "--help" || cmd == "-h" || cmd == "help" ? 0 : 2;

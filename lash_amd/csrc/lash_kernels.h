@@ -415,6 +415,25 @@ hipError_t launch_gather_rows(const uint8_t *d_src, const uint32_t *d_order, uin
 hipError_t launch_collision_vectors(const double *d_card, uint32_t n, double *d_P, hipStream_t stream);
 hipError_t launch_collision_gemm(const double *d_A, uint32_t m, const double *d_B, uint32_t n, double *d_X, hipStream_t stream);
 
+// ---- prefix unions along orderings (prefix_union.hip) -------------------------------------------------------------
+// hist[(o * len + t) * 256 + b] += bin b of the register histogram (as launch_sketch_hist's) of image[orders[o][0]] U ... U
+// image[orders[o][t]], for the launch's n_orders orders (at most 65 535).  hist must be zero before the launch; every entry of
+// orders must be a valid image index.  The table of n_words 32-bit words is cut into `slices` contiguous runs (1 .. n_words), one
+// workgroup per (slice, order); the sums do not depend on the cut.
+struct PrefixUnionArgs {
+    const uint8_t  *img;       // images: `hdr` header bytes, then the registers; `stride` bytes apart
+    uint64_t        stride;
+    uint32_t        hdr;
+    uint32_t        hmh_be;    // HyperMinHash: the u16 registers are big-endian in the image
+    const uint32_t *orders;    // [n_orders][len]
+    uint32_t        len;
+    uint32_t        n_words;   // register bytes / 4
+    uint32_t        slices;
+    uint32_t       *hist;      // [n_orders][len][256]
+};
+uint32_t   prefix_union_default_slices(uint32_t n_words, uint32_t n_orders, uint32_t cu_count);
+hipError_t launch_prefix_union(const PrefixUnionArgs &args, int algo, uint32_t n_orders, hipStream_t stream);
+
 // ---- synthetic genomes --------------------------------------------------------------------
 hipError_t launch_synth(uint64_t first_genome, uint32_t n_genomes, uint64_t n_bases, uint8_t *d_out, hipStream_t stream);
 

@@ -754,6 +754,27 @@ class SketchSet:
     def prepare(self, qry=None):
         self._ctx._check(self._lib.lash_sketch_set_prepare(self._ctx._h, self._h, (qry or self)._h))
 
+    def prefix_union_cardinalities(self, orders, estimator="fgra", hll_bias=None, slices=0, hist_budget_bytes=0):
+        """`lash growth`: orders = uint32 [n_orders, len] member indices; float64 [n_orders, len] out, entry (o, t) the distinct-count
+        estimate of members orders[o][0..t] united — the bits cardinalities() gives for the image of that union
+        (lash_sketch_set_prefix_union_cardinalities).  slices / hist_budget_bytes: how the work is cut (0 = the library chooses); the
+        numbers do not depend on them.  LASH_ERANGE / LASH_EINVAL raise a LashError whose .index is the refused position o * len + t."""
+        o = np.ascontiguousarray(orders, dtype=np.uint32)
+        assert o.ndim == 2
+        out = np.zeros(o.shape, dtype=np.float64)
+        opts = _lib.PrefixUnionOpts(int(slices), int(hist_budget_bytes))
+        bad = C.c_uint64(2**64 - 1)
+        rc = self._lib.lash_sketch_set_prefix_union_cardinalities(self._ctx._h, self._h, o.ctypes.data if o.size else None, o.shape[0], o.shape[1],
+                                                                  ULL_ESTIMATORS[estimator], _bias_handle(hll_bias), C.byref(opts),
+                                                                  out.ctypes.data if out.size else None, C.byref(bad))
+        if rc != _lib.OK:
+            msg = self._lib.lash_strerror(rc).decode() + (" (order %d, step %d)" % divmod(bad.value, o.shape[1]) if rc == _lib.ERANGE else "")
+            last = self._lib.lash_ctx_last_error(self._ctx._h)
+            e = LashError(rc, msg + (" " + last.decode() if rc == _lib.EINVAL and last else ""))
+            e.index = bad.value
+            raise e
+        return out
+
     def hmh_expected_collisions(self, r0, r1, qry=None, n_cols=None):
         """hyperminhash's expected collisions of the block's SMALL pairs (both sketches <= 2^19 distinct k-mers) as a float64
         [r1 - r0, n_cols] array for lash_dist_rows' hmh_ec (other entries are not read), or None when the block has none.
