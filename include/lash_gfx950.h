@@ -753,6 +753,35 @@ int lash_sketch_set_prefix_union_cardinalities(lash_ctx *ctx, lash_sketch_set *s
 int lash_sketch_set_prefix_union_plan(lash_ctx *ctx, const lash_sketch_set *set, uint32_t n_orders, uint32_t len,
                                       const lash_prefix_union_opts *opts, lash_prefix_union_opts *out_plan);
 
+/* ---- merge: one sketch per group of members of a set (`lash merge`, group_union.hip) ----
+ * The groups are a CSR list: group g holds members[group_off[g] .. group_off[g + 1]), indices into the set; group_off[0] = 0 and the
+ * offsets never decrease.  Groups may overlap, a member may repeat within a group, a group may be empty.  Image g of the output
+ * (n_groups serialized images in the context's layout, back to back) is byte for byte what lash_merge_images leaves when the members
+ * are folded into the image of an empty sketch one after another, header included; an empty group is that empty image.  The fold runs
+ * on the device: a thread owns registers and walks members, a group longer than `segment` members is folded into partial unions in
+ * scratch memory which are folded again (group_union.hip).
+ *   opts (may be NULL; a zero field = the library chooses)
+ *     segment               members per task of the first level; partial unions are folded max(segment, 2) at a time
+ *     slices                workgroups an image's registers are cut over (clamped to the number of 16-byte units)
+ *     scratch_budget_bytes  bound on the partial unions held at once: the groups go in chunks under it, at least one group per chunk
+ *                           (a single group may exceed it) [1 GiB]
+ *   The bytes do not depend on opts: the merge rules are commutative, associative and idempotent.
+ *   LASH_EINVAL  NULL arguments, offsets that do not start at 0 or decrease, a member >= the set's size (*bad_index = its position in
+ *                members), a set made under another layout than the context's
+ *   LASH_ENOMEM  the partial unions of one chunk do not fit the device (lash_ctx_last_error names the groups and the bytes)
+ * The set's own state is left untouched.  The host form is synchronous; _device writes to device memory and is asynchronous on the
+ * context's stream (the lists are copied before it returns).
+ * _plan: what a call with these offsets would run with — segment, slices, and scratch_budget_bytes = the scratch bytes it allocates. */
+typedef struct { uint32_t segment; uint32_t slices; uint64_t scratch_budget_bytes; } lash_group_union_opts;   /* 0 = the library chooses */
+int lash_sketch_set_group_union(lash_ctx *ctx, const lash_sketch_set *set, const uint64_t *group_off, const uint32_t *members,
+                                uint32_t n_groups, const lash_group_union_opts *opts /* may be NULL */,
+                                uint8_t *out_images /* host, n_groups images */, uint64_t *bad_index);
+int lash_sketch_set_group_union_device(lash_ctx *ctx, const lash_sketch_set *set, const uint64_t *group_off, const uint32_t *members,
+                                       uint32_t n_groups, const lash_group_union_opts *opts /* may be NULL */,
+                                       uint8_t *d_out_images /* device, n_groups images */, uint64_t *bad_index);
+int lash_sketch_set_group_union_plan(lash_ctx *ctx, const lash_sketch_set *set, const uint64_t *group_off, uint32_t n_groups,
+                                     const lash_group_union_opts *opts, lash_group_union_opts *out_plan);
+
 /* Synthetic genomes of SURVEY.md §8(d) generated in HBM (bench / tests): genome ids first..first+n-1,
  * n_bases ASCII bytes each, written back to back at d_out. */
 int lash_synth_genomes_device(lash_ctx *ctx, uint64_t first_genome, uint32_t n_genomes, uint64_t n_bases, uint8_t *d_out);

@@ -68,6 +68,11 @@ class PrefixUnionOpts(C.Structure):
     _fields_ = [("slices", C.c_uint32), ("hist_budget_bytes", C.c_uint64)]
 
 
+class GroupUnionOpts(C.Structure):
+    """lash_group_union_opts: how lash_sketch_set_group_union cuts its work (0 = the library chooses)"""
+    _fields_ = [("segment", C.c_uint32), ("slices", C.c_uint32), ("scratch_budget_bytes", C.c_uint64)]
+
+
 LINKAGE_AVERAGE, LINKAGE_SINGLE, LINKAGE_COMPLETE = 0, 1, 2
 
 _vp, _u64, _u32, _int = C.c_void_p, C.c_uint64, C.c_uint32, C.c_int
@@ -208,6 +213,9 @@ PROTOTYPES = {
     "lash_tree_free": (None, [_vp, _vp]),
     "lash_sketch_set_prefix_union_cardinalities": (_int, [_vp, _vp, _vp, _u32, _u32, _int, _vp, C.POINTER(PrefixUnionOpts), _vp, C.POINTER(_u64)]),
     "lash_sketch_set_prefix_union_plan": (_int, [_vp, _vp, _u32, _u32, C.POINTER(PrefixUnionOpts), C.POINTER(PrefixUnionOpts)]),
+    "lash_sketch_set_group_union": (_int, [_vp, _vp, _vp, _vp, _u32, C.POINTER(GroupUnionOpts), _vp, C.POINTER(_u64)]),
+    "lash_sketch_set_group_union_device": (_int, [_vp, _vp, _vp, _vp, _u32, C.POINTER(GroupUnionOpts), _vp, C.POINTER(_u64)]),
+    "lash_sketch_set_group_union_plan": (_int, [_vp, _vp, _vp, _u32, C.POINTER(GroupUnionOpts), C.POINTER(GroupUnionOpts)]),
     "lash_synth_genomes_device": (_int, [_vp, _u64, _u32, _u64, _vp]),
 }
 

@@ -788,6 +788,8 @@ std::string load_dist_side(const DistOptions &opt, DistSide &out)
     out.names = std::move(in.rnames);
     out.order = std::move(in.rorder);
     out.images = std::move(in.rimg_store);
+    std::map<std::string, std::string> found;
+    if (find_files(opt.ref_prefix, found).empty()) out.params_file = found["params"];
     return "";
 }
 

@@ -57,6 +57,7 @@ struct DistSide {
     std::vector<std::string> names;      // the name file
     std::vector<uint32_t> order;         // the rows, as indices into names: the reference's key order, or list order under file_order
     std::vector<uint8_t> images;         // the sketch file, inflated: one image per name
+    std::string params_file;             // the collection's parameters JSON, as found (merge.cpp copies it)
 };
 std::string load_dist_side(const DistOptions &opt, DistSide &out);
 // The HLL++ tables of a run, as `dist` gets them (--hll-bias FILE / --hll-bias-sim on opt.device): *out stays NULL for hmh / ull sketches

@@ -16,6 +16,7 @@
 #include "fastx.hpp"
 #include "inflate_fast.hpp"
 #include "json_out.hpp"
+#include "merge.hpp"
 #include "name_order.hpp"
 #include "pgzip.hpp"
 #include "sketch_files.hpp"
@@ -220,6 +221,32 @@ char *lash_host_read_list(const char *path, uint64_t *n)
     for (auto &f : files) { j += f; j += '\n'; }
     *n = files.size();
     return dup_str(j);
+}
+
+// merge.hpp: a groups file's text against '\n'-separated names.  Returns NULL, the group names '\n'-joined in *group_names and the CSR
+// list in *off ([*n_groups + 1]) and *members (all malloc'd); else the refusal (malloc'd).
+char *lash_host_parse_groups(const char *text, uint64_t text_bytes, const char *names_nl, uint64_t n_names, char **group_names, uint64_t *n_groups,
+                             uint64_t **off, uint32_t **members)
+{
+    std::vector<std::string> names;
+    const char *p = names_nl;
+    for (uint64_t i = 0; i < n_names; ++i) {
+        const char *e = strchr(p, '\n');
+        names.emplace_back(p, e ? (size_t)(e - p) : strlen(p));
+        p = e ? e + 1 : p + strlen(p);
+    }
+    GroupList gl;
+    const std::string err = parse_groups(std::string(text, (size_t)text_bytes), names, gl);
+    if (!err.empty()) return dup_str(err);
+    std::string j;
+    for (auto &g : gl.names) { j += g; j += '\n'; }
+    *group_names = dup_str(j);
+    *n_groups = gl.names.size();
+    *off = (uint64_t *)malloc(gl.off.size() * 8);
+    memcpy(*off, gl.off.data(), gl.off.size() * 8);
+    *members = (uint32_t *)malloc((gl.members.size() + 1) * 4);
+    if (!gl.members.empty()) memcpy(*members, gl.members.data(), gl.members.size() * 4);
+    return nullptr;
 }
 
 char *lash_host_zstd_write(const char *path, const uint8_t *data, uint64_t n, int level, int workers)

@@ -3,6 +3,7 @@
 //   lash sketch -f LIST [-o sketch] [-k 16] [-t N] [-a hmh|hll|ull] [-p 10] [-s 42]        (main.rs:30-96, 180-279)
 //   lash dist   -q PREFIX -r PREFIX [-o dist] [-t N] [-e fgra|ml] [-m 1|0] [--fp32] [--dm]   (main.rs:107-176, 280-617)
 //   lash growth -r PREFIX [-o growth] [--orders P] [--seed S] [--file-order] [-e fgra|ml] [-t N]   (not upstream: union cardinality along orderings)
+//   lash merge  -r PREFIX -o OUT (--groups FILE | --all NAME) [--keep-others] [--file-order] [-t N]   (not upstream: one sketch per group of sketches)
 //   lash hll-bias -o FILE [-p P[,P...]] [--points N] [--trials T] [--seed S] [--device D]    (not upstream: HLL++ bias tables, simulated)
 // Extras that do not exist upstream: --gpus N / --device D / --devices LIST (which GPUs to use, one worker each), --batch-mb M, --stream-mb M (files
 // larger than M MiB are streamed in chunks with on-device accumulation), --hmh-x-low, --min-count M [--count-cells-log2 L] (drop the k-mers a
@@ -28,6 +29,7 @@
 #include "../../../include/lash_gfx950.h"
 #include "dist.hpp"
 #include "growth.hpp"
+#include "merge.hpp"
 #include "sketch_files.hpp"
 
 using namespace lashhost;
@@ -49,6 +51,7 @@ void usage()
             "  sketch  Sketches genomes and serializes them, sketches are compressed\n"
             "  dist    Computes distance between sketches\n"
             "  growth  Union cardinality of a collection along orderings: how much each further genome adds\n"
+            "  merge   One sketch per group of a collection's sketches (clusters, the files of a sample), united on the GPU\n"
             "  hll-bias  Simulates the HLL++ bias tables on the GPU and writes the file dist --hll-bias reads\n\n"
             "sketch options:\n"
             "  -f, --file <file>            One file containing list of FASTA/FASTQ files (.gz/.zstd supported), one per line\n"
@@ -129,6 +132,20 @@ void usage()
             "  -e, --estimator <fgra|ml>  -t, --threads <n> (formatting only; the bytes do not depend on it)  --device <D>\n"
             "      --hll-bias <file> | --hll-bias-sim   as for dist: without tables an hll union with an estimate <= 5 * 2^p is refused\n"
             "                               All orders are folded on the GPU in one pass per chunk of orders; hmh, hll, and ull up to -p 16\n"
+            "merge options:\n"
+            "  -r, --reference <prefix>     The collection, read as dist reads a side\n"
+            "  -o, --output <prefix>        Where the merged collection goes: {prefix}_sketches.bin, _files.json (the group names) and\n"
+            "                               _parameters.json (the input's, copied): dist, growth and merge read it like any other\n"
+            "      --groups <file>          Lines of group<TAB>member, a member being a name of the collection: what dist --cluster and\n"
+            "                               --derep write, heading line included.  One sketch per group, the union of its members, in order\n"
+            "                               of first appearance.  A member may be in several groups; a name several sketches carry selects\n"
+            "                               all of them.  Blank lines are skipped; a line without exactly one tab, an empty name or an\n"
+            "                               unknown member is refused with its line number\n"
+            "      --all <name>             One group of every sketch instead, called <name>; not with --groups or --keep-others\n"
+            "      --keep-others            Sketches in no group follow the groups under their own names, in row order (the reference's\n"
+            "                               key order, where a repeated name is one row; list order with --file-order) [default: dropped,\n"
+            "                               and counted on stderr]\n"
+            "      --file-order  --device <D>  -t, --threads <n> (compression only; the bytes of the sketches do not depend on it)\n"
             "hll-bias options:\n"
             "  -o, --output <file>          Where the tables go (text: \"p <p> <n>\" then n lines \"<raw estimate> <bias>\")\n"
             "  -p, --precision <p[,p...]>   Precisions to simulate, each 4-18 [default: 4,5,...,18]\n"
@@ -493,6 +510,50 @@ int cmd_growth(int argc, char **argv)
     return 0;
 }
 
+// lash merge -r PREFIX -o OUT (--groups FILE | --all NAME) [--keep-others] [--file-order] [--device D] [--layout SPEC] [-t N]
+int cmd_merge(int argc, char **argv)
+{
+    Args a;
+    std::string err;
+    const std::map<std::string, std::string> alias = {{"r", "reference"}, {"o", "output"}, {"t", "threads"}};
+    const std::vector<std::string> known = {"reference", "output", "threads", "groups", "all", "keep-others", "file-order", "device", "layout", "help"};
+    for (int i = 2; i < argc; ++i) {
+        const std::string s = argv[i];
+        if (s.rfind("--", 0) != 0) continue;
+        const std::string key = s.substr(2, s.find('=') == std::string::npos ? std::string::npos : s.find('=') - 2);
+        if (std::find(known.begin(), known.end(), key) == known.end()) { fprintf(stderr, "error: unexpected argument '--%s'\n", key.c_str()); return 2; }
+    }
+    if (!parse(argc, argv, 2, alias, {"keep-others", "file-order", "help"}, a, err)) { fprintf(stderr, "error: %s\n", err.c_str()); return 2; }
+    if (a.flags.count("help")) { usage(); return 0; }
+    if (!a.kv.count("reference") || !a.kv.count("output")) {
+        fprintf(stderr, "error: the following required arguments were not provided:\n%s%s", a.kv.count("reference") ? "" : "  --reference <prefix>\n",
+                a.kv.count("output") ? "" : "  --output <prefix>\n");
+        return 2;
+    }
+    if (a.kv.count("groups") && a.kv.count("all")) { fprintf(stderr, "error: --groups cannot be used with --all (a list of groups or one group of everything, not both)\n"); return 2; }
+    if (!a.kv.count("groups") && !a.kv.count("all")) { fprintf(stderr, "error: one of --groups <file> and --all <name> is required\n"); return 2; }
+    if (a.kv.count("all") && a.flags.count("keep-others")) { fprintf(stderr, "error: --keep-others cannot be used with --all (--all leaves no others)\n"); return 2; }
+    if (a.kv.count("all") && a.kv["all"].empty()) { fprintf(stderr, "error: invalid value '' for --all: a name is required\n"); return 2; }
+    MergeOptions opt;
+    opt.side.ref_prefix = opt.side.query_prefix = a.kv["reference"];
+    opt.output = a.kv["output"];
+    if (a.kv.count("groups")) opt.groups_file = a.kv["groups"];
+    if (a.kv.count("all")) opt.all_name = a.kv["all"];
+    opt.keep_others = a.flags.count("keep-others") != 0;
+    opt.side.file_order = a.flags.count("file-order") != 0;
+    uint64_t threads = std::thread::hardware_concurrency(), dev = 0;
+    if (a.kv.count("threads") && !to_u64(a.kv["threads"], threads)) { fprintf(stderr, "error: invalid value for --threads\n"); return 2; }
+    if (a.kv.count("device") && !to_u64(a.kv["device"], dev)) { fprintf(stderr, "error: invalid value for --device\n"); return 2; }
+    opt.side.threads = (int)std::max<uint64_t>(1, threads);
+    opt.side.device = (int)dev;
+    err = layout_from_option(a.kv.count("layout") ? a.kv["layout"] : "", opt.side.layout);
+    if (!err.empty()) { fprintf(stderr, "error: %s\n", err.c_str()); return 2; }
+    err = run_merge(opt);
+    if (!err.empty()) { fprintf(stderr, "Error: %s\n", err.c_str()); return 1; }
+    printf("Merged sketches written.\n");
+    return 0;
+}
+
 int cmd_hll_bias(int argc, char **argv)
 {
     Args a;
@@ -561,6 +622,7 @@ int main(int argc, char **argv)
     if (cmd == "dist") return cmd_dist(argc, argv);
     if (cmd == "hll-bias") return cmd_hll_bias(argc, argv);
     if (cmd == "growth") return cmd_growth(argc, argv);
+    if (cmd == "merge") return cmd_merge(argc, argv);
     if (cmd == "--version" || cmd == "-V") { printf("Genome Sketching via HyperLogLog, HyperMinhash and UltraLogLog %s\n", VERSION); return 0; }
     usage();
     return cmd == "--help" || cmd == "-h" || cmd == "help" ? 0 : 2;

@@ -204,6 +204,8 @@ struct lash_ctx {
     DevBuf ec_ref, ec_qry, ec_x, ec_card;   // lash_set_ec_block: cell vectors [n][65536] f64, products, cardinalities
     DevBuf wf_scratch, wf_out;           // lash_sketch_set_pair_block_within: [offsets | masks | tile counts], the compacted candidates
     DevBuf top_buf;                      // lash_sketch_set_pair_block_top: [cutoff keys | interval keys | same_col] (dist_top.hip)
+    DevBuf gu_members, gu_tasks, gu_part, gu_hist, gu_out;   // lash_sketch_set_group_union: the member list, a chunk's tasks, its partials (two
+                                         // halves in turn), its HyperLogLog histograms; gu_out: the images of the host-buffer entry
     DevBuf hll_flags;                    // [hll_flags_n] per genome of the last HyperLogLog sketch call: a register > 53 - p
     uint32_t hll_flags_n = 0;            // (lash_ctx_hll_inexact_sums)
     bool hll_flags_on_host = false;      // the list below stands for the flags (hll_replay_sums has dealt with the others)

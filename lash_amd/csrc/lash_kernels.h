@@ -434,6 +434,40 @@ struct PrefixUnionArgs {
 uint32_t   prefix_union_default_slices(uint32_t n_words, uint32_t n_orders, uint32_t cu_count);
 hipError_t launch_prefix_union(const PrefixUnionArgs &args, int algo, uint32_t n_orders, hipStream_t stream);
 
+// ---- unions of groups of images (group_union.hip) -----------------------------------------------------------------
+// One level of the fold of `lash merge`: task t unites `count` sources into one destination.  Sources are register tables `src_stride`
+// bytes apart, `src_hdr` bytes into each: at the first level the set's images, picked by members[src_begin + j]; above it
+// (members == NULL) the partials src_begin + j the level below left.  A destination is a partial (dst = its slot in `part`: bare
+// tables of 4 * n_words bytes in register order) or, with GU_FINAL set, image dst & ~GU_FINAL of `out`: registers in the image's
+// byte order behind a header; HyperLogLog headers wait for launch_group_union_headers, which reads the histograms the final tasks
+// add into hist[image][72] (zero before the first level).  A count of 0 writes the empty table.  An image is cut into `slices`
+// runs of whole units (4 words; 1 word for the two-word table), a run goes to `lanes` threads (a power of two <= 256) and a
+// workgroup takes 256 / lanes tasks: the bytes written do not depend on slices or lanes.
+constexpr uint32_t GU_FINAL = 0x80000000u;
+struct GroupTask { uint64_t src_begin; uint32_t count; uint32_t dst; };
+struct GroupUnionArgs {
+    const uint8_t   *src;
+    uint64_t         src_stride;
+    uint32_t         src_hdr;
+    uint32_t         src_be;     // HyperMinHash: the sources hold big-endian u16 registers (images of such a layout)
+    const uint32_t  *members;
+    const GroupTask *tasks;
+    uint32_t         n_tasks;
+    uint32_t         n_words;    // register bytes / 4
+    uint32_t         slices, lanes;
+    uint8_t         *part;
+    uint8_t         *out;
+    uint64_t         out_stride;
+    uint32_t         hdr;        // header bytes of an output image
+    uint32_t         out_be;
+    uint32_t        *hist;
+    uint64_t         hdr_tpl, alpha_bits;
+    int              p;
+};
+uint32_t   group_union_unit_words(uint32_t n_words);
+hipError_t launch_group_union(const GroupUnionArgs &args, int algo, hipStream_t stream);
+hipError_t launch_group_union_headers(const GroupUnionArgs &args, uint32_t n_images, hipStream_t stream);   // HyperLogLog only
+
 // ---- synthetic genomes --------------------------------------------------------------------
 hipError_t launch_synth(uint64_t first_genome, uint32_t n_genomes, uint64_t n_bases, uint8_t *d_out, hipStream_t stream);
 

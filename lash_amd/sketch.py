@@ -775,6 +775,50 @@ class SketchSet:
             raise e
         return out
 
+    def _groups_csr(self, groups):
+        if isinstance(groups, np.ndarray) and groups.ndim == 2:              # equal-sized groups as a matrix
+            return np.arange(groups.shape[0] + 1, dtype=np.uint64) * np.uint64(groups.shape[1]), np.ascontiguousarray(groups, dtype=np.uint32).reshape(-1)
+        off = np.zeros(len(groups) + 1, dtype=np.uint64)
+        off[1:] = np.cumsum([len(g) for g in groups], dtype=np.uint64)
+        mem = np.ascontiguousarray([m for g in groups for m in g], dtype=np.uint32)
+        return off, mem
+
+    def group_union(self, groups, segment=None, slices=None, scratch_budget=None, device_out=None):
+        """`lash merge`: groups = a list of lists of member indices (overlaps, repeats and empty groups are fine); one image per group, the
+        union of its members — byte for byte the fold of merge_images over them from the empty sketch (lash_sketch_set_group_union).
+        Returns uint8 [n_groups, image_bytes]; with device_out (a CUDA uint8 tensor of that many bytes) the images are written there,
+        asynchronously on the context's stream, and device_out is returned.  segment / slices / scratch_budget: how the work is cut
+        (None = the library chooses); the bytes do not depend on them.  LASH_EINVAL for a bad member raises a LashError whose .index
+        is its position in the flattened list."""
+        off, mem = self._groups_csr(groups)
+        opts = _lib.GroupUnionOpts(int(segment or 0), int(slices or 0), int(scratch_budget or 0))
+        bad = C.c_uint64(2**64 - 1)
+        ib = self._ctx.image_bytes(self.algo, self.p)
+        mp = mem.ctypes.data if mem.size else None
+        if device_out is None:
+            out = np.zeros((len(groups), ib), dtype=np.uint8)
+            rc = self._lib.lash_sketch_set_group_union(self._ctx._h, self._h, off.ctypes.data, mp, len(groups), C.byref(opts),
+                                                       out.ctypes.data if out.size else None, C.byref(bad))
+        else:
+            assert device_out.is_cuda and device_out.is_contiguous() and device_out.numel() * device_out.element_size() >= len(groups) * ib
+            out = device_out
+            rc = self._lib.lash_sketch_set_group_union_device(self._ctx._h, self._h, off.ctypes.data, mp, len(groups), C.byref(opts),
+                                                              device_out.data_ptr() if len(groups) else None, C.byref(bad))
+        if rc != _lib.OK:
+            last = self._lib.lash_ctx_last_error(self._ctx._h)
+            e = LashError(rc, self._lib.lash_strerror(rc).decode() + (" " + last.decode() if last else ""))
+            e.index = bad.value
+            raise e
+        return out
+
+    def group_union_plan(self, groups, segment=None, slices=None, scratch_budget=None):
+        """(segment, slices, scratch bytes) a group_union call with these arguments runs with (lash_sketch_set_group_union_plan)"""
+        off, _ = self._groups_csr(groups)
+        opts = _lib.GroupUnionOpts(int(segment or 0), int(slices or 0), int(scratch_budget or 0))
+        plan = _lib.GroupUnionOpts()
+        self._ctx._check(self._lib.lash_sketch_set_group_union_plan(self._ctx._h, self._h, off.ctypes.data, len(groups), C.byref(opts), C.byref(plan)))
+        return int(plan.segment), int(plan.slices), int(plan.scratch_budget_bytes)
+
     def hmh_expected_collisions(self, r0, r1, qry=None, n_cols=None):
         """hyperminhash's expected collisions of the block's SMALL pairs (both sketches <= 2^19 distinct k-mers) as a float64
         [r1 - r0, n_cols] array for lash_dist_rows' hmh_ec (other entries are not read), or None when the block has none.
