@@ -782,6 +782,37 @@ int lash_sketch_set_group_union_device(lash_ctx *ctx, const lash_sketch_set *set
 int lash_sketch_set_group_union_plan(lash_ctx *ctx, const lash_sketch_set *set, const uint64_t *group_off, uint32_t n_groups,
                                      const lash_group_union_opts *opts, lash_group_union_opts *out_plan);
 
+/* ---- spectrum: how the union's k-mers are shared inside a group (`lash spectrum`, group_spectrum.hip) ----
+ * HyperMinHash sets only.  The groups are the CSR list of lash_sketch_set_group_union above (overlaps, repeats and empty groups are
+ * legal; a member listed twice counts twice).  With r[j][b] the 16 384 16-bit registers of member j's image, for a group G of n members:
+ *   U_b = max over j in G of r[j][b]                       the union's register: one k-mer of the union, drawn uniformly from the
+ *                                                          bucket's distinct k-mers
+ *   c_b = #{ j in G : r[j][b] == U_b } if U_b != 0, else 0  the members that hold that k-mer
+ *   hist[c] = #{ b : c_b == c }, c = 0 .. n                 hist[0] = the empty buckets; the bins sum to 16 384
+ * so hist[1 .. n] over the occupied buckets is a uniform sample, of up to 16 384 k-mers, of the group's multiplicity spectrum: the
+ * distinct k-mers held by exactly c members are about hist[c] / (16384 - hist[0]) x the union's cardinality.  For a group of two,
+ * hist[2] and 16384 - hist[0] are the C and N of lash_hmh_pair_counts.  All of it is exact integer work.
+ *   out_hist          uint32 bins, CSR: group g's n_g + 1 bins at out_hist[group_off[g] + g .. group_off[g + 1] + g], group_off[n_groups]
+ *                     + n_groups in all
+ *   out_union_images  may be NULL; else n_groups images, byte for byte lash_sketch_set_group_union's (the fold runs anyway: the counts
+ *                     are taken against it, and the union's cardinality is what scales the bins)
+ *   opts              as for lash_sketch_set_group_union, and lash_sketch_set_group_union_plan answers for segment and slices;
+ *                     scratch_budget_bytes bounds the union's partials together with the count tables (64 KiB for each group longer
+ *                     than min(segment, 65 535) members) of a chunk of groups, at least one group per chunk
+ *   The bins do not depend on opts: they are sums of integers.
+ *   LASH_EINVAL  what lash_sketch_set_group_union refuses (*bad_index = the position in members of a member >= the set's size), and a
+ *                set that is not HyperMinHash: an hll or ull register does not identify a k-mer (lash_ctx_last_error says so)
+ *   LASH_ENOMEM  the scratch of one chunk does not fit the device
+ * The set's own state is left untouched.  The host form is synchronous; _device writes to device memory and is asynchronous on the
+ * context's stream (the lists are copied before it returns). */
+int lash_sketch_set_group_spectrum(lash_ctx *ctx, const lash_sketch_set *set, const uint64_t *group_off, const uint32_t *members,
+                                   uint32_t n_groups, const lash_group_union_opts *opts /* may be NULL */,
+                                   uint32_t *out_hist /* host */, uint8_t *out_union_images /* host, may be NULL */, uint64_t *bad_index);
+int lash_sketch_set_group_spectrum_device(lash_ctx *ctx, const lash_sketch_set *set, const uint64_t *group_off, const uint32_t *members,
+                                          uint32_t n_groups, const lash_group_union_opts *opts /* may be NULL */,
+                                          uint32_t *d_out_hist /* device */, uint8_t *d_out_union_images /* device, may be NULL */,
+                                          uint64_t *bad_index);
+
 /* Synthetic genomes of SURVEY.md §8(d) generated in HBM (bench / tests): genome ids first..first+n-1,
  * n_bases ASCII bytes each, written back to back at d_out. */
 int lash_synth_genomes_device(lash_ctx *ctx, uint64_t first_genome, uint32_t n_genomes, uint64_t n_bases, uint8_t *d_out);

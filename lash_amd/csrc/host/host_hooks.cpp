@@ -20,6 +20,7 @@
 #include "name_order.hpp"
 #include "pgzip.hpp"
 #include "sketch_files.hpp"
+#include "spectrum.hpp"
 #include "zstd_dl.hpp"
 
 using namespace lashhost;
@@ -341,6 +342,19 @@ int64_t lash_host_formatter_block(lash_host_formatter *f, int algo, int p, int k
                              f->col_card.data(), t, f->row_names, f->col_names, f->col_tab, f->row_id.data(), f->col_id.data(), matrix != 0, threads, text);
     if (!f->err.empty()) return -1;
     return write_text(f, fd);
+}
+
+// spectrum.cpp's derived numbers of one group: out_classes = {core, shell, cloud}; out_pan / out_core [n] (either may be NULL: no curves)
+void lash_host_spectrum_numbers(const uint32_t *hist, uint32_t n, double U, double core, double cloud, double *out_classes, double *out_pan,
+                                double *out_core)
+{
+    const SpectrumClasses k = spectrum_classes(hist, n, U, core, cloud);
+    out_classes[0] = k.core; out_classes[1] = k.shell; out_classes[2] = k.cloud;
+    if (!out_pan || !out_core) return;
+    std::vector<double> pan, in_all;
+    spectrum_curves(hist, n, U, pan, in_all);
+    std::copy(pan.begin(), pan.end(), out_pan);
+    std::copy(in_all.begin(), in_all.end(), out_core);
 }
 
 }  // extern "C"

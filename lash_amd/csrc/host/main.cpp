@@ -4,6 +4,7 @@
 //   lash dist   -q PREFIX -r PREFIX [-o dist] [-t N] [-e fgra|ml] [-m 1|0] [--fp32] [--dm]   (main.rs:107-176, 280-617)
 //   lash growth -r PREFIX [-o growth] [--orders P] [--seed S] [--file-order] [-e fgra|ml] [-t N]   (not upstream: union cardinality along orderings)
 //   lash merge  -r PREFIX -o OUT (--groups FILE | --all NAME) [--keep-others] [--file-order] [-t N]   (not upstream: one sketch per group of sketches)
+//   lash spectrum -r PREFIX -o OUT [--groups FILE | --all NAME] [--core F] [--cloud F] [--curves] [--file-order] [-t N]   (not upstream: k-mer sharing spectrum of groups, hmh)
 //   lash hll-bias -o FILE [-p P[,P...]] [--points N] [--trials T] [--seed S] [--device D]    (not upstream: HLL++ bias tables, simulated)
 // Extras that do not exist upstream: --gpus N / --device D / --devices LIST (which GPUs to use, one worker each), --batch-mb M, --stream-mb M (files
 // larger than M MiB are streamed in chunks with on-device accumulation), --hmh-x-low, --min-count M [--count-cells-log2 L] (drop the k-mers a
@@ -31,6 +32,7 @@
 #include "growth.hpp"
 #include "merge.hpp"
 #include "sketch_files.hpp"
+#include "spectrum.hpp"
 
 using namespace lashhost;
 
@@ -52,6 +54,7 @@ void usage()
             "  dist    Computes distance between sketches\n"
             "  growth  Union cardinality of a collection along orderings: how much each further genome adds\n"
             "  merge   One sketch per group of a collection's sketches (clusters, the files of a sample), united on the GPU\n"
+            "  spectrum  How the k-mers of each group's union are shared among its members: core, shell and cloud (hmh sketches)\n"
             "  hll-bias  Simulates the HLL++ bias tables on the GPU and writes the file dist --hll-bias reads\n\n"
             "sketch options:\n"
             "  -f, --file <file>            One file containing list of FASTA/FASTQ files (.gz/.zstd supported), one per line\n"
@@ -146,6 +149,22 @@ void usage()
             "                               key order, where a repeated name is one row; list order with --file-order) [default: dropped,\n"
             "                               and counted on stderr]\n"
             "      --file-order  --device <D>  -t, --threads <n> (compression only; the bytes of the sketches do not depend on it)\n"
+            "spectrum options:\n"
+            "  -r, --reference <prefix>     The collection, read as dist reads a side; HyperMinHash sketches only (an hll or ull register\n"
+            "                               does not identify a k-mer: such a collection is refused)\n"
+            "  -o, --output <prefix>        Where the tables go.  {prefix}_spectrum.tsv: Group<TAB>Members<TAB>Count<TAB>Buckets<TAB>Kmers, one line per\n"
+            "                               group and count c >= 1 that has buckets: Buckets of the occupied buckets hold a k-mer that exactly c\n"
+            "                               members have, Kmers = Buckets / occupied x the union's distinct k-mers.  {prefix}_groups.tsv:\n"
+            "                               Group<TAB>Members<TAB>Occupied<TAB>Union<TAB>Core<TAB>Shell<TAB>Cloud, one line per group; floats with three decimals\n"
+            "      --groups <file>          Lines of group<TAB>member as for merge (what dist --cluster and --derep write).  A sketch counts once\n"
+            "                               per group however often its name is listed; two sketches that carry one name count as two\n"
+            "      --all <name>             One group of every sketch, called <name> [the default, called all]; not with --groups\n"
+            "      --core <F>               A count c of a group of n members is core iff c >= F x n [default: 0.95] ...\n"
+            "      --cloud <F>              ... cloud iff c < F x n [default: 0.15], else shell.  Both in (0, 1], cloud <= core\n"
+            "      --curves                 Also {prefix}_curves.tsv: Group<TAB>Genomes<TAB>Pan<TAB>Core, one line per group and m = 1 .. n: the expected\n"
+            "                               distinct k-mers of the union (Pan) and of the intersection (Core) of m members, exactly, over all\n"
+            "                               subsets of m members (growth --orders P samples orderings instead)\n"
+            "      --file-order  --device <D>  --layout <SPEC>  -t, --threads <n> (accepted as for merge; the tables do not depend on them)\n"
             "hll-bias options:\n"
             "  -o, --output <file>          Where the tables go (text: \"p <p> <n>\" then n lines \"<raw estimate> <bias>\")\n"
             "  -p, --precision <p[,p...]>   Precisions to simulate, each 4-18 [default: 4,5,...,18]\n"
@@ -554,6 +573,58 @@ int cmd_merge(int argc, char **argv)
     return 0;
 }
 
+// lash spectrum -r PREFIX -o OUT [--groups FILE | --all NAME] [--core F] [--cloud F] [--curves] [--file-order] [--device D] [--layout SPEC] [-t N]
+int cmd_spectrum(int argc, char **argv)
+{
+    Args a;
+    std::string err;
+    const std::map<std::string, std::string> alias = {{"r", "reference"}, {"o", "output"}, {"t", "threads"}};
+    const std::vector<std::string> known = {"reference", "output", "threads", "groups", "all", "core", "cloud", "curves", "file-order", "device", "layout", "help"};
+    for (int i = 2; i < argc; ++i) {
+        const std::string s = argv[i];
+        if (s.rfind("--", 0) != 0) continue;
+        const std::string key = s.substr(2, s.find('=') == std::string::npos ? std::string::npos : s.find('=') - 2);
+        if (std::find(known.begin(), known.end(), key) == known.end()) { fprintf(stderr, "error: unexpected argument '--%s'\n", key.c_str()); return 2; }
+    }
+    if (!parse(argc, argv, 2, alias, {"curves", "file-order", "help"}, a, err)) { fprintf(stderr, "error: %s\n", err.c_str()); return 2; }
+    if (a.flags.count("help")) { usage(); return 0; }
+    if (!a.kv.count("reference") || !a.kv.count("output")) {
+        fprintf(stderr, "error: the following required arguments were not provided:\n%s%s", a.kv.count("reference") ? "" : "  --reference <prefix>\n",
+                a.kv.count("output") ? "" : "  --output <prefix>\n");
+        return 2;
+    }
+    if (a.kv.count("groups") && a.kv.count("all")) { fprintf(stderr, "error: --groups cannot be used with --all (a list of groups or one group of everything, not both)\n"); return 2; }
+    if (a.kv.count("all") && a.kv["all"].empty()) { fprintf(stderr, "error: invalid value '' for --all: a name is required\n"); return 2; }
+    SpectrumOptions opt;
+    for (const char *key : {"core", "cloud"}) {
+        if (!a.kv.count(key)) continue;
+        const std::string &v = a.kv[key];
+        char *e = nullptr;
+        const double f = v.empty() ? NAN : strtod(v.c_str(), &e);
+        if (!e || *e != 0 || !(f > 0.0 && f <= 1.0)) { fprintf(stderr, "error: invalid value '%s' for --%s: a number in (0, 1] is required\n", v.c_str(), key); return 2; }
+        (std::string(key) == "core" ? opt.core : opt.cloud) = f;
+    }
+    err = check_fractions(opt.core, opt.cloud);
+    if (!err.empty()) { fprintf(stderr, "error: %s (--core %g, --cloud %g)\n", err.c_str(), opt.core, opt.cloud); return 2; }
+    opt.side.ref_prefix = opt.side.query_prefix = a.kv["reference"];
+    opt.output = a.kv["output"];
+    if (a.kv.count("groups")) opt.groups_file = a.kv["groups"];
+    if (a.kv.count("all")) opt.all_name = a.kv["all"];
+    opt.curves = a.flags.count("curves") != 0;
+    opt.side.file_order = a.flags.count("file-order") != 0;
+    uint64_t threads = std::thread::hardware_concurrency(), dev = 0;
+    if (a.kv.count("threads") && !to_u64(a.kv["threads"], threads)) { fprintf(stderr, "error: invalid value for --threads\n"); return 2; }
+    if (a.kv.count("device") && !to_u64(a.kv["device"], dev)) { fprintf(stderr, "error: invalid value for --device\n"); return 2; }
+    opt.side.threads = (int)std::max<uint64_t>(1, threads);
+    opt.side.device = (int)dev;
+    err = layout_from_option(a.kv.count("layout") ? a.kv["layout"] : "", opt.side.layout);
+    if (!err.empty()) { fprintf(stderr, "error: %s\n", err.c_str()); return 2; }
+    err = run_spectrum(opt);
+    if (!err.empty()) { fprintf(stderr, "Error: %s\n", err.c_str()); return 1; }
+    printf("Spectrum tables written.\n");
+    return 0;
+}
+
 int cmd_hll_bias(int argc, char **argv)
 {
     Args a;
@@ -623,6 +694,7 @@ int main(int argc, char **argv)
     if (cmd == "hll-bias") return cmd_hll_bias(argc, argv);
     if (cmd == "growth") return cmd_growth(argc, argv);
     if (cmd == "merge") return cmd_merge(argc, argv);
+    if (cmd == "spectrum") return cmd_spectrum(argc, argv);
     if (cmd == "--version" || cmd == "-V") { printf("Genome Sketching via HyperLogLog, HyperMinhash and UltraLogLog %s\n", VERSION); return 0; }
     usage();
     return cmd == "--help" || cmd == "-h" || cmd == "help" ? 0 : 2;

@@ -206,6 +206,9 @@ struct lash_ctx {
     DevBuf top_buf;                      // lash_sketch_set_pair_block_top: [cutoff keys | interval keys | same_col] (dist_top.hip)
     DevBuf gu_members, gu_tasks, gu_part, gu_hist, gu_out;   // lash_sketch_set_group_union: the member list, a chunk's tasks, its partials (two
                                          // halves in turn), its HyperLogLog histograms; gu_out: the images of the host-buffer entry
+    DevBuf gs_members, gs_tasks, gs_counts, gs_union, gs_hist;   // lash_sketch_set_group_spectrum: the member list, a chunk's [tasks | bins of its
+                                         // count tables], its count tables; gs_union: the union images when the caller takes none (and the
+                                         // host-buffer entry's); gs_hist: the bins of the host-buffer entry
     DevBuf hll_flags;                    // [hll_flags_n] per genome of the last HyperLogLog sketch call: a register > 53 - p
     uint32_t hll_flags_n = 0;            // (lash_ctx_hll_inexact_sums)
     bool hll_flags_on_host = false;      // the list below stands for the flags (hll_replay_sums has dealt with the others)

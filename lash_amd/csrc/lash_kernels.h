@@ -468,6 +468,34 @@ uint32_t   group_union_unit_words(uint32_t n_words);
 hipError_t launch_group_union(const GroupUnionArgs &args, int algo, hipStream_t stream);
 hipError_t launch_group_union_headers(const GroupUnionArgs &args, uint32_t n_images, hipStream_t stream);   // HyperLogLog only
 
+// ---- k-mer sharing spectra of groups of HyperMinHash images (group_spectrum.hip) -----------------------------------
+// Task t walks members[src_begin .. src_begin + count) of group `group` (count <= GS_SEGMENT_MAX: the walk counts in 16-bit fields)
+// against that group's finished union image uni + group * uni_stride and counts, per register, the members whose register equals the
+// union's and is not 0.  A group's only task (table == GS_NO_TABLE) adds its counts straight into the group's bins hist[hist_begin + c];
+// a task of a group cut into several adds them into the group's count table counts[table][16384] (zero before the launch), which
+// launch_group_spectrum_finish turns into bins: table t belongs to the bins at table_hist[t].  hist is zero before the first launch.
+// slices / lanes cut an image's 2048 units of eight registers as GroupUnionArgs' do; the bins do not depend on them: integer sums.
+constexpr uint32_t GS_NO_TABLE = 0xFFFFFFFFu;
+constexpr uint32_t GS_SEGMENT_MAX = 65535u;
+struct SpectrumTask { uint64_t src_begin; uint64_t hist_begin; uint32_t count; uint32_t group; uint32_t table; uint32_t pad; };
+struct GroupSpectrumArgs {
+    const uint8_t      *src;        // the set's images
+    uint64_t            src_stride;
+    uint32_t            src_hdr;
+    uint32_t            slices, lanes;
+    uint32_t            n_tasks;
+    const uint8_t      *uni;        // the groups' union images, registers in the set's byte order
+    uint64_t            uni_stride;
+    uint32_t            uni_hdr;
+    const uint32_t     *members;
+    const SpectrumTask *tasks;
+    uint32_t           *counts;
+    const uint64_t     *table_hist;
+    uint32_t           *hist;
+};
+hipError_t launch_group_spectrum(const GroupSpectrumArgs &args, hipStream_t stream);
+hipError_t launch_group_spectrum_finish(const GroupSpectrumArgs &args, uint32_t n_tables, hipStream_t stream);
+
 // ---- synthetic genomes --------------------------------------------------------------------
 hipError_t launch_synth(uint64_t first_genome, uint32_t n_genomes, uint64_t n_bases, uint8_t *d_out, hipStream_t stream);
 

@@ -819,6 +819,43 @@ class SketchSet:
         self._ctx._check(self._lib.lash_sketch_set_group_union_plan(self._ctx._h, self._h, off.ctypes.data, len(groups), C.byref(opts), C.byref(plan)))
         return int(plan.segment), int(plan.slices), int(plan.scratch_budget_bytes)
 
+    def group_spectrum(self, groups, segment=None, slices=None, scratch_budget=None, union_images=False, device_out=None):
+        """`lash spectrum` (HyperMinHash sets): groups as for group_union; per group a uint32 array of len(group) + 1 bins, bin c the
+        buckets whose union register is held by exactly c members (bin 0: the empty buckets; the bins sum to 16 384): a uniform sample
+        of the group's k-mer multiplicity spectrum (lash_sketch_set_group_spectrum).  union_images=True also returns group_union's
+        images: (bins, uint8 [n_groups, image_bytes]).  segment / slices / scratch_budget: how the work is cut; the bins do not
+        depend on them.  device_out = (a CUDA int32 / uint32 tensor of sum(len(g) + 1) words, a CUDA uint8 tensor of the images or
+        None): both are written there, asynchronously on the context's stream, and device_out is returned.  LASH_EINVAL raises a
+        LashError (an hll / ull set; a bad member, whose position in the flattened list is .index)."""
+        off, mem = self._groups_csr(groups)
+        opts = _lib.GroupUnionOpts(int(segment or 0), int(slices or 0), int(scratch_budget or 0))
+        bad = C.c_uint64(2**64 - 1)
+        ib = self._ctx.image_bytes(self.algo, self.p)
+        mp = mem.ctypes.data if mem.size else None
+        n_bins = int(off[-1]) + len(groups)
+        if device_out is None:
+            hist = np.zeros(n_bins, dtype=np.uint32)
+            img = np.zeros((len(groups), ib), dtype=np.uint8) if union_images else None
+            rc = self._lib.lash_sketch_set_group_spectrum(self._ctx._h, self._h, off.ctypes.data, mp, len(groups), C.byref(opts),
+                                                          hist.ctypes.data if hist.size else None,
+                                                          img.ctypes.data if img is not None and img.size else None, C.byref(bad))
+        else:
+            d_hist, d_img = device_out
+            assert d_hist.is_cuda and d_hist.is_contiguous() and d_hist.element_size() == 4 and d_hist.numel() >= n_bins
+            assert d_img is None or (d_img.is_cuda and d_img.is_contiguous() and d_img.numel() * d_img.element_size() >= len(groups) * ib)
+            rc = self._lib.lash_sketch_set_group_spectrum_device(self._ctx._h, self._h, off.ctypes.data, mp, len(groups), C.byref(opts),
+                                                                 d_hist.data_ptr() if len(groups) else None,
+                                                                 d_img.data_ptr() if d_img is not None and len(groups) else None, C.byref(bad))
+        if rc != _lib.OK:
+            last = self._lib.lash_ctx_last_error(self._ctx._h)
+            e = LashError(rc, self._lib.lash_strerror(rc).decode() + (" " + last.decode() if last else ""))
+            e.index = bad.value
+            raise e
+        if device_out is not None:
+            return device_out
+        bins = [hist[int(off[g]) + g:int(off[g + 1]) + g + 1] for g in range(len(groups))]
+        return (bins, img) if union_images else bins
+
     def hmh_expected_collisions(self, r0, r1, qry=None, n_cols=None):
         """hyperminhash's expected collisions of the block's SMALL pairs (both sketches <= 2^19 distinct k-mers) as a float64
         [r1 - r0, n_cols] array for lash_dist_rows' hmh_ec (other entries are not read), or None when the block has none.
