@@ -708,6 +708,35 @@ void     lash_tree_free(lash_ctx *ctx, lash_tree *t);
 typedef struct lash_nj_join { uint32_t a, b; double len_a, len_b; } lash_nj_join;
 int      lash_tree_build_nj(lash_ctx *ctx, lash_tree *t, lash_nj_join *out, lash_tree_stats *stats);
 
+/* lash_tree_build_pcoa: `lash dist --pcoa K`, principal coordinates (PCoA, classical MDS) of the same lash_tree matrix (dist_pcoa.hip;
+ * create / set_rows / get_rows / free as above; n >= 2, k 1..16).  The rule: A = -1/2 D o D (every cell, the diagonal included, as set);
+ * B[i][j] = A[i][j] - (r[i] + r[j]) + g, r the row means of A and g the mean of r (Gower centring, in place on the device).  The axes are
+ * the k' = min(k, n - 1) ALGEBRAICALLY largest eigenpairs (theta_a, v_a) of B, theta_1 >= theta_2 >= ..., |v_a|_2 = 1 -- not the largest
+ * in size: sketch distances are not Euclidean, B has negative eigenvalues and one of them may exceed theta_k in size.  The sign of v_a
+ * makes its component of largest size positive (ties: the lowest row).
+ *   out_eigenvalues[a] = theta_a            out_coords[i * k + a] = v_a[i] * sqrt(max(theta_a, 0))
+ * so an axis with theta_a <= 0 is all +0.0, and so is every entry a >= k' (B has at most n - 1 non-zero eigenvalues).  Where eigenvalues
+ * coincide, any orthonormal basis of their eigenspace is a valid answer.
+ * The solver is a subspace iteration on B + sigma I with min(n, max(2k, k + 8)) vectors and a Rayleigh-Ritz step per iteration; the Ritz
+ * values are sorted algebraically, so a negative eigenvalue the subspace holds costs a spare vector; sigma = |B|_F / 1000 + 1.1 times the
+ * Frobenius norm of B outside the subspace covers the negative eigenvalues it does not hold, renewed every iteration.  A converged
+ * answer is accepted only if theta_k' + sigma >= 0 (then no eigenvalue outside the subspace exceeds theta_k'); otherwise the solve is
+ * repeated from the start vectors with sigma >= -lambda_min(B) throughout, which ranks algebraically.  It stops when |B v_a - theta_a v_a|_2 <=
+ * tol * max(theta_1, 0) holds for every a <= k', the residuals being those of B itself, computed on the device.  tol <= 0 means 1e-10,
+ * max_iter = 0 means 2000.  Otherwise LASH_EINVAL with a last-error text that gives the iterations done and the worst relative residual,
+ * and the outputs are untouched.  Everything is queued on ctx's stream; per iteration two 32 x 32 matrices come to the host (Q^T B Q, solved
+ * there by cyclic Jacobi, and the Gram matrix of the residual vectors, whose diagonal holds the squared norms) with one status word,
+ * and the 32 x 32 Ritz vectors and 32 Ritz values go back.  No floating-point atomics, every reduction a fixed tree, start vectors from splitmix64 with a fixed
+ * seed: two builds of the same matrix bits give the same output bits, whatever order and split set_rows received.
+ * It consumes the matrix, as lash_tree_build does.  LASH_EINVAL, with a last-error text: k outside 1..16, a second build (of any kind),
+ * n < 2, a row that was never set, a NaN or an infinite value among the cells set_rows read (the text names row and col).
+ * stats (may be NULL): iterations (of both passes together, as max_iter counts them); products = B Q products, each reading the matrix once; bytes = 8 n^2; worst_residual = the largest of
+ * the k' relative residuals at exit; shift = the last sigma; trace = the sum of B[i][i], which theta_a is divided by for the share of an
+ * axis (it can pass 1 in sum when negative eigenvalues exist). */
+typedef struct lash_pcoa_stats { uint64_t iterations, products, bytes; double worst_residual, shift, trace; } lash_pcoa_stats;
+int      lash_tree_build_pcoa(lash_ctx *ctx, lash_tree *t, uint32_t k, double tol, uint32_t max_iter, double *out_eigenvalues, double *out_coords,
+                              lash_pcoa_stats *stats);
+
 /* HyperMinHash sets: hyperminhash's expected_collisions(n, m) for the pairs of a block in which BOTH sketches hold at most 2^19
  * distinct k-mers (the regime in which the crate walks 65 536 cells per pair; lash_hmh_pair_expected_collisions below):
  * out_ec[(r - r0) * n_cols + c] for exactly those pairs — the other entries are left untouched, lash_dist_rows derives theirs in

@@ -63,6 +63,12 @@ class NjJoin(C.Structure):
     _fields_ = [("a", C.c_uint32), ("b", C.c_uint32), ("len_a", C.c_double), ("len_b", C.c_double)]
 
 
+class PcoaStats(C.Structure):
+    """lash_pcoa_stats: what one lash_tree_build_pcoa did"""
+    _fields_ = [("iterations", C.c_uint64), ("products", C.c_uint64), ("bytes", C.c_uint64), ("worst_residual", C.c_double),
+                ("shift", C.c_double), ("trace", C.c_double)]
+
+
 class PrefixUnionOpts(C.Structure):
     """lash_prefix_union_opts: how lash_sketch_set_prefix_union_cardinalities cuts its work (0 = the library chooses)"""
     _fields_ = [("slices", C.c_uint32), ("hist_budget_bytes", C.c_uint64)]
@@ -210,6 +216,7 @@ PROTOTYPES = {
     "lash_tree_get_rows": (_int, [_vp, _vp, _u32, _u32, _vp]),
     "lash_tree_build": (_int, [_vp, _vp, _int, _vp, C.POINTER(TreeStats)]),
     "lash_tree_build_nj": (_int, [_vp, _vp, _vp, C.POINTER(TreeStats)]),
+    "lash_tree_build_pcoa": (_int, [_vp, _vp, _u32, C.c_double, _u32, _vp, _vp, C.POINTER(PcoaStats)]),
     "lash_tree_free": (None, [_vp, _vp]),
     "lash_sketch_set_prefix_union_cardinalities": (_int, [_vp, _vp, _vp, _u32, _u32, _int, _vp, C.POINTER(PrefixUnionOpts), _vp, C.POINTER(_u64)]),
     "lash_sketch_set_prefix_union_plan": (_int, [_vp, _vp, _u32, _u32, C.POINTER(PrefixUnionOpts), C.POINTER(PrefixUnionOpts)]),

@@ -39,6 +39,8 @@
 // (lash_tree_set_rows; other devices' workers hand theirs over through the host).  After the last block lash_tree_build merges on the
 // device; --tree writes the Newick text, --cluster D --linkage average|complete the clusters of the cut at D (newick.hpp).  --tree --nj
 // fills the same matrix and lets lash_tree_build_nj join it: the neighbour-joining tree, unrooted, no heights to cut.
+// --pcoa K (not upstream; same files only) fills the same matrix too and lets lash_tree_build_pcoa centre it and solve its K algebraically
+// largest eigenpairs on the device; K eigenvalues and N x K coordinates come back and go out as one table (dist_format: pcoa_text).
 #include "dist.hpp"
 
 #include <dirent.h>
@@ -185,6 +187,8 @@ std::string load_input(const DistOptions &opt, const Timing &timing, DistInput &
         return "--cluster needs an all-vs-all run: -q and -r must name the same sketch files";
     if (opt.tree && !(in.same_files && in.same_sketches))
         return "--tree needs an all-vs-all run: -q and -r must name the same sketch files";
+    if (opt.pcoa && !(in.same_files && in.same_sketches))
+        return "--pcoa needs an all-vs-all run: -q and -r must name the same sketch files";
     if (opt.has_derep && !(in.same_files && in.same_sketches))
         return "--derep needs an all-vs-all run: -q and -r must name the same sketch files";
     // utils.rs:111-127: the maps' key order (a repeated name is one entry carrying its last sketch)
@@ -590,6 +594,22 @@ std::string finish_tree(Run &run)
 {
     const DistInput &in = run.in;
     const DistOptions &opt = run.opt;
+    if (opt.pcoa) {
+        const uint32_t k = opt.pcoa;
+        std::vector<double> eig(k), coords((size_t)in.nr * k);
+        lash_pcoa_stats st{};
+        const auto t0 = std::chrono::steady_clock::now();
+        const int rc = lash_tree_build_pcoa(run.tree_ctx, run.tree, k, 0.0, 0, eig.data(), coords.data(), &st);
+        const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        if (rc != LASH_OK) return std::string("--pcoa: ") + lash_strerror(rc) + " " + lash_ctx_last_error(run.tree_ctx);
+        if (run.timing.on) fprintf(stderr, "[lash dist] --pcoa: %u names, %llu iterations, %llu products, %llu matrix bytes, shift %.6g, worst residual "
+                                           "%.3g, build %.3f ms\n", in.nr, (unsigned long long)st.iterations, (unsigned long long)st.products,
+                                   (unsigned long long)st.bytes, st.shift, st.worst_residual, ms);
+        const std::string text = pcoa_text(in.row_name, k, eig.data(), coords.data(), st.trace);
+        fwrite(text.data(), 1, text.size(), run.out);
+        run.timing.mark("--pcoa: the coordinates written");
+        return "";
+    }
     if (opt.nj) {
         std::vector<lash_nj_join> joins(in.nr > 1 ? in.nr - 1 : 0);
         lash_tree_stats st{};
@@ -665,6 +685,7 @@ std::string run_dist(const DistOptions &opt)
     DistInput in;
     std::string err = load_input(opt, timing, in);
     if (!err.empty()) return err;
+    if (opt.pcoa && in.nr < 2) return "--pcoa needs at least 2 names: " + std::to_string(in.nr) + " cannot be ordinated";
     const bool hll = in.algo_id == LASH_HLL, hmh = in.algo_id == LASH_HMH;
     lash_hll_bias *bias = nullptr;
     if (hll && !opt.hll_bias_file.empty()) {
@@ -707,7 +728,7 @@ std::string run_dist(const DistOptions &opt)
     run.gpu_ec = small_ref && small_qry;
     run.out = fopen(opt.output_file.c_str(), "w");
     if (!run.out) return "cannot create " + opt.output_file;
-    if (opt.tree) {}                                                                                 // (the tree is the whole output)
+    if (opt.tree || opt.pcoa) {}                                                                     // (the tree, or the table of coordinates, is the whole output)
     else if (opt.has_cluster || opt.has_derep) fprintf(run.out, "Representative\tMember\n");
     else if (!opt.matrix) fprintf(run.out, "Reference\tQuery\tDistance\n");                          // main.rs:409-412
     else for (uint32_t j = 0; j < in.nq; ++j) fprintf(run.out, "\t%s", in.col_name[j].c_str());      // main.rs:439-441

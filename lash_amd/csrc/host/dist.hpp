@@ -26,7 +26,9 @@ struct DistOptions {
     bool nj = false;           // --nj (with --tree): the neighbour-joining tree instead of a linkage tree (lash_tree_build_nj)
     int linkage = -1;          // --linkage average|single|complete: LASH_LINKAGE_*; -1 = not given (--tree: average; --cluster: single, the
                                // union-find route, which an explicit single takes too; average / complete cut the tree at D)
-    bool use_tree() const { return tree || (has_cluster && (linkage == LASH_LINKAGE_AVERAGE || linkage == LASH_LINKAGE_COMPLETE)); }
+    uint32_t pcoa = 0;         // --pcoa K (1..16): the K principal coordinates of all names of a triangle run instead of pairs, from the same
+                               // matrix on the device (lash_tree_build_pcoa); 0 = off
+    bool use_tree() const { return tree || pcoa || (has_cluster && (linkage == LASH_LINKAGE_AVERAGE || linkage == LASH_LINKAGE_COMPLETE)); }
     bool has_derep = false;    // --derep D: greedy representatives of a triangle run in row order; "within D" iff --max-dist D prints the pair
     double derep_dist = 0.0;
     int measure = LASH_MEASURE_JACCARD;   // --containment query|reference: LASH_MEASURE_CONTAIN_*; directional, so the run is a rectangle even

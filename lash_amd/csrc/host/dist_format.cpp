@@ -3,6 +3,7 @@
 
 #include <charconv>
 #include <cmath>
+#include <cstdio>
 #include <cstring>
 #include <algorithm>
 #include <atomic>
@@ -202,6 +203,24 @@ std::string dist_block_values(int algo, int p, int k, int model, bool fp32, cons
         }
         return f;
     });
+}
+
+std::string pcoa_text(const std::vector<std::string> &name, uint32_t k, const double *eigenvalues, const double *coords, double trace)
+{
+    char num[40];
+    std::string text = "#Eigenvalue";
+    for (uint32_t a = 0; a < k; ++a) { snprintf(num, sizeof num, "\t%.10g", eigenvalues[a]); text += num; }
+    text += "\n#Explained";
+    for (uint32_t a = 0; a < k; ++a) { snprintf(num, sizeof num, "\t%.10g", trace != 0.0 ? eigenvalues[a] / trace : NAN); text += num; }
+    text += "\nName";
+    for (uint32_t a = 0; a < k; ++a) { snprintf(num, sizeof num, "\tPC%u", a + 1); text += num; }
+    text += "\n";
+    for (size_t i = 0; i < name.size(); ++i) {
+        text += name[i];
+        for (uint32_t a = 0; a < k; ++a) { snprintf(num, sizeof num, "\t%.10g", coords[i * k + a]); text += num; }
+        text += "\n";
+    }
+    return text;
 }
 
 }  // namespace lashhost

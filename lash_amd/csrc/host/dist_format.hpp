@@ -67,5 +67,8 @@ std::string dist_block_rows(int algo, int p, int k, int model, bool fp32, const 
 // dist_block_rows, or the two names of a NaN distance.
 std::string dist_block_values(int algo, int p, int k, int model, bool fp32, const void *hll_bias, uint32_t i0, uint32_t i1, const double *card,
                               const BlockTables &t, const std::vector<std::string> &name, const uint32_t *name_id, int threads, double *out);
+// --pcoa K: the table of lash_tree_build_pcoa's result, tab-separated, every number as %.10g: "#Eigenvalue" and the k eigenvalues;
+// "#Explained" and eigenvalue / trace for each (nan when the trace is 0); "Name", "PC1" .. "PCk"; one line per name with coords[i * k + a].
+std::string pcoa_text(const std::vector<std::string> &name, uint32_t k, const double *eigenvalues, const double *coords, double trace);
 
 }  // namespace lashhost

@@ -14,7 +14,7 @@
 // the pairs with distance <= D), --top K (only each name's K nearest), --cluster D (single-linkage clusters of an all-vs-all instead
 // of pairs), --derep D (greedy representatives of an all-vs-all in row order), --containment query|reference (the distance of the
 // containment fraction instead of the Jaccard-derived one; always a rectangle), --tree / --linkage average|single|complete (one Newick
-// tree of an all-vs-all, merged on the GPU; with --cluster D, that tree cut at D), --tree --nj (the neighbour-joining tree instead, joined on the GPU) (reference rows per GPU call); both: --layout SPEC (or $LASH_LAYOUT): the crate-internal rules as data, see `lash_layout`
+// tree of an all-vs-all, merged on the GPU; with --cluster D, that tree cut at D), --tree --nj (the neighbour-joining tree instead, joined on the GPU), --pcoa K (principal coordinates of an all-vs-all, solved on the GPU) (reference rows per GPU call); both: --layout SPEC (or $LASH_LAYOUT): the crate-internal rules as data, see `lash_layout`
 // in include/lash_gfx950.h.
 #include <algorithm>
 #include <chrono>
@@ -111,6 +111,14 @@ void usage()
             "                     mashtree) instead of a linkage tree, joined on the GPU from the same matrix.  It assumes no clock, so\n"
             "                     it is the one to read as a phylogeny; it is unrooted (the root prints as a trifurcation) and a branch\n"
             "                     length may be negative.  Not with --linkage or --cluster: an NJ tree has no heights to cut\n"
+            "      --pcoa <K>     all-vs-all only: principal coordinates (PCoA, classical MDS; skbio pcoa, ape::pcoa, cmdscale) of all names\n"
+            "                     instead of pairs, K 1-16.  The matrix of printed distances is Gower-centred and its K algebraically largest\n"
+            "                     eigenpairs are solved on the GPU (8 x N^2 bytes of device memory).  Output, tab-separated, numbers as\n"
+            "                     %%.10g: #Eigenvalue and K values; #Explained and K values, eigenvalue / trace (they can sum past 1: sketch\n"
+            "                     distances are not Euclidean and the trace counts the negative eigenvalues); Name PC1 .. PCK; one line per\n"
+            "                     name in row order.  An axis whose eigenvalue is <= 0, or beyond N - 1, is all zeros; where eigenvalues\n"
+            "                     coincide the axes are one valid basis of their space.  Not with --dm, --top, --max-dist, --cluster, --derep,\n"
+            "                     --containment, --tree, --nj or --linkage\n"
             "      --containment <query|reference>  the distance of the containment fraction instead of the Jaccard-derived one, for sides\n"
             "                     of different size (a genome against a metagenome, a plasmid against its host): query = how much of the\n"
             "                     query is in the reference, reference = how much of the reference is in the query.  Directional, so\n"
@@ -467,6 +475,25 @@ int cmd_dist(int argc, char **argv)
         if (opt.linkage >= 0) { fprintf(stderr, "error: --nj cannot be used with --linkage (neighbour joining is a rule of its own, not a linkage)\n"); return 2; }
         if (!opt.tree) { fprintf(stderr, "error: --nj needs --tree (it says which tree --tree writes)\n"); return 2; }
         opt.nj = true;
+    }
+    if (a.kv.count("pcoa")) {
+        const std::string &v = a.kv["pcoa"];
+        uint64_t n = 0;
+        if (!to_u64(v, n) || n < 1 || n > 16) { fprintf(stderr, "error: invalid value '%s' for --pcoa: an integer from 1 to 16 is required\n", v.c_str()); return 2; }
+        if (opt.matrix) { fprintf(stderr, "error: --pcoa cannot be used with --dm (coordinates are not a matrix of distances)\n"); return 2; }
+        if (opt.top) { fprintf(stderr, "error: --pcoa cannot be used with --top (principal coordinates need every pair)\n"); return 2; }
+        if (opt.has_max_dist) { fprintf(stderr, "error: --pcoa cannot be used with --max-dist (principal coordinates need every pair)\n"); return 2; }
+        if (opt.has_cluster) { fprintf(stderr, "error: --pcoa cannot be used with --cluster (coordinates or clusters, not both)\n"); return 2; }
+        if (opt.has_derep) { fprintf(stderr, "error: --pcoa cannot be used with --derep (coordinates or greedy representatives, not both)\n"); return 2; }
+        if (opt.measure != LASH_MEASURE_JACCARD) { fprintf(stderr, "error: --pcoa cannot be used with --containment (principal coordinates need a symmetric distance)\n"); return 2; }
+        if (opt.tree) { fprintf(stderr, "error: --pcoa cannot be used with --tree (coordinates or a tree, not both)\n"); return 2; }
+        if (opt.nj) { fprintf(stderr, "error: --pcoa cannot be used with --nj (coordinates or a tree, not both)\n"); return 2; }
+        if (opt.linkage >= 0) { fprintf(stderr, "error: --pcoa cannot be used with --linkage (principal coordinates merge no clusters)\n"); return 2; }
+        if (prefix_stem(opt.query_prefix) != prefix_stem(opt.ref_prefix)) {
+            fprintf(stderr, "error: --pcoa needs an all-vs-all run: -q and -r must name the same sketch files\n");
+            return 2;
+        }
+        opt.pcoa = (uint32_t)n;
     }
     err = layout_from_option(a.kv.count("layout") ? a.kv["layout"] : "", opt.layout);
     if (!err.empty()) { fprintf(stderr, "error: %s\n", err.c_str()); return 2; }

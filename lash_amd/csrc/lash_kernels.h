@@ -415,6 +415,22 @@ hipError_t launch_gather_rows(const uint8_t *d_src, const uint32_t *d_order, uin
 hipError_t launch_collision_vectors(const double *d_card, uint32_t n, double *d_P, hipStream_t stream);
 hipError_t launch_collision_gemm(const double *d_A, uint32_t m, const double *d_B, uint32_t n, double *d_X, hipStream_t stream);
 
+// ---- principal coordinates of the lash_tree matrix (dist_pcoa.hip) --------------------------------------------------
+// Panels are row-major [n][ld], ld = 16 or 32, columns >= m zero; the small matrices (G, R, W) are [32][32].  Every sum is a fixed tree.
+// centre: D -> B in place (Gower); scal[0] = g, scal[1] = |B|_F^2, scal[2] = trace(B).  product: Y = B Q with v_mfma_f64_16x16x4_f64, B
+// read once; part holds pcoa_product_segments(n) panels when that is above 1.  gram: G = X^T Z through partial[ceil(n / 64)][32][32].
+// orthonormalise: Z <- Z R^-1 with G = Z^T Z = R^T R, twice; *flag is raised by a pivot that is not positive.  rotate: V = Q W, U = Y W,
+// Z = U + sigma V, E = U - V diag(theta).
+uint32_t   pcoa_product_segments(uint32_t n, uint32_t *seg_len);
+hipError_t launch_pcoa_centre(double *d_D, uint32_t n, double *d_rmean, double *d_rowsq, double *d_diag, double *d_scal, hipStream_t stream);
+hipError_t launch_pcoa_init(double *d_Q, uint32_t n, uint32_t ld, uint32_t m, hipStream_t stream);
+hipError_t launch_pcoa_product(const double *d_B, uint32_t n, const double *d_Q, uint32_t ld, double *d_Y, double *d_part, hipStream_t stream);
+hipError_t launch_pcoa_gram(const double *d_X, const double *d_Z, uint32_t n, uint32_t ld, double *d_partial, double *d_G, hipStream_t stream);
+hipError_t launch_pcoa_orthonormalise(double *d_Z, uint32_t n, uint32_t ld, uint32_t m, double *d_partial, double *d_G, double *d_R, uint32_t *d_flag,
+                                      hipStream_t stream);
+hipError_t launch_pcoa_rotate(const double *d_Q, const double *d_Y, const double *d_W, const double *d_theta, double sigma, double *d_V, double *d_Z,
+                              double *d_E, uint32_t n, uint32_t ld, hipStream_t stream);
+
 // ---- prefix unions along orderings (prefix_union.hip) -------------------------------------------------------------
 // hist[(o * len + t) * 256 + b] += bin b of the register histogram (as launch_sketch_hist's) of image[orders[o][0]] U ... U
 // image[orders[o][t]], for the launch's n_orders orders (at most 65 535).  hist must be zero before the launch; every entry of
