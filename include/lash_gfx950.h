@@ -842,6 +842,40 @@ int lash_sketch_set_group_spectrum_device(lash_ctx *ctx, const lash_sketch_set *
                                           uint32_t *d_out_hist /* device */, uint8_t *d_out_union_images /* device, may be NULL */,
                                           uint64_t *bad_index);
 
+/* ---- screen: winner-takes-all containment of queries against candidate references (`lash screen`, screen_wta.hip) ----
+ * HyperMinHash sets only, both.  With q[b] the 16 384 16-bit registers of a query's image and r_i[b] those of reference row i:
+ *   reference i HOLDS bucket b  iff  q[b] != 0 and r_i[b] == q[b]     the query's sampled k-mer of the bucket is one of the reference's
+ * Every query row j of `qry` has a candidate list L_j = (i_0, i_1, ...) = cand_ref[cand_off[j] .. cand_off[j + 1]) of rows of `ref`;
+ * POSITION IS PRIORITY, i_0 is best.  For the list of one query:
+ *   winner[b] = the smallest position t such that i_t holds b, NONE (0xFFFFFFFF) if no candidate holds b
+ *   shared[t] = #{ b : i_t holds b }                                   the C of lash_hmh_pair_counts for the pair (i_t, query)
+ *   won[t]    = #{ b : winner[b] == t }                                the buckets credited to i_t when each goes to its best holder
+ * so won[t] <= shared[t]; the sum of won over a list is the number of buckets some candidate holds, at most the query's occupied
+ * buckets; a row listed twice wins nothing at its later position; an empty list gives nothing.  Lists may overlap.  All of it is exact
+ * integer work, and equality and "not 0" do not depend on the layout's register byte order.
+ *   cand_off          n_qry + 1 offsets, n_qry = the query set's size; cand_off[0] = 0 and the offsets never decrease
+ *   out_shared,       uint32, cand_off[n_qry] each: entry cand_off[j] + t belongs to position t of query j's list
+ *   out_won
+ *   opts              as for lash_sketch_set_group_union: segment = the positions of a list one task walks, slices = the workgroups an
+ *                     image's registers are cut over (lash_sketch_set_group_union_plan on the reference set and cand_off answers for
+ *                     both); scratch_budget_bytes bounds the winner tables (64 KiB per query) of a chunk of queries, at least one
+ *                     query per chunk [1 GiB]
+ *   The counts do not depend on opts: they are minima and sums of integers.
+ *   LASH_EINVAL  NULL arguments, offsets that do not start at 0 or decrease, a cand_ref entry >= the reference set's size (*bad_index =
+ *                its position in cand_ref), a set that is not HyperMinHash: an hll or ull register does not identify a k-mer
+ *                (lash_ctx_last_error says which set), a set made under another layout than the context's
+ *   LASH_ENOMEM  the winner tables of one chunk do not fit the device
+ * cand_off[n_qry] == 0 is LASH_OK and touches nothing.  Both sets' own state (the cardinalities they have taken, what prepare built) is
+ * left untouched.  The host form is synchronous; _device writes to device memory and is asynchronous on the context's stream (the
+ * lists are copied before it returns). */
+int lash_sketch_set_screen_wta(lash_ctx *ctx, const lash_sketch_set *ref, const lash_sketch_set *qry,
+                               const uint64_t *cand_off /* n_qry + 1, CSR over the query set's rows */,
+                               const uint32_t *cand_ref /* reference rows, best first */, const lash_group_union_opts *opts /* may be NULL */,
+                               uint32_t *out_shared /* host */, uint32_t *out_won /* host */, uint64_t *bad_index);
+int lash_sketch_set_screen_wta_device(lash_ctx *ctx, const lash_sketch_set *ref, const lash_sketch_set *qry, const uint64_t *cand_off,
+                                      const uint32_t *cand_ref, const lash_group_union_opts *opts /* may be NULL */,
+                                      uint32_t *d_out_shared /* device */, uint32_t *d_out_won /* device */, uint64_t *bad_index);
+
 /* Synthetic genomes of SURVEY.md §8(d) generated in HBM (bench / tests): genome ids first..first+n-1,
  * n_bases ASCII bytes each, written back to back at d_out. */
 int lash_synth_genomes_device(lash_ctx *ctx, uint64_t first_genome, uint32_t n_genomes, uint64_t n_bases, uint8_t *d_out);

@@ -225,6 +225,8 @@ PROTOTYPES = {
     "lash_sketch_set_group_union_plan": (_int, [_vp, _vp, _vp, _u32, C.POINTER(GroupUnionOpts), C.POINTER(GroupUnionOpts)]),
     "lash_sketch_set_group_spectrum": (_int, [_vp, _vp, _vp, _vp, _u32, C.POINTER(GroupUnionOpts), _vp, _vp, C.POINTER(_u64)]),
     "lash_sketch_set_group_spectrum_device": (_int, [_vp, _vp, _vp, _vp, _u32, C.POINTER(GroupUnionOpts), _vp, _vp, C.POINTER(_u64)]),
+    "lash_sketch_set_screen_wta": (_int, [_vp, _vp, _vp, _vp, _vp, C.POINTER(GroupUnionOpts), _vp, _vp, C.POINTER(_u64)]),
+    "lash_sketch_set_screen_wta_device": (_int, [_vp, _vp, _vp, _vp, _vp, C.POINTER(GroupUnionOpts), _vp, _vp, C.POINTER(_u64)]),
     "lash_synth_genomes_device": (_int, [_vp, _u64, _u32, _u64, _vp]),
 }
 

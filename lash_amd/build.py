@@ -8,7 +8,7 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(PKG)
 CSRC = os.path.join(PKG, "csrc")
 LIB = os.path.join(PKG, "liblash_gfx950.so")
-SOURCES = ["lash_api.hip", "lash_plan.hip", "lash_hll_replay.hip", "lash_dist_api.hip", "lash_growth_api.hip", "prefix_union.hip", "lash_group_union_api.hip", "group_union.hip", "lash_group_spectrum_api.hip", "group_spectrum.hip", "sketch_set.hip", "sketch_kernels.hip", "sole_kernels.hip", "kmer_filter.hip", "pack_kernels.hip", "text_tiles.hip", "fastq_check.hip", "fasta_index.hip", "fasta_coords.hip", "fasta_windows.hip", "fasta_translate.hip", "lash_fasta_api.hip", "dist_kernels.hip", "dist_filter.hip", "dist_top.hip", "dist_cluster.hip", "dist_derep.hip", "dist_tree.hip", "dist_nj.hip", "dist_pcoa.hip", "pair_planes.hip", "dist_estimators.hip", "hll_bias_sim.hip"]
+SOURCES = ["lash_api.hip", "lash_plan.hip", "lash_hll_replay.hip", "lash_dist_api.hip", "lash_growth_api.hip", "prefix_union.hip", "lash_group_union_api.hip", "group_union.hip", "lash_group_spectrum_api.hip", "group_spectrum.hip", "lash_screen_api.hip", "screen_wta.hip", "sketch_set.hip", "sketch_kernels.hip", "sole_kernels.hip", "kmer_filter.hip", "pack_kernels.hip", "text_tiles.hip", "fastq_check.hip", "fasta_index.hip", "fasta_coords.hip", "fasta_windows.hip", "fasta_translate.hip", "lash_fasta_api.hip", "dist_kernels.hip", "dist_filter.hip", "dist_top.hip", "dist_cluster.hip", "dist_derep.hip", "dist_tree.hip", "dist_nj.hip", "dist_pcoa.hip", "pair_planes.hip", "dist_estimators.hip", "hll_bias_sim.hip"]
 HEADERS = ["lash_common.h", "lash_ctx.h", "lash_internal.h", "lash_kernels.h", "lash_device.h", "sketch_rules.h", "ull_estimators.h", "dist_pair.h", "dist_filter.h", "dist_tree.h", "text_tiles.h", os.path.join(ROOT, "include", "lash_gfx950.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wno-unused-function"]
 
@@ -62,7 +62,7 @@ def build_library(force=False, verbose=False):
 
 
 HOST_DIR = os.path.join(CSRC, "host")
-HOST_SOURCES = ["main.cpp", "sketch_files.cpp", "chunk_reader.cpp", "fastx.cpp", "pgzip.cpp", "inflate_fast.cpp", "zstd_dl.cpp", "codec_dl.cpp", "json_out.cpp", "name_order.cpp", "dist_format.cpp", "newick.cpp", "dist.cpp", "growth.cpp", "merge.cpp", "spectrum.cpp"]
+HOST_SOURCES = ["main.cpp", "sketch_files.cpp", "chunk_reader.cpp", "fastx.cpp", "pgzip.cpp", "inflate_fast.cpp", "zstd_dl.cpp", "codec_dl.cpp", "json_out.cpp", "name_order.cpp", "dist_format.cpp", "newick.cpp", "dist.cpp", "growth.cpp", "merge.cpp", "spectrum.cpp", "screen.cpp"]
 CLI = os.path.join(PKG, "bin", "lash")
 HOSTLIB = os.path.join(PKG, "liblash_host.so")
 

@@ -46,6 +46,12 @@ char *put_dist(char *p, double d)
 
 }  // namespace
 
+void append_dist(std::string &out, double d)
+{
+    char buf[32];
+    out.append(buf, (size_t)(put_dist(buf, d) - buf));
+}
+
 size_t row_text_bound(const std::string &rname, const std::vector<std::string> &qtab, uint32_t n_print, bool matrix)
 {
     if (matrix) return 1 + rname.size() + (size_t)n_print * 28;

@@ -16,6 +16,9 @@ std::vector<std::string> tabbed_names(const std::vector<std::string> &names);
 void name_ids(const std::vector<std::string> &row_name, const std::vector<std::string> &col_name, std::vector<uint32_t> &row_id,
               std::vector<uint32_t> &col_id);
 
+// Appends one distance as every row prints it: "{:.6}" (main.rs:456,461), NaN as Rust's Display writes it
+void append_dist(std::string &out, double d);
+
 // Appends the text of ONE reference row: its first n_print columns, dist[c] the distance to column c, except where the column
 // carries the row's name (col_id[c] == row_id), which prints 0 (main.rs:452-453).  qtab: tabbed_names() of the columns (list form).
 void append_row(std::string &out, const std::string &rname, const std::vector<std::string> &qtab, uint32_t n_print, const double *dist,

@@ -5,6 +5,7 @@
 //   lash growth -r PREFIX [-o growth] [--orders P] [--seed S] [--file-order] [-e fgra|ml] [-t N]   (not upstream: union cardinality along orderings)
 //   lash merge  -r PREFIX -o OUT (--groups FILE | --all NAME) [--keep-others] [--file-order] [-t N]   (not upstream: one sketch per group of sketches)
 //   lash spectrum -r PREFIX -o OUT [--groups FILE | --all NAME] [--core F] [--cloud F] [--curves] [--file-order] [-t N]   (not upstream: k-mer sharing spectrum of groups, hmh)
+//   lash screen -r DB -q SAMPLE -o FILE [--max-dist D] [--keep-losers] [-m 1|0] [--file-order] [--block-rows N] [-t N]   (not upstream: winner-takes-all containment of samples against a database, hmh)
 //   lash hll-bias -o FILE [-p P[,P...]] [--points N] [--trials T] [--seed S] [--device D]    (not upstream: HLL++ bias tables, simulated)
 // Extras that do not exist upstream: --gpus N / --device D / --devices LIST (which GPUs to use, one worker each), --batch-mb M, --stream-mb M (files
 // larger than M MiB are streamed in chunks with on-device accumulation), --hmh-x-low, --min-count M [--count-cells-log2 L] (drop the k-mers a
@@ -31,6 +32,7 @@
 #include "dist.hpp"
 #include "growth.hpp"
 #include "merge.hpp"
+#include "screen.hpp"
 #include "sketch_files.hpp"
 #include "spectrum.hpp"
 
@@ -55,6 +57,7 @@ void usage()
             "  growth  Union cardinality of a collection along orderings: how much each further genome adds\n"
             "  merge   One sketch per group of a collection's sketches (clusters, the files of a sample), united on the GPU\n"
             "  spectrum  How the k-mers of each group's union are shared among its members: core, shell and cloud (hmh sketches)\n"
+            "  screen  What is in a sample: references scored by containment, every shared k-mer credited to its best reference only (hmh sketches)\n"
             "  hll-bias  Simulates the HLL++ bias tables on the GPU and writes the file dist --hll-bias reads\n\n"
             "sketch options:\n"
             "  -f, --file <file>            One file containing list of FASTA/FASTQ files (.gz/.zstd supported), one per line\n"
@@ -173,6 +176,24 @@ void usage()
             "                               distinct k-mers of the union (Pan) and of the intersection (Core) of m members, exactly, over all\n"
             "                               subsets of m members (growth --orders P samples orderings instead)\n"
             "      --file-order  --device <D>  --layout <SPEC>  -t, --threads <n> (accepted as for merge; the tables do not depend on them)\n"
+            "screen options:\n"
+            "  -r, --reference <prefix>     The database, read as dist reads a side; HyperMinHash sketches only (an hll or ull collection is refused)\n"
+            "  -q, --query <prefix>         The samples (metagenomes, read sets), sketched with the same -k; HyperMinHash too\n"
+            "  -o, --output <file>          Where the table goes: Query<TAB>Reference<TAB>Shared<TAB>Won<TAB>Buckets<TAB>Distance<TAB>WtaDistance, queries in\n"
+            "                               row order (the reference's key order, or list order with --file-order), a query's references best\n"
+            "                               first.  Distance = what dist --containment reference prints for the pair (the same name prints its\n"
+            "                               own distance, not 0).  Shared = the buckets whose sampled k-mer of the query is one of the\n"
+            "                               reference's; Won = those of them no better reference of the query holds (winner takes all, like mash\n"
+            "                               screen -w); Buckets = the buckets either sketch occupies.  WtaDistance = Distance recomputed with\n"
+            "                               Won in the place of Shared.  Better: Distance ascending, then the larger reference, then its row\n"
+            "      --max-dist <D>           The candidates of a query are the references with Distance <= D, and a row is printed iff its\n"
+            "                               WtaDistance <= D too, D in [0, 1] [default: every reference whose collision-corrected similarity is\n"
+            "                               positive: Distance < 1]\n"
+            "      --keep-losers            Print every candidate, also those whose WtaDistance no longer passes\n"
+            "  -m, --model <1|0>  --file-order  --block-rows <N>  --device <D>  --layout <SPEC>  -t, --threads <n> (the bytes do not depend on\n"
+            "                               --block-rows or -t)\n"
+            "                               A 5 Mbp genome in a 5 Gbp sample rests on about 16 of the 16384 buckets: winner takes all removes\n"
+            "                               redundancy, it does not add resolution\n"
             "hll-bias options:\n"
             "  -o, --output <file>          Where the tables go (text: \"p <p> <n>\" then n lines \"<raw estimate> <bias>\")\n"
             "  -p, --precision <p[,p...]>   Precisions to simulate, each 4-18 [default: 4,5,...,18]\n"
@@ -652,6 +673,64 @@ int cmd_spectrum(int argc, char **argv)
     return 0;
 }
 
+// lash screen -r DB_PREFIX -q SAMPLE_PREFIX -o FILE [--max-dist D] [--keep-losers] [-m 0|1] [--file-order] [--block-rows N] [--device D] [--layout SPEC] [-t N]
+int cmd_screen(int argc, char **argv)
+{
+    Args a;
+    std::string err;
+    const std::map<std::string, std::string> alias = {{"r", "reference"}, {"q", "query"}, {"o", "output"}, {"t", "threads"}, {"m", "model"}};
+    const std::vector<std::string> known = {"reference", "query", "output", "threads", "model", "max-dist", "keep-losers", "file-order", "block-rows",
+                                            "device", "layout", "help"};
+    for (int i = 2; i < argc; ++i) {
+        const std::string s = argv[i];
+        if (s.rfind("--", 0) != 0) continue;
+        const std::string key = s.substr(2, s.find('=') == std::string::npos ? std::string::npos : s.find('=') - 2);
+        if (std::find(known.begin(), known.end(), key) == known.end()) { fprintf(stderr, "error: unexpected argument '--%s'\n", key.c_str()); return 2; }
+    }
+    if (!parse(argc, argv, 2, alias, {"keep-losers", "file-order", "help"}, a, err)) { fprintf(stderr, "error: %s\n", err.c_str()); return 2; }
+    if (a.flags.count("help")) { usage(); return 0; }
+    if (!a.kv.count("reference") || !a.kv.count("query") || !a.kv.count("output")) {
+        fprintf(stderr, "error: the following required arguments were not provided:\n%s%s%s", a.kv.count("reference") ? "" : "  --reference <prefix>\n",
+                a.kv.count("query") ? "" : "  --query <prefix>\n", a.kv.count("output") ? "" : "  --output <file>\n");
+        return 2;
+    }
+    ScreenOptions opt;
+    if (a.kv.count("max-dist")) {
+        const std::string &v = a.kv["max-dist"];
+        char *e = nullptr;
+        const double d = v.empty() ? NAN : strtod(v.c_str(), &e);
+        if (!e || *e != 0 || !check_screen_max_dist(d).empty()) {
+            fprintf(stderr, "error: invalid value '%s' for --max-dist: %s\n", v.c_str(), check_screen_max_dist(NAN).c_str());
+            return 2;
+        }
+        opt.has_max_dist = true;
+        opt.max_dist = d;
+    }
+    uint64_t model = 1, threads = std::thread::hardware_concurrency(), dev = 0, block_rows = 0;
+    if (a.kv.count("model") && (!to_u64(a.kv["model"], model) || model > 1)) {
+        fprintf(stderr, "error: invalid value '%s' for --model: 0 or 1 is required\n", a.kv["model"].c_str());
+        return 2;
+    }
+    if (a.kv.count("block-rows") && !to_u64(a.kv["block-rows"], block_rows)) { fprintf(stderr, "error: invalid value for --block-rows\n"); return 2; }
+    if (a.kv.count("threads") && !to_u64(a.kv["threads"], threads)) { fprintf(stderr, "error: invalid value for --threads\n"); return 2; }
+    if (a.kv.count("device") && !to_u64(a.kv["device"], dev)) { fprintf(stderr, "error: invalid value for --device\n"); return 2; }
+    opt.side.ref_prefix = a.kv["reference"];
+    opt.side.query_prefix = a.kv["query"];
+    opt.output = a.kv["output"];
+    opt.keep_losers = a.flags.count("keep-losers") != 0;
+    opt.side.model = (int)model;
+    opt.side.block_rows = (uint32_t)std::min<uint64_t>(block_rows, 0xFFFFFFFFull);
+    opt.side.threads = (int)std::max<uint64_t>(1, threads);
+    opt.side.device = (int)dev;
+    opt.side.file_order = a.flags.count("file-order") != 0;
+    err = layout_from_option(a.kv.count("layout") ? a.kv["layout"] : "", opt.side.layout);
+    if (!err.empty()) { fprintf(stderr, "error: %s\n", err.c_str()); return 2; }
+    err = run_screen(opt);
+    if (!err.empty()) { fprintf(stderr, "Error: %s\n", err.c_str()); return 1; }
+    printf("Screen table written.\n");
+    return 0;
+}
+
 int cmd_hll_bias(int argc, char **argv)
 {
     Args a;
@@ -722,6 +801,7 @@ int main(int argc, char **argv)
     if (cmd == "growth") return cmd_growth(argc, argv);
     if (cmd == "merge") return cmd_merge(argc, argv);
     if (cmd == "spectrum") return cmd_spectrum(argc, argv);
+    if (cmd == "screen") return cmd_screen(argc, argv);
     if (cmd == "--version" || cmd == "-V") { printf("Genome Sketching via HyperLogLog, HyperMinhash and UltraLogLog %s\n", VERSION); return 0; }
     usage();
     return cmd == "--help" || cmd == "-h" || cmd == "help" ? 0 : 2;

@@ -252,7 +252,8 @@ void lash_ctx_destroy(lash_ctx *ctx)
     for (DevBuf *b : {&ctx->items, &ctx->item_begin, &ctx->item_kmers, &ctx->partials, &ctx->gregs, &ctx->counter, &ctx->st_seq, &ctx->st_rec,
                       &ctx->st_img, &ctx->hll_flags, &ctx->ec_ref, &ctx->ec_qry, &ctx->ec_x, &ctx->ec_card, &ctx->wf_scratch, &ctx->wf_out, &ctx->top_buf,
                       &ctx->fa_off, &ctx->fa_scratch, &ctx->fc_scratch, &ctx->kf_keep, &ctx->gu_members, &ctx->gu_tasks, &ctx->gu_part, &ctx->gu_hist,
-                      &ctx->gu_out, &ctx->gs_members, &ctx->gs_tasks, &ctx->gs_counts, &ctx->gs_union, &ctx->gs_hist})
+                      &ctx->gu_out, &ctx->gs_members, &ctx->gs_tasks, &ctx->gs_counts, &ctx->gs_union, &ctx->gs_hist,
+                      &ctx->sw_cand, &ctx->sw_tasks, &ctx->sw_winner, &ctx->sw_out})
         release(*b);
     {
         lash_packed &sc = ctx->scratch;

@@ -209,6 +209,8 @@ struct lash_ctx {
     DevBuf gs_members, gs_tasks, gs_counts, gs_union, gs_hist;   // lash_sketch_set_group_spectrum: the member list, a chunk's [tasks | bins of its
                                          // count tables], its count tables; gs_union: the union images when the caller takes none (and the
                                          // host-buffer entry's); gs_hist: the bins of the host-buffer entry
+    DevBuf sw_cand, sw_tasks, sw_winner, sw_out;   // lash_sketch_set_screen_wta: the candidate list, a chunk's [tasks | offsets | entry -> table], its
+                                         // winner tables; sw_out: [shared | won] of the host-buffer entry
     DevBuf hll_flags;                    // [hll_flags_n] per genome of the last HyperLogLog sketch call: a register > 53 - p
     uint32_t hll_flags_n = 0;            // (lash_ctx_hll_inexact_sums)
     bool hll_flags_on_host = false;      // the list below stands for the flags (hll_replay_sums has dealt with the others)

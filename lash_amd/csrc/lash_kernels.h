@@ -512,6 +512,36 @@ struct GroupSpectrumArgs {
 hipError_t launch_group_spectrum(const GroupSpectrumArgs &args, hipStream_t stream);
 hipError_t launch_group_spectrum_finish(const GroupSpectrumArgs &args, uint32_t n_tables, hipStream_t stream);
 
+// ---- winner-takes-all containment of HyperMinHash images (screen_wta.hip) -------------------------------------------
+// cand is the whole candidate list of a call (reference rows, every one < the reference set's size); a chunk is the queries
+// [q0, q0 + n) with the entries [e0, e0 + n_entries) of the list, cand_off[i] the first entry of query q0 + i (n + 1 offsets into cand)
+// and winner[i][16384] its winner table.  Task t walks cand[src_begin .. src_begin + count), the positions pos0 .. pos0 + count - 1 of
+// query `query`'s list, against that query's image and keeps, per register, the first position whose register equals the query's and
+// is not 0.  A list's only task (single != 0) stores the winners, SW_NONE where nobody holds; a task of a list cut into several takes
+// the minimum into the table, which is SW_NONE everywhere before the launch.  launch_screen_count, after it on the same stream: entry
+// e0 + e belongs to query q0 + pair_table[e]; out_shared[e0 + e] = the registers it holds, out_won[e0 + e] = those whose winner is its
+// position.  slices / lanes cut an image's 2048 units of eight registers as GroupUnionArgs' do; nothing depends on them: integer minima.
+constexpr uint32_t SW_NONE = 0xFFFFFFFFu;
+struct ScreenTask { uint64_t src_begin; uint32_t count; uint32_t query; uint32_t pos0; uint32_t table; uint32_t single; uint32_t pad; };
+struct ScreenWtaArgs {
+    const uint8_t    *ref;        // the reference set's images
+    uint64_t          ref_stride;
+    const uint8_t    *qry;        // the query set's images, registers in the same byte order
+    uint64_t          qry_stride;
+    uint32_t          ref_hdr, qry_hdr;
+    uint32_t          slices, lanes;
+    uint32_t          n_tasks, q0;
+    uint64_t          e0, n_entries;
+    const uint32_t   *cand;
+    const ScreenTask *tasks;
+    const uint64_t   *cand_off;
+    const uint32_t   *pair_table;
+    uint32_t         *winner;
+    uint32_t         *out_shared, *out_won;
+};
+hipError_t launch_screen_winner(const ScreenWtaArgs &args, hipStream_t stream);
+hipError_t launch_screen_count(const ScreenWtaArgs &args, hipStream_t stream);
+
 // ---- synthetic genomes --------------------------------------------------------------------
 hipError_t launch_synth(uint64_t first_genome, uint32_t n_genomes, uint64_t n_bases, uint8_t *d_out, hipStream_t stream);
 

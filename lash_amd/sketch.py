@@ -856,6 +856,40 @@ class SketchSet:
         bins = [hist[int(off[g]) + g:int(off[g + 1]) + g + 1] for g in range(len(groups))]
         return (bins, img) if union_images else bins
 
+    def screen_wta(self, qry, candidates, segment=None, slices=None, scratch_budget=None, device_out=None):
+        """`lash screen` (HyperMinHash sets; called on the reference set): candidates = one list per row of `qry` of rows of this set, best
+        first.  Reference i holds bucket b of a query iff the query's register there is not 0 and i's equals it; a bucket goes to the first
+        candidate of the list that holds it.  Returns (shared, won), each a list of uint32 arrays, one per query: shared[j][t] the buckets
+        position t of query j's list holds (the C of hmh_pair_counts), won[j][t] those it won (lash_sketch_set_screen_wta).  segment /
+        slices / scratch_budget: how the work is cut; the counts do not depend on them.  device_out = (two CUDA int32 / uint32 tensors of
+        sum(len(l)) words): both are written there, asynchronously on the context's stream, and device_out is returned.  LASH_EINVAL
+        raises a LashError (an hll / ull set; a bad row, whose position in the flattened lists is .index)."""
+        assert len(candidates) == qry.n
+        off, mem = self._groups_csr(candidates)
+        opts = _lib.GroupUnionOpts(int(segment or 0), int(slices or 0), int(scratch_budget or 0))
+        bad = C.c_uint64(2**64 - 1)
+        mp = mem.ctypes.data if mem.size else None
+        n = int(off[-1])
+        if device_out is None:
+            shared, won = np.zeros(n, dtype=np.uint32), np.zeros(n, dtype=np.uint32)
+            rc = self._lib.lash_sketch_set_screen_wta(self._ctx._h, self._h, qry._h, off.ctypes.data, mp, C.byref(opts),
+                                                      shared.ctypes.data if n else None, won.ctypes.data if n else None, C.byref(bad))
+        else:
+            d_shared, d_won = device_out
+            for d in device_out:
+                assert d.is_cuda and d.is_contiguous() and d.element_size() == 4 and d.numel() >= n
+            rc = self._lib.lash_sketch_set_screen_wta_device(self._ctx._h, self._h, qry._h, off.ctypes.data, mp, C.byref(opts),
+                                                             d_shared.data_ptr() if n else None, d_won.data_ptr() if n else None, C.byref(bad))
+        if rc != _lib.OK:
+            last = self._lib.lash_ctx_last_error(self._ctx._h)
+            e = LashError(rc, self._lib.lash_strerror(rc).decode() + (" " + last.decode() if last else ""))
+            e.index = bad.value
+            raise e
+        if device_out is not None:
+            return device_out
+        cut = [(int(off[j]), int(off[j + 1])) for j in range(len(candidates))]
+        return [shared[a:b] for a, b in cut], [won[a:b] for a, b in cut]
+
     def hmh_expected_collisions(self, r0, r1, qry=None, n_cols=None):
         """hyperminhash's expected collisions of the block's SMALL pairs (both sketches <= 2^19 distinct k-mers) as a float64
         [r1 - r0, n_cols] array for lash_dist_rows' hmh_ec (other entries are not read), or None when the block has none.
