@@ -1,34 +1,25 @@
-// main.cpp — `lash` command line for the gfx950 build: the flag surface of the reference's clap definition
-// (/root/reference/src/main.rs:26-177) on top of liblash_gfx950.so.
-//   lash sketch -f LIST [-o sketch] [-k 16] [-t N] [-a hmh|hll|ull] [-p 10] [-s 42]        (main.rs:30-96, 180-279)
-//   lash dist   -q PREFIX -r PREFIX [-o dist] [-t N] [-e fgra|ml] [-m 1|0] [--fp32] [--dm]   (main.rs:107-176, 280-617)
-//   lash growth -r PREFIX [-o growth] [--orders P] [--seed S] [--file-order] [-e fgra|ml] [-t N]   (not upstream: union cardinality along orderings)
-//   lash merge  -r PREFIX -o OUT (--groups FILE | --all NAME) [--keep-others] [--file-order] [-t N]   (not upstream: one sketch per group of sketches)
-//   lash spectrum -r PREFIX -o OUT [--groups FILE | --all NAME] [--core F] [--cloud F] [--curves] [--file-order] [-t N]   (not upstream: k-mer sharing spectrum of groups, hmh)
-//   lash screen -r DB -q SAMPLE -o FILE [--max-dist D] [--keep-losers] [-m 1|0] [--file-order] [--block-rows N] [-t N]   (not upstream: winner-takes-all containment of samples against a database, hmh)
-//   lash hll-bias -o FILE [-p P[,P...]] [--points N] [--trials T] [--seed S] [--device D]    (not upstream: HLL++ bias tables, simulated)
-// Extras that do not exist upstream: --gpus N / --device D / --devices LIST (which GPUs to use, one worker each), --batch-mb M, --stream-mb M (files
-// larger than M MiB are streamed in chunks with on-device accumulation), --hmh-x-low, --min-count M [--count-cells-log2 L] (drop the k-mers a
-// file holds fewer than M times, counted on the GPU), --window (one sketch per W-base window of every record), --translate (six-frame protein sketches of nucleotide FASTA, translated on the GPU), --per-record (one sketch per FASTA record, the records
-// found on the GPU); dist: --device D, --block-rows N, --hll-bias FILE / --hll-bias-sim (HLL++ bias tables from a file / simulated on the GPU),
-// --file-order (rows / columns in list-file order instead of the reference's seeded hash-map order), --max-dist D (print only
-// the pairs with distance <= D), --top K (only each name's K nearest), --cluster D (single-linkage clusters of an all-vs-all instead
-// of pairs), --derep D (greedy representatives of an all-vs-all in row order), --containment query|reference (the distance of the
-// containment fraction instead of the Jaccard-derived one; always a rectangle), --tree / --linkage average|single|complete (one Newick
-// tree of an all-vs-all, merged on the GPU; with --cluster D, that tree cut at D), --tree --nj (the neighbour-joining tree instead, joined on the GPU), --pcoa K (principal coordinates of an all-vs-all, solved on the GPU) (reference rows per GPU call); both: --layout SPEC (or $LASH_LAYOUT): the crate-internal rules as data, see `lash_layout`
-// in include/lash_gfx950.h.
+// main.cpp — the `lash` command line of the gfx950 build, on top of liblash_gfx950.so.  One function per command:
+//   sketch    FASTA/FASTQ files to sketches: the reference's flags (its src/main.rs:30-96, 180-279) and the GPU-side extras
+//   dist      distances between two sets of sketches (main.rs:107-176, 280-617) and the output forms built on them
+//   growth    union cardinality of a collection along orderings                           (not upstream)
+//   merge     one sketch per group of a collection's sketches                             (not upstream)
+//   spectrum  how the k-mers of each group's union are shared among its members, hmh      (not upstream)
+//   screen    winner-takes-all containment of samples against a database, hmh             (not upstream)
+//   hll-bias  the HLL++ bias tables `dist --hll-bias` reads, simulated                    (not upstream)
+// Every option is described once, in usage() below; --layout SPEC (or $LASH_LAYOUT) in include/lash_gfx950.h (`lash_layout`).
+// Each cmd_* is its option table, the checks that are its own, the assignments into its options struct, and the run; parsing,
+// the typed values and the checks several commands share are in cli_args.hpp.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
-#include <cstring>
-#include <map>
 #include <string>
 #include <thread>
 #include <vector>
 
 #include "../../../include/lash_gfx950.h"
+#include "cli_args.hpp"
 #include "dist.hpp"
 #include "growth.hpp"
 #include "merge.hpp"
@@ -41,11 +32,6 @@ using namespace lashhost;
 namespace {
 
 const char *VERSION = "0.1.4";      // main.rs:27 (hard-coded there although the crate is 0.1.6)
-
-struct Args {
-    std::map<std::string, std::string> kv;
-    std::map<std::string, bool> flags;
-};
 
 void usage()
 {
@@ -204,145 +190,103 @@ void usage()
             "      --device <D>             GPU to use [default: 0]\n");
 }
 
-bool parse(int argc, char **argv, int first, const std::map<std::string, std::string> &alias,
-           const std::vector<std::string> &bool_flags, Args &out, std::string &err)
-{
-    for (int i = first; i < argc; ++i) {
-        std::string a = argv[i];
-        std::string key, val;
-        bool has_val = false;
-        if (a.rfind("--", 0) == 0) {
-            size_t eq = a.find('=');
-            key = a.substr(2, eq == std::string::npos ? std::string::npos : eq - 2);
-            if (eq != std::string::npos) { val = a.substr(eq + 1); has_val = true; }
-        } else if (a.size() >= 2 && a[0] == '-') {
-            auto it = alias.find(a.substr(1, 1));
-            if (it == alias.end()) { err = "unexpected argument '" + a + "'"; return false; }
-            key = it->second;
-            if (a.size() > 2) { val = a.substr(2); has_val = true; }
-        } else { err = "unexpected argument '" + a + "'"; return false; }
-        bool is_flag = false;
-        for (auto &f : bool_flags) if (f == key) is_flag = true;
-        if (is_flag) { out.flags[key] = true; continue; }
-        if (!has_val) {
-            if (i + 1 >= argc) { err = "a value is required for '--" + key + "'"; return false; }
-            val = argv[++i];
-        }
-        out.kv[key] = val;
-    }
-    return true;
-}
+// sketch, dist and hll-bias take an unknown --name (and its value) in silence, as they always have: candidates to close separately
+const Command SKETCH = {{{"file", 'f', true}, {"output", 'o', true}, {"kmer", 'k', true}, {"threads", 't', true}, {"algorithm", 'a', true},
+                         {"precision", 'p', true}, {"seed", 's', true}, {"aa", 0, false}, {"per-record", 0, false}, {"window", 0, true},
+                         {"translate", 0, false}, {"min-count", 0, true}, {"count-cells-log2", 0, true}, {"gpus", 0, true}, {"device", 0, true},
+                         {"devices", 0, true}, {"batch-mb", 0, true}, {"stream-mb", 0, true}, {"hmh-x-low", 0, false}, {"layout", 0, true}}, false};
+const Command DIST = {{{"query", 'q', true}, {"reference", 'r', true}, {"output_file", 'o', true}, {"threads", 't', true}, {"estimator", 'e', true},
+                       {"model", 'm', true}, {"fp32", 0, false}, {"dm", 0, false}, {"file-order", 0, false}, {"max-dist", 0, true}, {"top", 0, true},
+                       {"cluster", 0, true}, {"derep", 0, true}, {"tree", 0, false}, {"linkage", 0, true}, {"nj", 0, false}, {"pcoa", 0, true},
+                       {"containment", 0, true}, {"hll-bias", 0, true}, {"hll-bias-sim", 0, false}, {"device", 0, true}, {"devices", 0, true},
+                       {"block-rows", 0, true}, {"layout", 0, true}}, false};
+const Command HLL_BIAS = {{{"output", 'o', true}, {"precision", 'p', true}, {"points", 0, true}, {"trials", 0, true}, {"seed", 0, true},
+                           {"device", 0, true}}, false};
+// one collection, one table: whatever else `dist` takes (-q, --dm, --top, ...) is not an option of these commands
+const Command GROWTH = {{{"reference", 'r', true}, {"output_file", 'o', true}, {"threads", 't', true}, {"estimator", 'e', true}, {"orders", 0, true},
+                         {"seed", 0, true}, {"file-order", 0, false}, {"hll-bias", 0, true}, {"hll-bias-sim", 0, false}, {"device", 0, true},
+                         {"layout", 0, true}}, true};
+const Command MERGE = {{{"reference", 'r', true}, {"output", 'o', true}, {"threads", 't', true}, {"groups", 0, true}, {"all", 0, true},
+                        {"keep-others", 0, false}, {"file-order", 0, false}, {"device", 0, true}, {"layout", 0, true}}, true};
+const Command SPECTRUM = {{{"reference", 'r', true}, {"output", 'o', true}, {"threads", 't', true}, {"groups", 0, true}, {"all", 0, true},
+                           {"core", 0, true}, {"cloud", 0, true}, {"curves", 0, false}, {"file-order", 0, false}, {"device", 0, true},
+                           {"layout", 0, true}}, true};
+const Command SCREEN = {{{"reference", 'r', true}, {"query", 'q', true}, {"output", 'o', true}, {"threads", 't', true}, {"model", 'm', true},
+                         {"max-dist", 0, true}, {"keep-losers", 0, false}, {"file-order", 0, false}, {"block-rows", 0, true}, {"device", 0, true},
+                         {"layout", 0, true}}, true};
 
-bool to_u64(const std::string &s, uint64_t &v)
+int panic(const char *what)                     // where the reference panics: its message, exit code 101
 {
-    if (s.empty()) return false;
-    char *e = nullptr;
-    v = strtoull(s.c_str(), &e, 10);
-    return e && *e == 0 && s[0] != '-';
+    fprintf(stderr, "%s\n", what);
+    return 101;
 }
 
 int cmd_sketch(int argc, char **argv)
 {
     Args a;
-    std::string err;
-    const std::map<std::string, std::string> alias = {{"f", "file"}, {"o", "output"}, {"k", "kmer"}, {"t", "threads"},
-                                                      {"a", "algorithm"}, {"p", "precision"}, {"s", "seed"}};
-    if (!parse(argc, argv, 2, alias, {"hmh-x-low", "aa", "per-record", "translate", "help"}, a, err)) { fprintf(stderr, "error: %s\n", err.c_str()); return 2; }
-    if (a.flags.count("help")) { usage(); return 0; }
-    if (!a.kv.count("file")) { fprintf(stderr, "error: the following required arguments were not provided:\n  --file <file>\n"); return 2; }
+    if (!a.parse(argc, argv, SKETCH)) return 2;
+    if (a.has("help")) { usage(); return 0; }
+    if (!a.require({{"file", "file"}})) return 2;
     SketchOptions opt;
-    const std::string output = a.kv.count("output") ? a.kv["output"] : "sketch";
-    const std::string alg = a.kv.count("algorithm") ? a.kv["algorithm"] : "hmh";
-    uint64_t k = 16, p = 10, seed = 42, threads = std::thread::hardware_concurrency(), gpus = 0, dev = 0, batch_mb = 64,
-             stream_mb = 1024;
-    if (a.kv.count("kmer") && !to_u64(a.kv["kmer"], k)) { fprintf(stderr, "error: invalid value for --kmer\n"); return 2; }
-    if (a.kv.count("precision") && !to_u64(a.kv["precision"], p)) { fprintf(stderr, "error: invalid value for --precision\n"); return 2; }
-    if (a.kv.count("seed") && !to_u64(a.kv["seed"], seed)) { fprintf(stderr, "error: invalid value for --seed\n"); return 2; }
-    if (a.kv.count("threads") && !to_u64(a.kv["threads"], threads)) { fprintf(stderr, "error: invalid value for --threads\n"); return 2; }
-    if (a.kv.count("gpus") && !to_u64(a.kv["gpus"], gpus)) { fprintf(stderr, "error: invalid value for --gpus\n"); return 2; }
-    if (a.kv.count("device") && !to_u64(a.kv["device"], dev)) { fprintf(stderr, "error: invalid value for --device\n"); return 2; }
-    if (a.kv.count("batch-mb") && !to_u64(a.kv["batch-mb"], batch_mb)) { fprintf(stderr, "error: invalid value for --batch-mb\n"); return 2; }
-    if (a.kv.count("stream-mb") && !to_u64(a.kv["stream-mb"], stream_mb)) { fprintf(stderr, "error: invalid value for --stream-mb\n"); return 2; }
-    if (alg == "hmh") opt.algo = LASH_HMH;
-    else if (alg == "hll") opt.algo = LASH_HLL;
-    else if (alg == "ull") opt.algo = LASH_ULL;
-    else { fprintf(stderr, "Algorithm must be either hmh, ull, or hll\n"); return 101; }      // main.rs:245 panic
-    if (k < 1 || k > 32) { fprintf(stderr, "k-mer length must be 1-32\n"); return 101; }       // utils.rs:501 panic
-    const bool amino = a.flags.count("aa") != 0;                                               // main.rs:97-104 (commented out there)
-    opt.per_record = a.flags.count("per-record") != 0;
-    opt.translate = a.flags.count("translate") != 0;
-    if (opt.translate && amino) { fprintf(stderr, "error: --translate cannot be used with --aa (--translate takes nucleotide input and makes the proteins itself)\n"); return 2; }
-    if (opt.translate && a.kv.count("min-count")) { fprintf(stderr, "error: --translate cannot be used with --min-count (k-mers are counted for nucleotide sketches only)\n"); return 2; }
-    if (opt.translate && a.kv.count("window")) { fprintf(stderr, "error: --translate cannot be used with --window (windows of translated records are not supported)\n"); return 2; }
-    if (a.kv.count("window")) {
-        uint64_t w = 0;
-        if (!to_u64(a.kv["window"], w) || w < 1) {
-            fprintf(stderr, "error: invalid value '%s' for --window: a positive integer is required\n", a.kv["window"].c_str());
-            return 2;
-        }
-        if (amino) { fprintf(stderr, "error: --window cannot be used with --aa (windows are cut for nucleotide FASTA only)\n"); return 2; }
-        if (w < k) { fprintf(stderr, "error: --window %llu is shorter than -k %llu: no window would hold a k-mer\n", (unsigned long long)w, (unsigned long long)k); return 2; }
-        if (a.kv.count("min-count")) { fprintf(stderr, "error: --window cannot be used with --min-count (k-mers are counted per file)\n"); return 2; }
-        opt.window = w;
-    }
-    if (opt.translate && k > 12) { fprintf(stderr, "k-mer length for amino acid must be 1\xe2\x80\x93" "12\n"); return 101; }   // the --aa message
-    if (opt.per_record && amino) { fprintf(stderr, "error: --per-record cannot be used with --aa (records are split for nucleotide FASTA only)\n"); return 2; }
-    if (amino && k > 12) { fprintf(stderr, "k-mer length for amino acid must be 1\xe2\x80\x93" "12\n"); return 101; }   // utils.rs:554 panic
-    if (a.kv.count("count-cells-log2") && !a.kv.count("min-count")) { fprintf(stderr, "error: --count-cells-log2 needs --min-count\n"); return 2; }
-    if (a.kv.count("min-count")) {
-        uint64_t m = 0, l2 = 0;
-        if (!to_u64(a.kv["min-count"], m) || m < 1 || m > 255) {
-            fprintf(stderr, "error: invalid value '%s' for --min-count: an integer from 1 to 255 is required\n", a.kv["min-count"].c_str());
-            return 2;
-        }
-        if (a.kv.count("count-cells-log2") && (!to_u64(a.kv["count-cells-log2"], l2) || l2 < 10 || l2 > 36)) {
-            fprintf(stderr, "error: invalid value '%s' for --count-cells-log2: an integer from 10 to 36 is required\n", a.kv["count-cells-log2"].c_str());
-            return 2;
-        }
-        if (amino) { fprintf(stderr, "error: --min-count cannot be used with --aa (k-mers are counted for nucleotide input only)\n"); return 2; }
-        if (opt.per_record) { fprintf(stderr, "error: --min-count cannot be used with --per-record (k-mers are counted per file)\n"); return 2; }
-        // the filtered launch exists where the sketch's registers are a plain table in LDS (include/lash_gfx950.h)
-        const uint64_t max_p = opt.algo == LASH_HLL ? 15 : 14;
-        if (opt.algo != LASH_HMH && p > max_p) {
-            fprintf(stderr, "error: --min-count supports -a %s up to -p %llu (and -a hmh); -p %llu is not supported\n", alg.c_str(),
-                    (unsigned long long)max_p, (unsigned long long)p);
-            return 2;
-        }
-        opt.min_count = (uint32_t)m;
-        opt.count_cells_log2 = (int)l2;
-    }
+    const std::string output = a.str("output", "sketch"), alg = a.str("algorithm", "hmh");
+    uint64_t k = 16, p = 10, seed = 42, threads = std::thread::hardware_concurrency(), gpus = 0, dev = 0, batch_mb = 64, stream_mb = 1024,
+             w = 0, m = 0, l2 = 0;
+    if (!a.u64("kmer", k) || !a.u64("precision", p) || !a.u64("seed", seed) || !a.u64("threads", threads) || !a.u64("gpus", gpus) ||
+        !a.u64("device", dev) || !a.u64("batch-mb", batch_mb) || !a.u64("stream-mb", stream_mb))
+        return 2;
+    static_assert(LASH_HMH == 0 && LASH_HLL == 1 && LASH_ULL == 2, "the place in the word list is the algorithm");
+    if (!a.choice("algorithm", {"hmh", "hll", "ull"}, opt.algo, nullptr)) return panic("Algorithm must be either hmh, ull, or hll");   // main.rs:245
+    if (k < 1 || k > 32) return panic("k-mer length must be 1-32");                                                                      // utils.rs:501
+    const char *amino_k = "k-mer length for amino acid must be 1\xe2\x80\x93" "12";                                                      // utils.rs:554
+    const bool amino = a.has("aa");                                                            // main.rs:97-104 (commented out there)
+    opt.per_record = a.has("per-record");
+    opt.translate = a.has("translate");
+    if (!a.allowed("translate", {{"aa", "--translate takes nucleotide input and makes the proteins itself"},
+                                 {"min-count", "k-mers are counted for nucleotide sketches only"},
+                                 {"window", "windows of translated records are not supported"}}))
+        return 2;
+    if (!a.u64("window", w, 1, UINT64_MAX, "a positive integer is required") ||
+        !a.allowed("window", {{"aa", "windows are cut for nucleotide FASTA only"},
+                              {nullptr, std::to_string(w) + " is shorter than -k " + std::to_string(k) + ": no window would hold a k-mer", w < k},
+                              {"min-count", "k-mers are counted per file"}}))
+        return 2;
+    if (opt.translate && k > 12) return panic(amino_k);                                        // the --aa message
+    if (!a.allowed("per-record", {{"aa", "records are split for nucleotide FASTA only"}})) return 2;
+    if (amino && k > 12) return panic(amino_k);
+    if (!a.allowed("count-cells-log2", {{nullptr, "needs --min-count", !a.has("min-count")}})) return 2;
+    // the filtered launch exists where the sketch's registers are a plain table in LDS (include/lash_gfx950.h)
+    const uint64_t max_p = opt.algo == LASH_HLL ? 15 : 14;
+    if (!a.u64("min-count", m, 1, 255, "an integer from 1 to 255 is required") ||
+        !a.u64("count-cells-log2", l2, 10, 36, "an integer from 10 to 36 is required") ||
+        !a.allowed("min-count", {{"aa", "k-mers are counted for nucleotide input only"},
+                                 {"per-record", "k-mers are counted per file"},
+                                 {nullptr, "supports -a " + alg + " up to -p " + std::to_string(max_p) + " (and -a hmh); -p " + std::to_string(p) +
+                                           " is not supported", opt.algo != LASH_HMH && p > max_p}}))
+        return 2;
+    opt.window = w;
+    opt.min_count = (uint32_t)m;
+    opt.count_cells_log2 = (int)l2;
     opt.k = (int)k;
     opt.precision = (int)p;
     opt.seed = seed;
     opt.threads = (int)std::max<uint64_t>(1, threads);
     opt.batch_bytes = std::max<uint64_t>(1, batch_mb) << 20;
     opt.stream_bytes = std::max<uint64_t>(1, stream_mb) << 20;
-    opt.flags = (a.flags.count("hmh-x-low") ? LASH_F_HMH_X_LOW : 0) | (amino || opt.translate ? LASH_F_AMINO : 0);
-    err = layout_from_option(a.kv.count("layout") ? a.kv["layout"] : "", opt.layout);
-    if (!err.empty()) { fprintf(stderr, "error: %s\n", err.c_str()); return 2; }
-    if (a.kv.count("devices")) {                              // explicit worker list, e.g. 0,1,2,3 (repeats allowed: 0,0 = two workers on GPU 0)
-        const std::string &l = a.kv["devices"];
-        size_t at = 0;
-        while (at <= l.size()) {
-            const size_t c = l.find(',', at);
-            uint64_t d = 0;
-            if (!to_u64(l.substr(at, c == std::string::npos ? std::string::npos : c - at), d)) { fprintf(stderr, "error: invalid value for --devices\n"); return 2; }
-            opt.devices.push_back((int)d);
-            if (c == std::string::npos) break;
-            at = c + 1;
-        }
-    } else if (gpus > 0) for (uint64_t d = 0; d < gpus; ++d) opt.devices.push_back((int)d);
-    else opt.devices.push_back((int)dev);
+    opt.flags = (a.has("hmh-x-low") ? LASH_F_HMH_X_LOW : 0) | (amino || opt.translate ? LASH_F_AMINO : 0);
+    if (!layout_option(a, opt.layout) || !devices_option(a, opt.devices)) return 2;   // --devices: the workers, e.g. 0,1,2,3 (0,0 = two on GPU 0)
+    if (!a.has("devices")) {
+        if (gpus > 0) for (uint64_t d = 0; d < gpus; ++d) opt.devices.push_back((int)d);
+        else opt.devices.push_back((int)dev);
+    }
 
     std::vector<std::string> files;
-    err = read_list_file(a.kv["file"], files);
-    if (!err.empty()) { fprintf(stderr, "Error: %s\n", err.c_str()); return 1; }
+    std::string err = read_list_file(a.str("file"), files);
+    if (!err.empty()) return finish(err, "");
     SketchStats st;
     err = sketch_files(opt, files, output, &st);
     if (opt.window && err.rfind("--window takes FASTA input", 0) == 0) { fprintf(stderr, "error: %s\n", err.c_str()); return 2; }   // a refusal of the flag
-    if (!err.empty()) { fprintf(stderr, "Error: %s\n", err.c_str()); return 1; }
-    err = write_parameters_json(output, alg, opt.k, opt.precision, opt.seed, amino || opt.translate);
-    if (!err.empty()) { fprintf(stderr, "Error: %s\n", err.c_str()); return 1; }
+    if (err.empty()) err = write_parameters_json(output, alg, opt.k, opt.precision, opt.seed, amino || opt.translate);
+    if (!err.empty()) return finish(err, "");
     if (opt.window)
         fprintf(stderr, "sketched %llu windows of %llu files (%.3f GB of FASTA text) in %.2f s on %zu GPU(s), %llu batches\n",
                 (unsigned long long)st.records, (unsigned long long)st.files, st.bytes / 1e9, st.seconds, opt.devices.size(),
@@ -366,417 +310,191 @@ std::string prefix_stem(const std::string &prefix)
     return stem;
 }
 
+// The output forms of dist stand in the order they were added; each names the earlier ones it cannot go with, so a new form is one
+// more block at the end: its value, its rules (the first that hits is the refusal), its field of DistOptions.
 int cmd_dist(int argc, char **argv)
 {
     Args a;
-    std::string err;
-    const std::map<std::string, std::string> alias = {{"q", "query"}, {"r", "reference"}, {"o", "output_file"}, {"t", "threads"},
-                                                      {"e", "estimator"}, {"m", "model"}};
-    if (!parse(argc, argv, 2, alias, {"fp32", "dm", "file-order", "hll-bias-sim", "tree", "nj", "help"}, a, err)) { fprintf(stderr, "error: %s\n", err.c_str()); return 2; }
-    if (a.flags.count("help")) { usage(); return 0; }
-    if (!a.kv.count("query") || !a.kv.count("reference")) {
-        fprintf(stderr, "error: the following required arguments were not provided:\n  --query <query>\n  --reference <reference>\n");
-        return 2;
-    }
+    if (!a.parse(argc, argv, DIST)) return 2;
+    if (a.has("help")) { usage(); return 0; }
+    if (!a.require({{"query", "query"}, {"reference", "reference"}}, true)) return 2;
     DistOptions opt;
-    opt.query_prefix = a.kv["query"];
-    opt.ref_prefix = a.kv["reference"];
-    opt.output_file = a.kv.count("output_file") ? a.kv["output_file"] : "dist";
-    opt.estimator = a.kv.count("estimator") ? a.kv["estimator"] : "fgra";
-    uint64_t model = 1, threads = std::thread::hardware_concurrency(), dev = 0, block_rows = 0;
-    if (a.kv.count("block-rows") && !to_u64(a.kv["block-rows"], block_rows)) { fprintf(stderr, "error: invalid value for --block-rows\n"); return 2; }
-    opt.block_rows = (uint32_t)std::min<uint64_t>(block_rows, 0xFFFFFFFFull);
-    if (a.kv.count("model") && !to_u64(a.kv["model"], model)) { fprintf(stderr, "error: invalid value for --model\n"); return 2; }
-    if (a.kv.count("threads") && !to_u64(a.kv["threads"], threads)) { fprintf(stderr, "error: invalid value for --threads\n"); return 2; }
-    if (a.kv.count("device") && !to_u64(a.kv["device"], dev)) { fprintf(stderr, "error: invalid value for --device\n"); return 2; }
-    opt.model = (int)model;
-    opt.threads = (int)std::max<uint64_t>(1, threads);
-    opt.fp32 = a.flags.count("fp32") != 0;
-    opt.matrix = a.flags.count("dm") != 0;
-    opt.file_order = a.flags.count("file-order") != 0;
-    opt.hll_bias_sim = a.flags.count("hll-bias-sim") != 0;
-    if (opt.hll_bias_sim && a.kv.count("hll-bias")) {
-        fprintf(stderr, "error: --hll-bias-sim cannot be used with --hll-bias (simulate the tables or read them from a file, not both)\n");
+    opt.query_prefix = a.str("query");
+    opt.ref_prefix = a.str("reference");
+    opt.output_file = a.str("output_file", "dist");
+    opt.estimator = a.str("estimator", "fgra");
+    uint64_t model = 1, block_rows = 0, top = 0, pcoa = 0;
+    int contain = 0;
+    if (!a.u64("block-rows", block_rows) || !a.u64("model", model) || !threads_device_order(a, opt) || !bias_source(a, opt) ||
+        !devices_option(a, opt.devices))
         return 2;
-    }
-    if (a.kv.count("hll-bias")) opt.hll_bias_file = a.kv["hll-bias"];
-    else if (const char *e = opt.hll_bias_sim ? nullptr : getenv("LASH_HLL_BIAS")) opt.hll_bias_file = e;
-    opt.device = (int)dev;
-    if (a.kv.count("devices")) {
-        const std::string &l = a.kv["devices"];
-        size_t at = 0;
-        while (at <= l.size()) {
-            const size_t c = l.find(',', at);
-            uint64_t d = 0;
-            if (!to_u64(l.substr(at, c == std::string::npos ? std::string::npos : c - at), d)) { fprintf(stderr, "error: invalid value for --devices\n"); return 2; }
-            opt.devices.push_back((int)d);
-            if (c == std::string::npos) break;
-            at = c + 1;
-        }
-    }
-    if (a.kv.count("max-dist")) {
-        const std::string &v = a.kv["max-dist"];
-        char *e = nullptr;
-        const double d = v.empty() ? NAN : strtod(v.c_str(), &e);
-        if (!e || *e != 0 || !std::isfinite(d)) { fprintf(stderr, "error: invalid value '%s' for --max-dist: a finite number is required\n", v.c_str()); return 2; }
-        if (opt.matrix) { fprintf(stderr, "error: --max-dist cannot be used with --dm (a square matrix cannot drop cells)\n"); return 2; }
-        opt.has_max_dist = true;
-        opt.max_dist = d;
-    }
-    if (a.kv.count("top")) {
-        const std::string &v = a.kv["top"];
-        uint64_t n = 0;
-        if (!to_u64(v, n) || n < 1 || n > LASH_TOP_MAX) {
-            fprintf(stderr, "error: invalid value '%s' for --top: an integer from 1 to %u is required\n", v.c_str(), LASH_TOP_MAX);
-            return 2;
-        }
-        if (opt.matrix) { fprintf(stderr, "error: --top cannot be used with --dm (a square matrix cannot drop cells)\n"); return 2; }
-        opt.top = (uint32_t)n;
-    }
-    if (a.kv.count("cluster")) {
-        const std::string &v = a.kv["cluster"];
-        char *e = nullptr;
-        const double d = v.empty() ? NAN : strtod(v.c_str(), &e);
-        if (!e || *e != 0 || !std::isfinite(d)) { fprintf(stderr, "error: invalid value '%s' for --cluster: a finite number is required\n", v.c_str()); return 2; }
-        if (opt.matrix) { fprintf(stderr, "error: --cluster cannot be used with --dm (clusters are not a matrix)\n"); return 2; }
-        if (opt.top) { fprintf(stderr, "error: --cluster cannot be used with --top (it prints clusters, not pairs)\n"); return 2; }
-        if (opt.has_max_dist) { fprintf(stderr, "error: --cluster cannot be used with --max-dist (--cluster D is its own cutoff)\n"); return 2; }
-        opt.has_cluster = true;
-        opt.cluster_dist = d;
-    }
-    if (a.kv.count("derep")) {
-        const std::string &v = a.kv["derep"];
-        char *e = nullptr;
-        const double d = v.empty() ? NAN : strtod(v.c_str(), &e);
-        if (!e || *e != 0 || !std::isfinite(d)) { fprintf(stderr, "error: invalid value '%s' for --derep: a finite number is required\n", v.c_str()); return 2; }
-        if (opt.matrix) { fprintf(stderr, "error: --derep cannot be used with --dm (representatives are not a matrix)\n"); return 2; }
-        if (opt.top) { fprintf(stderr, "error: --derep cannot be used with --top (it prints representatives, not pairs)\n"); return 2; }
-        if (opt.has_max_dist) { fprintf(stderr, "error: --derep cannot be used with --max-dist (--derep D is its own cutoff)\n"); return 2; }
-        if (opt.has_cluster) { fprintf(stderr, "error: --derep cannot be used with --cluster (greedy representatives or single-linkage clusters, not both)\n"); return 2; }
-        if (opt.devices.size() > 1) {
-            fprintf(stderr, "error: --derep cannot be used with more than one entry in --devices: a block of rows is decided from the "
-                            "representatives of the blocks before it, so the blocks run in row order on one worker\n");
-            return 2;
-        }
-        opt.has_derep = true;
-        opt.derep_dist = d;
-    }
-    if (a.kv.count("containment")) {
-        const std::string &v = a.kv["containment"];
-        if (v == "query") opt.measure = LASH_MEASURE_CONTAIN_QUERY;
-        else if (v == "reference") opt.measure = LASH_MEASURE_CONTAIN_REFERENCE;
-        else { fprintf(stderr, "error: invalid value '%s' for --containment: query or reference is required\n", v.c_str()); return 2; }
-        if (opt.matrix) { fprintf(stderr, "error: --containment cannot be used with --dm (list form only)\n"); return 2; }
-        if (opt.has_cluster) { fprintf(stderr, "error: --containment cannot be used with --cluster (clusters need a symmetric distance)\n"); return 2; }
-        if (opt.has_derep) { fprintf(stderr, "error: --containment cannot be used with --derep (representatives need a symmetric distance)\n"); return 2; }
-    }
-    if (a.flags.count("tree")) {
-        if (opt.matrix) { fprintf(stderr, "error: --tree cannot be used with --dm (a tree is not a matrix)\n"); return 2; }
-        if (opt.top) { fprintf(stderr, "error: --tree cannot be used with --top (a tree needs every pair)\n"); return 2; }
-        if (opt.has_max_dist) { fprintf(stderr, "error: --tree cannot be used with --max-dist (a tree needs every pair)\n"); return 2; }
-        if (opt.has_cluster) { fprintf(stderr, "error: --tree cannot be used with --cluster (the whole tree or its cut at D, not both)\n"); return 2; }
-        if (opt.has_derep) { fprintf(stderr, "error: --tree cannot be used with --derep (a tree or greedy representatives, not both)\n"); return 2; }
-        if (opt.measure != LASH_MEASURE_JACCARD) { fprintf(stderr, "error: --tree cannot be used with --containment (a tree needs a symmetric distance)\n"); return 2; }
-        if (prefix_stem(opt.query_prefix) != prefix_stem(opt.ref_prefix)) {
-            fprintf(stderr, "error: --tree needs an all-vs-all run: -q and -r must name the same sketch files\n");
-            return 2;
-        }
-        opt.tree = true;
-    }
-    if (a.kv.count("linkage")) {
-        const std::string &v = a.kv["linkage"];
-        if (v == "average") opt.linkage = LASH_LINKAGE_AVERAGE;
-        else if (v == "single") opt.linkage = LASH_LINKAGE_SINGLE;
-        else if (v == "complete") opt.linkage = LASH_LINKAGE_COMPLETE;
-        else { fprintf(stderr, "error: invalid value '%s' for --linkage: average, single or complete is required\n", v.c_str()); return 2; }
-        if (!opt.tree && !opt.has_cluster) { fprintf(stderr, "error: --linkage needs --tree or --cluster (it says how their clusters are merged)\n"); return 2; }
-    }
-    if (a.flags.count("nj")) {
-        if (opt.has_cluster) { fprintf(stderr, "error: --nj cannot be used with --cluster (a neighbour-joining tree has no heights to cut)\n"); return 2; }
-        if (opt.linkage >= 0) { fprintf(stderr, "error: --nj cannot be used with --linkage (neighbour joining is a rule of its own, not a linkage)\n"); return 2; }
-        if (!opt.tree) { fprintf(stderr, "error: --nj needs --tree (it says which tree --tree writes)\n"); return 2; }
-        opt.nj = true;
-    }
-    if (a.kv.count("pcoa")) {
-        const std::string &v = a.kv["pcoa"];
-        uint64_t n = 0;
-        if (!to_u64(v, n) || n < 1 || n > 16) { fprintf(stderr, "error: invalid value '%s' for --pcoa: an integer from 1 to 16 is required\n", v.c_str()); return 2; }
-        if (opt.matrix) { fprintf(stderr, "error: --pcoa cannot be used with --dm (coordinates are not a matrix of distances)\n"); return 2; }
-        if (opt.top) { fprintf(stderr, "error: --pcoa cannot be used with --top (principal coordinates need every pair)\n"); return 2; }
-        if (opt.has_max_dist) { fprintf(stderr, "error: --pcoa cannot be used with --max-dist (principal coordinates need every pair)\n"); return 2; }
-        if (opt.has_cluster) { fprintf(stderr, "error: --pcoa cannot be used with --cluster (coordinates or clusters, not both)\n"); return 2; }
-        if (opt.has_derep) { fprintf(stderr, "error: --pcoa cannot be used with --derep (coordinates or greedy representatives, not both)\n"); return 2; }
-        if (opt.measure != LASH_MEASURE_JACCARD) { fprintf(stderr, "error: --pcoa cannot be used with --containment (principal coordinates need a symmetric distance)\n"); return 2; }
-        if (opt.tree) { fprintf(stderr, "error: --pcoa cannot be used with --tree (coordinates or a tree, not both)\n"); return 2; }
-        if (opt.nj) { fprintf(stderr, "error: --pcoa cannot be used with --nj (coordinates or a tree, not both)\n"); return 2; }
-        if (opt.linkage >= 0) { fprintf(stderr, "error: --pcoa cannot be used with --linkage (principal coordinates merge no clusters)\n"); return 2; }
-        if (prefix_stem(opt.query_prefix) != prefix_stem(opt.ref_prefix)) {
-            fprintf(stderr, "error: --pcoa needs an all-vs-all run: -q and -r must name the same sketch files\n");
-            return 2;
-        }
-        opt.pcoa = (uint32_t)n;
-    }
-    err = layout_from_option(a.kv.count("layout") ? a.kv["layout"] : "", opt.layout);
-    if (!err.empty()) { fprintf(stderr, "error: %s\n", err.c_str()); return 2; }
-    err = run_dist(opt);
-    if (!err.empty()) { fprintf(stderr, "Error: %s\n", err.c_str()); return 1; }
-    printf("Distances computed.\n");                                                          // main.rs:615
-    return 0;
+    opt.block_rows = (uint32_t)std::min<uint64_t>(block_rows, 0xFFFFFFFFull);
+    opt.model = (int)model;
+    opt.fp32 = a.has("fp32");
+    opt.matrix = a.has("dm");
+    const Rule all_vs_all = {nullptr, "needs an all-vs-all run: -q and -r must name the same sketch files",
+                             prefix_stem(opt.query_prefix) != prefix_stem(opt.ref_prefix)};
+    if (!a.real("max-dist", opt.max_dist) || !a.allowed("max-dist", {{"dm", "a square matrix cannot drop cells"}})) return 2;
+    if (!a.u64("top", top, 1, LASH_TOP_MAX, "an integer from 1 to " + std::to_string(LASH_TOP_MAX) + " is required") ||
+        !a.allowed("top", {{"dm", "a square matrix cannot drop cells"}}))
+        return 2;
+    if (!a.real("cluster", opt.cluster_dist) ||
+        !a.allowed("cluster", {{"dm", "clusters are not a matrix"},
+                               {"top", "it prints clusters, not pairs"},
+                               {"max-dist", "--cluster D is its own cutoff"}}))
+        return 2;
+    if (!a.real("derep", opt.derep_dist) ||
+        !a.allowed("derep", {{"dm", "representatives are not a matrix"},
+                             {"top", "it prints representatives, not pairs"},
+                             {"max-dist", "--derep D is its own cutoff"},
+                             {"cluster", "greedy representatives or single-linkage clusters, not both"},
+                             {nullptr, "cannot be used with more than one entry in --devices: a block of rows is decided from the "
+                                       "representatives of the blocks before it, so the blocks run in row order on one worker", opt.devices.size() > 1}}))
+        return 2;
+    if (!a.choice("containment", {"query", "reference"}, contain, "query or reference is required") ||
+        !a.allowed("containment", {{"dm", "list form only"},
+                                   {"cluster", "clusters need a symmetric distance"},
+                                   {"derep", "representatives need a symmetric distance"}}))
+        return 2;
+    if (!a.allowed("tree", {{"dm", "a tree is not a matrix"},
+                            {"top", "a tree needs every pair"},
+                            {"max-dist", "a tree needs every pair"},
+                            {"cluster", "the whole tree or its cut at D, not both"},
+                            {"derep", "a tree or greedy representatives, not both"},
+                            {"containment", "a tree needs a symmetric distance"},
+                            all_vs_all}))
+        return 2;
+    static_assert(LASH_LINKAGE_AVERAGE == 0 && LASH_LINKAGE_SINGLE == 1 && LASH_LINKAGE_COMPLETE == 2, "the place in the word list is the linkage");
+    if (!a.choice("linkage", {"average", "single", "complete"}, opt.linkage, "average, single or complete is required") ||
+        !a.allowed("linkage", {{nullptr, "needs --tree or --cluster (it says how their clusters are merged)", !a.has("tree") && !a.has("cluster")}}))
+        return 2;
+    if (!a.allowed("nj", {{"cluster", "a neighbour-joining tree has no heights to cut"},
+                          {"linkage", "neighbour joining is a rule of its own, not a linkage"},
+                          {nullptr, "needs --tree (it says which tree --tree writes)", !a.has("tree")}}))
+        return 2;
+    if (!a.u64("pcoa", pcoa, 1, 16, "an integer from 1 to 16 is required") ||
+        !a.allowed("pcoa", {{"dm", "coordinates are not a matrix of distances"},
+                            {"top", "principal coordinates need every pair"},
+                            {"max-dist", "principal coordinates need every pair"},
+                            {"cluster", "coordinates or clusters, not both"},
+                            {"derep", "coordinates or greedy representatives, not both"},
+                            {"containment", "principal coordinates need a symmetric distance"},
+                            {"tree", "coordinates or a tree, not both"},
+                            {"nj", "coordinates or a tree, not both"},
+                            {"linkage", "principal coordinates merge no clusters"},
+                            all_vs_all}))
+        return 2;
+    opt.has_max_dist = a.has("max-dist");
+    opt.top = (uint32_t)top;
+    opt.has_cluster = a.has("cluster");
+    opt.has_derep = a.has("derep");
+    if (a.has("containment")) opt.measure = contain == 0 ? LASH_MEASURE_CONTAIN_QUERY : LASH_MEASURE_CONTAIN_REFERENCE;
+    opt.tree = a.has("tree");
+    opt.nj = a.has("nj");
+    opt.pcoa = (uint32_t)pcoa;
+    if (!layout_option(a, opt.layout)) return 2;
+    return finish(run_dist(opt), "Distances computed.\n");                                    // main.rs:615
 }
 
-// lash growth -r PREFIX [-o growth] [--orders P] [--seed S] [--file-order] [-e fgra|ml] [-t N] [--hll-bias FILE | --hll-bias-sim] [--device D]
 int cmd_growth(int argc, char **argv)
 {
     Args a;
-    std::string err;
-    const std::map<std::string, std::string> alias = {{"r", "reference"}, {"o", "output_file"}, {"t", "threads"}, {"e", "estimator"}};
-    // one collection, one table: whatever else `dist` takes (-q, --dm, --top, ...) is not an option of this command
-    const std::vector<std::string> known = {"reference", "output_file", "threads", "estimator", "orders", "seed", "file-order", "hll-bias",
-                                            "hll-bias-sim", "device", "layout", "help"};
-    for (int i = 2; i < argc; ++i) {
-        const std::string s = argv[i];
-        if (s.rfind("--", 0) != 0) continue;
-        const std::string key = s.substr(2, s.find('=') == std::string::npos ? std::string::npos : s.find('=') - 2);
-        if (std::find(known.begin(), known.end(), key) == known.end()) { fprintf(stderr, "error: unexpected argument '--%s'\n", key.c_str()); return 2; }
-    }
-    if (!parse(argc, argv, 2, alias, {"file-order", "hll-bias-sim", "help"}, a, err)) { fprintf(stderr, "error: %s\n", err.c_str()); return 2; }
-    if (a.flags.count("help")) { usage(); return 0; }
-    if (!a.kv.count("reference")) { fprintf(stderr, "error: the following required arguments were not provided:\n  --reference <reference>\n"); return 2; }
+    if (!a.parse(argc, argv, GROWTH)) return 2;
+    if (a.has("help")) { usage(); return 0; }
+    if (!a.require({{"reference", "reference"}})) return 2;
     GrowthOptions opt;
-    opt.side.ref_prefix = opt.side.query_prefix = a.kv["reference"];
-    opt.output_file = a.kv.count("output_file") ? a.kv["output_file"] : "growth";
-    opt.side.estimator = a.kv.count("estimator") ? a.kv["estimator"] : "fgra";
-    if (opt.side.estimator != "fgra" && opt.side.estimator != "ml") {
-        fprintf(stderr, "error: invalid value '%s' for --estimator: fgra or ml is required\n", opt.side.estimator.c_str());
+    opt.side.ref_prefix = opt.side.query_prefix = a.str("reference");
+    opt.output_file = a.str("output_file", "growth");
+    opt.side.estimator = a.str("estimator", "fgra");
+    uint64_t orders = 1;
+    int estimator = 0;
+    if (!a.choice("estimator", {"fgra", "ml"}, estimator, "fgra or ml is required") ||
+        !a.u64("orders", orders, 1, 0xFFFFFFFFull, "a positive integer is required") || !a.u64("seed", opt.seed) ||
+        !threads_device_order(a, opt.side) || !bias_source(a, opt.side) || !layout_option(a, opt.side.layout))
         return 2;
-    }
-    uint64_t orders = 1, threads = std::thread::hardware_concurrency(), dev = 0;
-    if (a.kv.count("orders") && (!to_u64(a.kv["orders"], orders) || orders < 1 || orders > 0xFFFFFFFFull)) {
-        fprintf(stderr, "error: invalid value '%s' for --orders: a positive integer is required\n", a.kv["orders"].c_str());
-        return 2;
-    }
-    if (a.kv.count("seed") && !to_u64(a.kv["seed"], opt.seed)) { fprintf(stderr, "error: invalid value for --seed\n"); return 2; }
-    if (a.kv.count("threads") && !to_u64(a.kv["threads"], threads)) { fprintf(stderr, "error: invalid value for --threads\n"); return 2; }
-    if (a.kv.count("device") && !to_u64(a.kv["device"], dev)) { fprintf(stderr, "error: invalid value for --device\n"); return 2; }
     opt.orders = (uint32_t)orders;
-    opt.side.threads = (int)std::max<uint64_t>(1, threads);
-    opt.side.device = (int)dev;
-    opt.side.file_order = a.flags.count("file-order") != 0;
-    opt.side.hll_bias_sim = a.flags.count("hll-bias-sim") != 0;
-    if (opt.side.hll_bias_sim && a.kv.count("hll-bias")) {
-        fprintf(stderr, "error: --hll-bias-sim cannot be used with --hll-bias (simulate the tables or read them from a file, not both)\n");
-        return 2;
-    }
-    if (a.kv.count("hll-bias")) opt.side.hll_bias_file = a.kv["hll-bias"];
-    else if (const char *e = opt.side.hll_bias_sim ? nullptr : getenv("LASH_HLL_BIAS")) opt.side.hll_bias_file = e;
-    err = layout_from_option(a.kv.count("layout") ? a.kv["layout"] : "", opt.side.layout);
-    if (!err.empty()) { fprintf(stderr, "error: %s\n", err.c_str()); return 2; }
-    err = run_growth(opt);
-    if (!err.empty()) { fprintf(stderr, "Error: %s\n", err.c_str()); return 1; }
-    printf("Growth table written.\n");
-    return 0;
+    return finish(run_growth(opt), "Growth table written.\n");
 }
 
-// lash merge -r PREFIX -o OUT (--groups FILE | --all NAME) [--keep-others] [--file-order] [--device D] [--layout SPEC] [-t N]
 int cmd_merge(int argc, char **argv)
 {
     Args a;
-    std::string err;
-    const std::map<std::string, std::string> alias = {{"r", "reference"}, {"o", "output"}, {"t", "threads"}};
-    const std::vector<std::string> known = {"reference", "output", "threads", "groups", "all", "keep-others", "file-order", "device", "layout", "help"};
-    for (int i = 2; i < argc; ++i) {
-        const std::string s = argv[i];
-        if (s.rfind("--", 0) != 0) continue;
-        const std::string key = s.substr(2, s.find('=') == std::string::npos ? std::string::npos : s.find('=') - 2);
-        if (std::find(known.begin(), known.end(), key) == known.end()) { fprintf(stderr, "error: unexpected argument '--%s'\n", key.c_str()); return 2; }
-    }
-    if (!parse(argc, argv, 2, alias, {"keep-others", "file-order", "help"}, a, err)) { fprintf(stderr, "error: %s\n", err.c_str()); return 2; }
-    if (a.flags.count("help")) { usage(); return 0; }
-    if (!a.kv.count("reference") || !a.kv.count("output")) {
-        fprintf(stderr, "error: the following required arguments were not provided:\n%s%s", a.kv.count("reference") ? "" : "  --reference <prefix>\n",
-                a.kv.count("output") ? "" : "  --output <prefix>\n");
-        return 2;
-    }
-    if (a.kv.count("groups") && a.kv.count("all")) { fprintf(stderr, "error: --groups cannot be used with --all (a list of groups or one group of everything, not both)\n"); return 2; }
-    if (!a.kv.count("groups") && !a.kv.count("all")) { fprintf(stderr, "error: one of --groups <file> and --all <name> is required\n"); return 2; }
-    if (a.kv.count("all") && a.flags.count("keep-others")) { fprintf(stderr, "error: --keep-others cannot be used with --all (--all leaves no others)\n"); return 2; }
-    if (a.kv.count("all") && a.kv["all"].empty()) { fprintf(stderr, "error: invalid value '' for --all: a name is required\n"); return 2; }
+    if (!a.parse(argc, argv, MERGE)) return 2;
+    if (a.has("help")) { usage(); return 0; }
     MergeOptions opt;
-    opt.side.ref_prefix = opt.side.query_prefix = a.kv["reference"];
-    opt.output = a.kv["output"];
-    if (a.kv.count("groups")) opt.groups_file = a.kv["groups"];
-    if (a.kv.count("all")) opt.all_name = a.kv["all"];
-    opt.keep_others = a.flags.count("keep-others") != 0;
-    opt.side.file_order = a.flags.count("file-order") != 0;
-    uint64_t threads = std::thread::hardware_concurrency(), dev = 0;
-    if (a.kv.count("threads") && !to_u64(a.kv["threads"], threads)) { fprintf(stderr, "error: invalid value for --threads\n"); return 2; }
-    if (a.kv.count("device") && !to_u64(a.kv["device"], dev)) { fprintf(stderr, "error: invalid value for --device\n"); return 2; }
-    opt.side.threads = (int)std::max<uint64_t>(1, threads);
-    opt.side.device = (int)dev;
-    err = layout_from_option(a.kv.count("layout") ? a.kv["layout"] : "", opt.side.layout);
-    if (!err.empty()) { fprintf(stderr, "error: %s\n", err.c_str()); return 2; }
-    err = run_merge(opt);
-    if (!err.empty()) { fprintf(stderr, "Error: %s\n", err.c_str()); return 1; }
-    printf("Merged sketches written.\n");
-    return 0;
+    if (!a.require({{"reference", "prefix"}, {"output", "prefix"}}) || !groups_or_all(a, true, opt.groups_file, opt.all_name) ||
+        !threads_device_order(a, opt.side) || !layout_option(a, opt.side.layout))
+        return 2;
+    opt.side.ref_prefix = opt.side.query_prefix = a.str("reference");
+    opt.output = a.str("output");
+    opt.keep_others = a.has("keep-others");
+    return finish(run_merge(opt), "Merged sketches written.\n");
 }
 
-// lash spectrum -r PREFIX -o OUT [--groups FILE | --all NAME] [--core F] [--cloud F] [--curves] [--file-order] [--device D] [--layout SPEC] [-t N]
 int cmd_spectrum(int argc, char **argv)
 {
     Args a;
-    std::string err;
-    const std::map<std::string, std::string> alias = {{"r", "reference"}, {"o", "output"}, {"t", "threads"}};
-    const std::vector<std::string> known = {"reference", "output", "threads", "groups", "all", "core", "cloud", "curves", "file-order", "device", "layout", "help"};
-    for (int i = 2; i < argc; ++i) {
-        const std::string s = argv[i];
-        if (s.rfind("--", 0) != 0) continue;
-        const std::string key = s.substr(2, s.find('=') == std::string::npos ? std::string::npos : s.find('=') - 2);
-        if (std::find(known.begin(), known.end(), key) == known.end()) { fprintf(stderr, "error: unexpected argument '--%s'\n", key.c_str()); return 2; }
-    }
-    if (!parse(argc, argv, 2, alias, {"curves", "file-order", "help"}, a, err)) { fprintf(stderr, "error: %s\n", err.c_str()); return 2; }
-    if (a.flags.count("help")) { usage(); return 0; }
-    if (!a.kv.count("reference") || !a.kv.count("output")) {
-        fprintf(stderr, "error: the following required arguments were not provided:\n%s%s", a.kv.count("reference") ? "" : "  --reference <prefix>\n",
-                a.kv.count("output") ? "" : "  --output <prefix>\n");
-        return 2;
-    }
-    if (a.kv.count("groups") && a.kv.count("all")) { fprintf(stderr, "error: --groups cannot be used with --all (a list of groups or one group of everything, not both)\n"); return 2; }
-    if (a.kv.count("all") && a.kv["all"].empty()) { fprintf(stderr, "error: invalid value '' for --all: a name is required\n"); return 2; }
+    if (!a.parse(argc, argv, SPECTRUM)) return 2;
+    if (a.has("help")) { usage(); return 0; }
     SpectrumOptions opt;
-    for (const char *key : {"core", "cloud"}) {
-        if (!a.kv.count(key)) continue;
-        const std::string &v = a.kv[key];
-        char *e = nullptr;
-        const double f = v.empty() ? NAN : strtod(v.c_str(), &e);
-        if (!e || *e != 0 || !(f > 0.0 && f <= 1.0)) { fprintf(stderr, "error: invalid value '%s' for --%s: a number in (0, 1] is required\n", v.c_str(), key); return 2; }
-        (std::string(key) == "core" ? opt.core : opt.cloud) = f;
-    }
-    err = check_fractions(opt.core, opt.cloud);
+    const auto fraction = [](double f) { return f > 0.0 && f <= 1.0; };
+    if (!a.require({{"reference", "prefix"}, {"output", "prefix"}}) || !groups_or_all(a, false, opt.groups_file, opt.all_name) ||
+        !a.real("core", opt.core, fraction, "a number in (0, 1] is required") || !a.real("cloud", opt.cloud, fraction, "a number in (0, 1] is required"))
+        return 2;
+    const std::string err = check_fractions(opt.core, opt.cloud);
     if (!err.empty()) { fprintf(stderr, "error: %s (--core %g, --cloud %g)\n", err.c_str(), opt.core, opt.cloud); return 2; }
-    opt.side.ref_prefix = opt.side.query_prefix = a.kv["reference"];
-    opt.output = a.kv["output"];
-    if (a.kv.count("groups")) opt.groups_file = a.kv["groups"];
-    if (a.kv.count("all")) opt.all_name = a.kv["all"];
-    opt.curves = a.flags.count("curves") != 0;
-    opt.side.file_order = a.flags.count("file-order") != 0;
-    uint64_t threads = std::thread::hardware_concurrency(), dev = 0;
-    if (a.kv.count("threads") && !to_u64(a.kv["threads"], threads)) { fprintf(stderr, "error: invalid value for --threads\n"); return 2; }
-    if (a.kv.count("device") && !to_u64(a.kv["device"], dev)) { fprintf(stderr, "error: invalid value for --device\n"); return 2; }
-    opt.side.threads = (int)std::max<uint64_t>(1, threads);
-    opt.side.device = (int)dev;
-    err = layout_from_option(a.kv.count("layout") ? a.kv["layout"] : "", opt.side.layout);
-    if (!err.empty()) { fprintf(stderr, "error: %s\n", err.c_str()); return 2; }
-    err = run_spectrum(opt);
-    if (!err.empty()) { fprintf(stderr, "Error: %s\n", err.c_str()); return 1; }
-    printf("Spectrum tables written.\n");
-    return 0;
+    if (!threads_device_order(a, opt.side) || !layout_option(a, opt.side.layout)) return 2;
+    opt.side.ref_prefix = opt.side.query_prefix = a.str("reference");
+    opt.output = a.str("output");
+    opt.curves = a.has("curves");
+    return finish(run_spectrum(opt), "Spectrum tables written.\n");
 }
 
-// lash screen -r DB_PREFIX -q SAMPLE_PREFIX -o FILE [--max-dist D] [--keep-losers] [-m 0|1] [--file-order] [--block-rows N] [--device D] [--layout SPEC] [-t N]
 int cmd_screen(int argc, char **argv)
 {
     Args a;
-    std::string err;
-    const std::map<std::string, std::string> alias = {{"r", "reference"}, {"q", "query"}, {"o", "output"}, {"t", "threads"}, {"m", "model"}};
-    const std::vector<std::string> known = {"reference", "query", "output", "threads", "model", "max-dist", "keep-losers", "file-order", "block-rows",
-                                            "device", "layout", "help"};
-    for (int i = 2; i < argc; ++i) {
-        const std::string s = argv[i];
-        if (s.rfind("--", 0) != 0) continue;
-        const std::string key = s.substr(2, s.find('=') == std::string::npos ? std::string::npos : s.find('=') - 2);
-        if (std::find(known.begin(), known.end(), key) == known.end()) { fprintf(stderr, "error: unexpected argument '--%s'\n", key.c_str()); return 2; }
-    }
-    if (!parse(argc, argv, 2, alias, {"keep-losers", "file-order", "help"}, a, err)) { fprintf(stderr, "error: %s\n", err.c_str()); return 2; }
-    if (a.flags.count("help")) { usage(); return 0; }
-    if (!a.kv.count("reference") || !a.kv.count("query") || !a.kv.count("output")) {
-        fprintf(stderr, "error: the following required arguments were not provided:\n%s%s%s", a.kv.count("reference") ? "" : "  --reference <prefix>\n",
-                a.kv.count("query") ? "" : "  --query <prefix>\n", a.kv.count("output") ? "" : "  --output <file>\n");
-        return 2;
-    }
+    if (!a.parse(argc, argv, SCREEN)) return 2;
+    if (a.has("help")) { usage(); return 0; }
     ScreenOptions opt;
-    if (a.kv.count("max-dist")) {
-        const std::string &v = a.kv["max-dist"];
-        char *e = nullptr;
-        const double d = v.empty() ? NAN : strtod(v.c_str(), &e);
-        if (!e || *e != 0 || !check_screen_max_dist(d).empty()) {
-            fprintf(stderr, "error: invalid value '%s' for --max-dist: %s\n", v.c_str(), check_screen_max_dist(NAN).c_str());
-            return 2;
-        }
-        opt.has_max_dist = true;
-        opt.max_dist = d;
-    }
-    uint64_t model = 1, threads = std::thread::hardware_concurrency(), dev = 0, block_rows = 0;
-    if (a.kv.count("model") && (!to_u64(a.kv["model"], model) || model > 1)) {
-        fprintf(stderr, "error: invalid value '%s' for --model: 0 or 1 is required\n", a.kv["model"].c_str());
+    uint64_t model = 1, block_rows = 0;
+    if (!a.require({{"reference", "prefix"}, {"query", "prefix"}, {"output", "file"}}) ||
+        !a.real("max-dist", opt.max_dist, [](double d) { return check_screen_max_dist(d).empty(); }, check_screen_max_dist(NAN)) ||
+        !a.u64("model", model, 0, 1, "0 or 1 is required") || !a.u64("block-rows", block_rows) || !threads_device_order(a, opt.side) ||
+        !layout_option(a, opt.side.layout))
         return 2;
-    }
-    if (a.kv.count("block-rows") && !to_u64(a.kv["block-rows"], block_rows)) { fprintf(stderr, "error: invalid value for --block-rows\n"); return 2; }
-    if (a.kv.count("threads") && !to_u64(a.kv["threads"], threads)) { fprintf(stderr, "error: invalid value for --threads\n"); return 2; }
-    if (a.kv.count("device") && !to_u64(a.kv["device"], dev)) { fprintf(stderr, "error: invalid value for --device\n"); return 2; }
-    opt.side.ref_prefix = a.kv["reference"];
-    opt.side.query_prefix = a.kv["query"];
-    opt.output = a.kv["output"];
-    opt.keep_losers = a.flags.count("keep-losers") != 0;
+    opt.has_max_dist = a.has("max-dist");
+    opt.side.ref_prefix = a.str("reference");
+    opt.side.query_prefix = a.str("query");
+    opt.output = a.str("output");
+    opt.keep_losers = a.has("keep-losers");
     opt.side.model = (int)model;
     opt.side.block_rows = (uint32_t)std::min<uint64_t>(block_rows, 0xFFFFFFFFull);
-    opt.side.threads = (int)std::max<uint64_t>(1, threads);
-    opt.side.device = (int)dev;
-    opt.side.file_order = a.flags.count("file-order") != 0;
-    err = layout_from_option(a.kv.count("layout") ? a.kv["layout"] : "", opt.side.layout);
-    if (!err.empty()) { fprintf(stderr, "error: %s\n", err.c_str()); return 2; }
-    err = run_screen(opt);
-    if (!err.empty()) { fprintf(stderr, "Error: %s\n", err.c_str()); return 1; }
-    printf("Screen table written.\n");
-    return 0;
+    return finish(run_screen(opt), "Screen table written.\n");
 }
 
 int cmd_hll_bias(int argc, char **argv)
 {
     Args a;
-    std::string err;
-    const std::map<std::string, std::string> alias = {{"o", "output"}, {"p", "precision"}};
-    if (!parse(argc, argv, 2, alias, {"help"}, a, err)) { fprintf(stderr, "error: %s\n", err.c_str()); return 2; }
-    if (a.flags.count("help")) { usage(); return 0; }
-    if (!a.kv.count("output")) { fprintf(stderr, "error: the following required arguments were not provided:\n  --output <file>\n"); return 2; }
+    if (!a.parse(argc, argv, HLL_BIAS)) return 2;
+    if (a.has("help")) { usage(); return 0; }
+    if (!a.require({{"output", "file"}})) return 2;
     HllBiasOptions opt;
-    opt.output = a.kv["output"];
+    opt.output = a.str("output");
     uint64_t points = 0, trials = 0, dev = 0;
-    if (a.kv.count("precision")) {
-        const std::string &l = a.kv["precision"];
-        size_t at = 0;
-        while (at <= l.size()) {
-            const size_t c = l.find(',', at);
-            uint64_t p = 0;
-            if (!to_u64(l.substr(at, c == std::string::npos ? std::string::npos : c - at), p) || p < 4 || p > 18) {
-                fprintf(stderr, "error: invalid value '%s' for --precision: a list of integers from 4 to 18 is required\n", l.c_str());
-                return 2;
-            }
-            for (int q : opt.ps)
-                if (q == (int)p) { fprintf(stderr, "error: invalid value '%s' for --precision: %d is named twice\n", l.c_str(), q); return 2; }
-            opt.ps.push_back((int)p);
-            if (c == std::string::npos) break;
-            at = c + 1;
-        }
-    } else for (int p = 4; p <= 18; ++p) opt.ps.push_back(p);
-    if (a.kv.count("points") && (!to_u64(a.kv["points"], points) || points < 6 || points > 0xFFFFFFFFull)) {
-        fprintf(stderr, "error: invalid value '%s' for --points: an integer of at least 6 is required (the bias is read from the 6 nearest)\n",
-                a.kv["points"].c_str());
+    std::vector<uint64_t> ps;
+    const bool all_in_range = a.u64_list("precision", ps, 4, 18);      // (ps holds the items before the first that is not)
+    for (size_t i = 0; i < ps.size(); ++i)
+        if (std::find(ps.begin(), ps.begin() + i, ps[i]) != ps.begin() + i) { a.invalid("precision", std::to_string(ps[i]) + " is named twice"); return 2; }
+    if (!all_in_range) { a.invalid("precision", "a list of integers from 4 to 18 is required"); return 2; }
+    if (!a.has("precision")) for (int p = 4; p <= 18; ++p) opt.ps.push_back(p);
+    for (uint64_t p : ps) opt.ps.push_back((int)p);
+    if (!a.u64("points", points, 6, 0xFFFFFFFFull, "an integer of at least 6 is required (the bias is read from the 6 nearest)") ||
+        !a.u64("trials", trials, 1, 1u << 20, "an integer from 1 to 1048576 is required") || !a.u64("seed", opt.seed) || !a.u64("device", dev))
         return 2;
-    }
-    if (a.kv.count("trials") && (!to_u64(a.kv["trials"], trials) || trials < 1 || trials > (1u << 20))) {
-        fprintf(stderr, "error: invalid value '%s' for --trials: an integer from 1 to 1048576 is required\n", a.kv["trials"].c_str());
-        return 2;
-    }
-    if (a.kv.count("seed") && !to_u64(a.kv["seed"], opt.seed)) { fprintf(stderr, "error: invalid value for --seed\n"); return 2; }
-    if (a.kv.count("device") && !to_u64(a.kv["device"], dev)) { fprintf(stderr, "error: invalid value for --device\n"); return 2; }
     opt.points = (uint32_t)points;
     opt.trials = (uint32_t)trials;
     opt.device = (int)dev;
-    err = run_hll_bias(opt);
-    if (!err.empty()) { fprintf(stderr, "Error: %s\n", err.c_str()); return 1; }
-    printf("HLL++ bias tables written.\n");
-    return 0;
+    return finish(run_hll_bias(opt), "HLL++ bias tables written.\n");
 }
 
 }  // namespace
